@@ -18,7 +18,9 @@ at 1/2/4/8 MI355X".  Config (weak scaling, fixed per-GPU work):
   data       synthetic (device-generated Gaussian inputs, uniform labels),
              random-init (Xavier) weights; no dataset download exists here
 
-Single GPU:  python bench.py [--steps K --warmup W]
+Single GPU:  python bench.py [--steps K --warmup W]      the headline figure only
+             python bench.py --full                      + everything listed under `--full` below
+             python bench.py --dump-outputs DIR          + what the timed step computes, as .npy
 N GPUs:      python bench.py --gpus N            (spawns `torch.distributed.run` itself, as a
                                                   child process, before any GPU call)
          or  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
@@ -27,9 +29,11 @@ Under a launcher the world size must equal --gpus (checked); with RCCL every ran
 must own a distinct GPU (checked: RCCL refuses two ranks on one device).
 
 Rank 0 prints ONE JSON line; `value` is the whole-job samples/sec (max step time
-over ranks).  Besides the headline it reports, per rank and maxed over ranks:
+over ranks) and `ms_per_step` the milliseconds one timed step took.  A plain run sets up,
+warms up, times `--steps` steps and prints that line, nothing else.  `--full` adds the
+measurements that take runs of their own, per rank and maxed over ranks:
   per_gpu_local_ms     the same engine's comm-free step (world 1, no collectives)
-  scaling_efficiency   per_gpu_local_ms / ms_per_step  (1.0 at N = 1)
+  scaling_efficiency   per_gpu_local_ms / ms_per_step  (1.0 at N = 1; null at N > 1 without --full)
   comm_us              standalone per-bucket reduce-scatter / all-gather times (N > 1)
   configs              BASELINE configs #4/#5 and the reference's own workload at this N:
                        LeNet-5 28x28 b256, ResNet-18 224x224 b64 / b256 (SGD momentum) and
@@ -38,8 +42,18 @@ over ranks).  Besides the headline it reports, per rank and maxed over ranks:
                        bucket reduce-scatters issued between the links of the backward
                        graph chain, sharded optimizer, bf16 weight all-gathers) with its own
                        comm-free local time and scaling efficiency (--no-configs skips)
+`--dump-outputs DIR` writes, after the timed steps, two sets of arrays (rank 0's; see
+dump_outputs): DIR/trajectory/ holds what the last timed step computed -- logits.npy (its
+[batch, classes] logits), loss_stats.npy (loss sum and correct count over the warm-up + timed
+steps), weights_sample.npy and momentum_sample.npy (a fixed, seeded sample of the flat fp32 master
+weights and SGD momentum after it) -- which carries the run's summation-order noise (fp32 atomics;
+1e-4 of the weights' scale after 72 steps); DIR/ itself holds the same arrays (and
+sample_index.npy, the sampled flat offsets) of that step run once more, untimed, from the seeded
+initial weights, which repeat from run to run.  Weights and batches are seeded, so equal arguments
+give equal inputs.
 `--compare-stock` also times a stock PyTorch-ROCm eager implementation
-(nn.Linear + DDP + torch.optim.SGD) of the headline config.
+(nn.Linear + DDP + torch.optim.SGD) of the headline config; it was opt-in before `--full`
+existed and stays a flag of its own (`--full` runs what a default run used to run).
 """
 from __future__ import annotations
 
@@ -158,6 +172,8 @@ def run_ldnn(ctx, args):
     if ctx.distributed:
         dist.broadcast(eng.flat.master, src=0)
         eng.flat.refresh_shadow()
+    # --dump-outputs: the seeded initial weights (the momentum starts at zero, the step count at 0)
+    master0 = eng.flat.master.detach().clone() if args.dump_outputs else None
     # synthetic batches generated once, each straight into its own input slot of the
     # engine (a prefetching loader's layout): the step reads it in place, no copy
     slots = fill_slots(eng, args, 17 + ctx.rank)
@@ -169,7 +185,11 @@ def run_ldnn(ctx, args):
     loss, acc = eng.read_stats(args.batch * (args.steps + args.warmup))
     extra = dict(train_loss=round(loss, 4), n_params=sum(p.numel() for p in model.parameters()),
                  buckets=len(eng.buckets), gemm_kernels=eng.describe())
-    if ctx.world_size > 1:
+    if args.dump_outputs:
+        dump_outputs(ctx, eng, master0, 1 + (args.warmup + args.steps - 1) % len(slots), args.dump_outputs)
+    if ctx.world_size > 1 and not args.full:
+        extra["local_s"] = None   # the comm-free engine is a run of its own: --full
+    elif ctx.world_size > 1:
         extra["comm_us"] = comm_micro(ctx, eng)
         # the same engine without any collective: this rank's comm-free step time
         torch.manual_seed(1234)
@@ -186,6 +206,67 @@ def run_ldnn(ctx, args):
         extra["local_s"] = timed(ctx, lstep, args.steps, args.warmup)
         del loc
     return el, extra
+
+
+DUMP_SAMPLE = 2 << 20   # sampled elements of the flat weights / momentum (8 MB each as fp32)
+
+
+def _step_arrays(eng, idx):
+    """The arrays a step leaves with its caller: its logits, the loss statistics [loss sum,
+    correct count] accumulated since reset_stats(), and the sampled fp32 master weights and
+    momentum (every rank calls this: gather_master is a collective when the optimizer is sharded)."""
+    eng.gather_master()
+    eng.sync()
+    torch.cuda.synchronize()
+    arrays = {
+        "logits": eng.h[-1][:, : eng.num_classes].float().cpu().numpy(),
+        "loss_stats": eng.stats.double().sum(0).cpu().numpy(),
+        "weights_sample": eng.flat.master.detach().float().cpu()[idx].numpy(),
+    }
+    if eng.mom is not None:
+        arrays["momentum_sample"] = eng.mom.float().cpu()[idx].numpy()
+    return arrays
+
+
+def dump_outputs(ctx, eng, master0, slot, out_dir):
+    """Two sets of float32 / float64 .npy files (rank 0 writes; ~52 MB in all), each the logits,
+    the loss statistics and a fixed, seeded sample (sample_index.npy) of the fp32 master weights
+    and momentum (the whole flat buffers are 80 MB each):
+
+    DIR/trajectory/<name>.npy   the last timed step as it ran: its logits, the statistics summed
+        over the warm-up + timed steps, weights and momentum after it.  Everything the run carried
+        from step to step is in here -- and so is its noise: the bias and head weight gradients are
+        summed with fp32 atomics, whose order varies, and over the steps one bf16 rounding flip
+        grows (measured between two runs of one build after 72 steps: 1e-4 of the weights' scale,
+        5e-3 to 7e-3 of the momentum's, one bf16 ulp of the logits, 1e-4 of the correct count).  Compare
+        these with tolerances of that size.
+    DIR/<name>.npy              the same step -- the same engine, captured graph and input slot --
+        run once more, untimed, from the run's seeded initial weights `master0`, zero momentum and
+        step count 0.  From equal weights the logits and statistics are equal bit for bit and the
+        updated weights and momentum differ by the fp32 rounding of the atomic sums at most
+        (measured: 1e-9 / 4e-9), so these repeat from run to run and compare output for output."""
+    import numpy as np
+
+    n = eng.flat.master.numel()
+    idx = torch.randint(0, n, (min(n, DUMP_SAMPLE),), generator=torch.Generator().manual_seed(20240229))
+    idx = torch.sort(idx).values
+    sets = {"trajectory": _step_arrays(eng, idx)}
+    with torch.no_grad():
+        eng.flat.master.copy_(master0)
+        if eng.mom is not None:
+            eng.mom.zero_()
+    eng.flat.refresh_shadow()
+    eng.load_optimizer_state({"step": 0.0})
+    eng.reset_stats()
+    eng.step(slot=slot)
+    sets[""] = dict(_step_arrays(eng, idx), sample_index=idx.double().numpy())
+    if not ctx.is_main:
+        return
+    for sub, arrays in sets.items():
+        os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+        for name, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            np.save(os.path.join(out_dir, sub, name + ".npy"), a)
 
 
 def comm_micro(ctx, eng, iters: int = 10) -> dict:
@@ -419,12 +500,20 @@ def main():
                     help="separate head dgrad GEMM instead of the head kernel's fused dgrad (dReLU + dbias)")
     ap.add_argument("--head-dgrad-mode", type=int, default=-1,
                     help="-1 auto (streaming dh kernel for <= 16 classes), 1 fused (h re-read), 2 fused (h in LDS)")
-    ap.add_argument("--compare-stock", action="store_true")
+    ap.add_argument("--compare-stock", action="store_true",
+                    help="also time a stock PyTorch-ROCm eager implementation (opt-in, not part of --full)")
     ap.add_argument("--backend", default="auto", help="auto (nccl = RCCL on GPUs) | gloo (testing only)")
     ap.add_argument("--grad-comm", choices=["bf16", "fp32"], default="bf16",
                     help="gradient reduce-scatter dtype at N > 1 (bf16: half the xGMI bytes, widened into the "
                          "fp32 shard of the sharded optimizer)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the LeNet-5 / ResNet-18 config timings")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the LeNet-5 / ResNet-18 / EnhancedCNN config timings and, at N > 1, "
+                         "the comm-free local step (scaling efficiency) and the per-bucket collective times")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the LeNet-5 / ResNet-18 / EnhancedCNN config timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/trajectory/<name>.npy "
+                         "and what the same step computes from the seeded initial weights to DIR/<name>.npy")
     args = ap.parse_args()
     GRAD_COMM["dtype"] = args.grad_comm
 
@@ -448,7 +537,7 @@ def main():
         if ctx.backend == "nccl" and len(set(comm_info["devices"])) != n:
             raise SystemExit(f"bench.py: RCCL ranks share a GPU: {comm_info['devices']}")
     el, extra = run_ldnn(ctx, args)
-    local_s = extra.pop("local_s", el)
+    local_s = extra.pop("local_s", el)   # None: N > 1 without --full
     comm = "RCCL" if ctx.backend == "nccl" else ctx.backend
     ms = el / args.steps * 1e3
     value = args.batch * n * args.steps / el
@@ -487,13 +576,13 @@ def main():
             "grad_comm_dtype": None if n == 1 else ("fp32" if args.no_shard else args.grad_comm),
         },
     }
-    rec["per_gpu_local_ms"] = round(local_s / args.steps * 1e3, 4)
-    rec["scaling_efficiency"] = round(local_s / el, 4)
+    rec["per_gpu_local_ms"] = None if local_s is None else round(local_s / args.steps * 1e3, 4)
+    rec["scaling_efficiency"] = None if local_s is None else round(local_s / el, 4)
     rec["rccl_ranks"] = n if ctx.backend == "nccl" else 0
     from ldnn.ops import _ext
     rec["native_build"] = _ext.build_info()   # which _C.so ran, and whether it matches this tree's sources
     rec.update(extra)
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         rec["configs"] = run_configs(ctx, CNN_CONFIGS, run_cnn)
     if args.compare_stock:
         el_s = run_stock(ctx, args)
