@@ -59,6 +59,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd"])
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--clip_grad_norm", type=float, default=0.0,
+                   help="clip the gradient by its global L2 norm (torch clip_grad_norm_ semantics) inside the fused "
+                        "optimizer, and skip a step whose norm is not finite; 0 (default) = off.  metrics.jsonl then "
+                        "logs grad_norm_last / grad_clipped_steps / grad_skipped_steps per global epoch")
     p.add_argument("--step_size", type=int, default=25, help="StepLR step (local epochs), BAR/main.py:54")
     p.add_argument("--gamma", type=float, default=0.1)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
@@ -96,6 +100,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resume", type=str, default=None, help="checkpoint path or 'latest'")
     p.add_argument("--timeout", type=float, default=600.0, help="collective timeout (s): failure detection")
     p.add_argument("--no_eval", action="store_true")
+    p.add_argument("--log_weights_digest", action="store_true",
+                   help="end every rank's metrics file with a final_weights record: the sha256 of that rank's "
+                        "state_dict (replicas of a per-step all-reduce run must report the same one)")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--graphs", dest="graphs", action="store_true", default=True,
                    help="(default) on a GPU, replay each training step from hipGraphs; with --sync_every step the "
@@ -122,21 +129,43 @@ def resolve_replace(flag: str, fixed_ratio, topology: str) -> bool:
     return flag == "on"
 
 
+def native_gpu(dev) -> bool:
+    """The native extension serves this device (what the static engine needs)."""
+    from .ops import _ext
+
+    return dev.type == "cuda" and _ext.use_native(torch.empty(0, device=dev))
+
+
+def weights_digest(model) -> str:
+    """sha256 over every state_dict entry (name, dtype, bytes): equal on two ranks exactly when
+    their replicas are bitwise equal."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for k, v in model.state_dict().items():
+        t = v.detach().cpu().contiguous()
+        h.update(f"{k}:{t.dtype}:{tuple(t.shape)}".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())   # (reshape: 0-dim BN counters too)
+    return h.hexdigest()
+
+
 def resolve_engine(args, model, dev, world: int) -> bool:
     """--engine auto|autograd|static -> run the static MLP engine?"""
     from .models.mlp import MLP
-    from .ops import _ext
 
     why = None
     if not isinstance(model, MLP):
         why = f"--model {args.model} is not an MLP"
-    elif dev.type != "cuda" or not _ext.use_native(torch.empty(0, device=dev)):
+    elif not native_gpu(dev):
         why = "the static engine needs the native extension on a GPU"
     elif args.grad_comm_dtype != "fp32":
         why = "--grad_comm_dtype bf16 runs on the autograd path"
     elif args.legacy_gossip and args.sync_every == "step" and args.topology != "allreduce" and world > 1:
         # the static engine's grad_mix always applies the combine (no reference-Q2 mode)
         why = "--legacy_gossip runs on the autograd path"
+    elif getattr(args, "clip_grad_norm", 0.0) > 0:
+        # the static engine's wgrad-fused optimizer epilogue cannot wait for a whole-model norm
+        why = "--clip_grad_norm runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -224,7 +253,8 @@ def main(argv=None):
 
     criterion = CrossEntropyLoss()
     if not use_engine:
-        optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay)
+        optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
+                                    max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None)
     scheduler = StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
 
     os.makedirs(args.out_dir, exist_ok=True)
@@ -283,6 +313,10 @@ def main(argv=None):
             for k, v in sorted(phases.items(), key=lambda kv: -kv[1]["total_ms"]):
                 print(f"[rank {rank}] {k:10s} {v['total_ms']:10.2f} ms total  {v['mean_ms']:8.3f} ms x {v['count']}")
 
+    if args.log_weights_digest:
+        # this rank's final replica as a digest in its own metrics file (train_global left the
+        # master whole)
+        logger.log(kind="final_weights", sha256=weights_digest(model))
     result = {"histories": [list(h) if not isinstance(h, list) else h for h in histories]}
     if rank == 0 and not args.no_eval:
         loss, acc, _, _ = evaluate(net, test_loader, criterion, dev, rank, num_classes=trainset.num_classes,

@@ -504,11 +504,62 @@ ldnn::GradZero grad_zero(const std::vector<std::pair<int64_t, int64_t>>& r, int6
   return z;
 }
 
+// the global-norm clipping state an update reads (nullptr: unclipped)
+const float* clip_ptr(const c10::optional<at::Tensor>& clip, const at::Tensor& like) {
+  if (!clip.has_value()) return nullptr;
+  check_dev(*clip, at::kFloat, "clip");
+  TORCH_CHECK(clip->is_contiguous() && clip->numel() >= ldnn::kClipState && clip->device() == like.device(),
+              "optimizer: clip must be a contiguous fp32 state of ", (int)ldnn::kClipState,
+              " elements on the parameters' device");
+  return clip->data_ptr<float>();
+}
+
+int64_t grad_sumsq(const at::Tensor& grad, const at::Tensor& partials, int64_t slot0) {
+  check_dev(grad, at::kFloat, "grad");
+  check_dev(partials, at::kFloat, "partials");
+  TORCH_CHECK(grad.is_contiguous() && partials.is_contiguous() && grad.device() == partials.device(),
+              "grad_sumsq: grad / partials must be contiguous and on one device");
+  const int64_t n = grad.numel();
+  const int64_t np = ldnn::grad_sumsq_parts(n);
+  TORCH_CHECK(slot0 >= 0 && slot0 + np <= partials.numel(), "grad_sumsq: ", np, " partial slots from ", slot0,
+              " do not fit the scratch of ", partials.numel());
+  check(ldnn::grad_sumsq(grad.data_ptr<float>(), n, partials.data_ptr<float>() + slot0, cur_stream(grad)),
+        "grad_sumsq");
+  return np;
+}
+
+void sumsq_total(const at::Tensor& partials, int64_t nparts, const at::Tensor& out) {
+  check_dev(partials, at::kFloat, "partials");
+  check_dev(out, at::kFloat, "out");
+  TORCH_CHECK(partials.is_contiguous() && nparts >= 0 && nparts <= partials.numel() && out.numel() >= 1 &&
+                  out.device() == partials.device(),
+              "sumsq_total: bad partials / out");
+  check(ldnn::sumsq_total(partials.data_ptr<float>(), (int)nparts, out.data_ptr<float>(), cur_stream(partials)),
+        "sumsq_total");
+}
+
+void clip_finalize(const at::Tensor& partials, int64_t nparts, const at::Tensor& state, double grad_scale,
+                   const c10::optional<at::Tensor>& ext) {
+  check_dev(partials, at::kFloat, "partials");
+  TORCH_CHECK(partials.is_contiguous() && nparts >= 0 && nparts <= partials.numel(),
+              "clip_finalize: nparts exceeds the scratch");
+  const float* st = clip_ptr(state, partials);
+  const float* ep = nullptr;
+  if (ext.has_value()) {
+    check_dev(*ext, at::kFloat, "ext");
+    TORCH_CHECK(ext->numel() >= 1 && ext->device() == partials.device(), "clip_finalize: bad ext");
+    ep = ext->data_ptr<float>();
+  }
+  check(ldnn::clip_finalize(partials.data_ptr<float>(), (int)nparts, ep, const_cast<float*>(st), (float)grad_scale,
+                            cur_stream(partials)),
+        "clip_finalize");
+}
+
 void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& mom,
               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double momentum,
               double dampening, double weight_decay, bool nesterov, bool first_step,
               const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, int64_t t_begin,
-              const c10::optional<at::Tensor>& t_out) {
+              const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip) {
   check_dev(param, at::kFloat, "param");
   check_dev(grad, at::kFloat, "grad");
   check_dev(hp, at::kFloat, "hp");
@@ -542,14 +593,15 @@ void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor&
     tr.out = bf16_mut(*t_out);
   }
   check(ldnn::sgd_step(param.data_ptr<float>(), grad.data_ptr<float>(), mp, sh, hp.data_ptr<float>(),
-                       (float)grad_scale, sp, n, cur_stream(param), t_out.has_value() ? &tr : nullptr),
+                       (float)grad_scale, sp, n, cur_stream(param), t_out.has_value() ? &tr : nullptr,
+                       clip_ptr(clip, param)),
         "sgd_step");
 }
 
 void adam_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double beta1,
                double beta2, double eps, double weight_decay, bool decoupled,
-               const std::vector<std::pair<int64_t, int64_t>>& zero_ranges) {
+               const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, const c10::optional<at::Tensor>& clip) {
   check_dev(param, at::kFloat, "param");
   check_dev(grad, at::kFloat, "grad");
   check_dev(m, at::kFloat, "exp_avg");
@@ -568,7 +620,7 @@ void adam_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor
   ldnn::AdamParams ap{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, decoupled ? 1 : 0,
                       grad_zero(zero_ranges, n)};
   check(ldnn::adam_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                        sh, hp.data_ptr<float>(), (float)grad_scale, ap, n, cur_stream(param)),
+                        sh, hp.data_ptr<float>(), (float)grad_scale, ap, n, cur_stream(param), clip_ptr(clip, param)),
         "adam_step");
 }
 
@@ -810,9 +862,10 @@ void head_wgrad(const at::Tensor& dz, const at::Tensor& h, const at::Tensor& dW,
   check(ldnn::head_wgrad(p, (int)splits, cur_stream(h)), "head_wgrad");
 }
 
-void bump_step(const at::Tensor& hp) {
+void bump_step(const at::Tensor& hp, const c10::optional<at::Tensor>& clip) {
   check_dev(hp, at::kFloat, "hp");
-  check(ldnn::bump_step(hp.data_ptr<float>(), cur_stream(hp)), "bump_step");
+  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2, "bump_step: hp must hold [lr, step]");
+  check(ldnn::bump_step(hp.data_ptr<float>(), cur_stream(hp), clip_ptr(clip, hp)), "bump_step");
 }
 
 void synth_normal(const at::Tensor& x, int64_t seed, double stddev) {
@@ -2011,12 +2064,19 @@ PYBIND11_MODULE(_C, m) {
         py::arg("hp"), py::arg("grad_scale"), py::arg("momentum"), py::arg("dampening"),
         py::arg("weight_decay"), py::arg("nesterov"), py::arg("first_step"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("t_begin") = 0,
-        py::arg("t_out") = py::none());
+        py::arg("t_out") = py::none(), py::arg("clip") = py::none());
   m.def("adam_step", &adam_step, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),
-        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{});
-  m.def("bump_step", &bump_step);
+        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
+  m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
+  m.def("grad_sumsq", &grad_sumsq, "per-workgroup sums of squares of a flat fp32 range into partials[slot0 ...]; "
+        "returns the number of slots written", py::arg("grad"), py::arg("partials"), py::arg("slot0") = 0);
+  m.def("grad_sumsq_parts", &ldnn::grad_sumsq_parts, py::arg("n"));
+  m.def("sumsq_total", &sumsq_total, py::arg("partials"), py::arg("nparts"), py::arg("out"));
+  m.def("clip_finalize", &clip_finalize, "global-norm clipping state (coef / skip / norm / counters) from the "
+        "partials (+ an external sum of squares)", py::arg("partials"), py::arg("nparts"), py::arg("state"),
+        py::arg("grad_scale"), py::arg("ext") = py::none());
   m.def("set_opt_max_blocks", &ldnn::set_opt_max_blocks, py::arg("n"),
         "grid cap of optimizer launches from now on (0 = default)");
   m.def("head_fwd_xent", &head_fwd_xent, "fused narrow Linear + softmax-xent + argmax (per-16-row stats slots)",

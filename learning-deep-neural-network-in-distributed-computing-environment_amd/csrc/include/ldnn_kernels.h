@@ -390,17 +390,48 @@ struct ShadowT {
   int rows = 0, cols = 0;
   uint16_t* out = nullptr;
 };
+// clip (optional, device fp32 [kClipState]): the global-norm clipping state clip_finalize wrote.
+// The update multiplies grad_scale by clip[kClipCoef]; with clip[kClipSkip] set it touches no
+// master / state / shadow element and only clears the requested gradient zero ranges.
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
-                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr = nullptr);
+                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr = nullptr,
+                    const float* clip = nullptr);
 struct AdamParams {
   float beta1, beta2, eps, weight_decay;
   int decoupled;  // AdamW
   GradZero zero;
 };
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
-                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s);
-// hp[1] += 1 (graph-capturable step counter)
-hipError_t bump_step(float* hp, hipStream_t s);
+                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip = nullptr);
+// hp[1] += 1 (graph-capturable step counter); with clip: not on a skipped step
+hipError_t bump_step(float* hp, hipStream_t s, const float* clip = nullptr);
+
+// ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ semantics) ----
+// Device state (fp32): max_norm is WRITTEN BY THE HOST (like hp[0] = lr, so a captured graph
+// follows a changed threshold), the rest by clip_finalize.  The counters are fp32 (exact to 2^24).
+enum ClipSlot : int {
+  kClipMaxNorm = 0,  // threshold (host)
+  kClipCoef = 1,     // min(1, max_norm / (norm + 1e-6)); 0 on a skipped step
+  kClipSkip = 2,     // 1 when the norm is not finite: the update kernels skip the step
+  kClipNorm = 3,     // last total norm
+  kClipSteps = 4,    // running counts: finalized steps, clipped steps, skipped steps
+  kClipClipped = 5,
+  kClipSkipped = 6,
+  kClipState = 8,
+};
+// workgroups (= partial slots) a grad_sumsq launch over n elements uses under the current grid cap
+int grad_sumsq_parts(int64_t n);
+// partials[slot0 + b] = sum of squares workgroup b saw of grad[0, n) (any element alignment; no
+// atomics: every slot is stored once, so a later fixed-order sum is bit-reproducible)
+// Plain (not nontemporal) loads: the optimizer re-reads the same gradient right after, from the
+// Infinity Cache (A/B of both policies: profiles/r7/grad_clip_ab.jsonl).
+hipError_t grad_sumsq(const float* grad, int64_t n, float* partials, hipStream_t s);
+// *out = (float) sum of partials[0, nparts) in a fixed order, in double (the sharded path's local sum)
+hipError_t sumsq_total(const float* partials, int nparts, float* out, hipStream_t s);
+// norm = grad_scale * sqrt(sum of partials[0, nparts) (+ *ext)); writes coef / skip / norm and
+// bumps the counters of `state`, reading state[kClipMaxNorm]
+hipError_t clip_finalize(const float* partials, int nparts, const float* ext, float* state, float grad_scale,
+                         hipStream_t s);
 
 // ---- classifier head (<= 64 classes): fused Linear + softmax-xent, and its wgrad
 struct HeadParams {

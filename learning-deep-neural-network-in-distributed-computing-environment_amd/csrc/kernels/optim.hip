@@ -52,6 +52,26 @@ __device__ __forceinline__ void clear4(const GradZero& z, float* grad, int64_t i
   }
 }
 
+// CLIP: the kernel also takes the global-norm clipping state (ldnn_kernels.h ClipSlot).  The
+// CLIP = false instances carry an empty argument and compile to the unclipped code.
+template <bool CLIP>
+struct ClipArg {
+  const float* st;
+};
+template <>
+struct ClipArg<false> {};
+
+// a skipped (non-finite norm) step: only the requested gradient zero ranges are cleared
+__device__ __forceinline__ void clear_only(const GradZero& z, float* grad, int64_t n) {
+  if (z.ze[0] <= z.zb[0] && z.ze[1] <= z.zb[1]) return;
+  const int64_t nv = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = t0; i < nv; i += stride) clear4(z, grad, i);
+  for (int64_t i = nv * 4 + t0; i < n; i += stride)
+    if (in_zero(z, i)) grad[i] = 0.f;
+}
+
 // one float4 of the SGD(-momentum) update: master, momentum, gradient clear; returns the
 // new bf16 shadow values
 template <bool NT>
@@ -79,10 +99,17 @@ __device__ __forceinline__ u16x4 sgd4(float* __restrict__ param, float* __restri
 // that matrix one 64 x 64 tile each and write the transposed tile through LDS; the rest
 // stride over the remaining elements -- one launch instead of the update plus a
 // transpose pass that re-reads the 32 MB shadow.
-template <bool NT, bool TR>
+template <bool NT, bool TR, bool CLIP>
 __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mom,
                            bf16_t* __restrict__ shadow, const float* __restrict__ hp, float grad_scale,
-                           SgdParams sp, int64_t n, ShadowT tr) {
+                           SgdParams sp, int64_t n, ShadowT tr, ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) {
+      clear_only(sp.zero, grad, n);
+      return;
+    }
+    grad_scale *= clip.st[kClipCoef];
+  }
   const float lr = hp[0];
   const int64_t nv = n / 4;
   int64_t bid = blockIdx.x, nblk = gridDim.x, skip_b = 0, skip_n = 0;
@@ -153,10 +180,17 @@ __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v,
   return p - (lr / bc1) * m / denom;
 }
 
-template <bool NT>
+template <bool NT, bool CLIP>
 __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mm,
                             float* __restrict__ vv, bf16_t* __restrict__ shadow, const float* __restrict__ hp,
-                            float grad_scale, AdamParams ap, int64_t n) {
+                            float grad_scale, AdamParams ap, int64_t n, ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) {
+      clear_only(ap.zero, grad, n);
+      return;
+    }
+    grad_scale *= clip.st[kClipCoef];
+  }
   const float lr = hp[0];
   const float t = hp[1];
   const float bc1 = 1.f - powf(ap.beta1, t);
@@ -193,6 +227,84 @@ __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
 }
 
 __global__ void bump_kernel(float* hp) { hp[1] += 1.f; }
+// (a skipped step does not advance Adam's step count)
+__global__ void bump_clip_kernel(float* hp, const float* __restrict__ clip) {
+  if (clip[kClipSkip] == 0.f) hp[1] += 1.f;
+}
+
+// Sum of squares of g[0, n): float4 loads from the first 16-byte aligned element on (the head
+// and tail scalars are peeled), four independent float4 accumulators per thread, wave64
+// shuffle reduce, cross-wave through LDS; ONE plain store per workgroup and no atomics, so
+// the partials -- and the fixed-order sum over them -- are the same bits on every run.
+__global__ void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partials) {
+  const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+  int64_t head = (4 - mis) & 3;
+  if (head > n) head = n;
+  const float* gb = g + head;
+  const int64_t nv = (n - head) / 4;
+  const int64_t tail0 = head + nv * 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  floatx4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+  int64_t i = t0;
+  for (; i + 3 * stride < nv; i += 4 * stride) {
+    const floatx4 v0 = ld4<false>(gb, i), v1 = ld4<false>(gb, i + stride), v2 = ld4<false>(gb, i + 2 * stride),
+                  v3 = ld4<false>(gb, i + 3 * stride);
+    a0 += v0 * v0;
+    a1 += v1 * v1;
+    a2 += v2 * v2;
+    a3 += v3 * v3;
+  }
+  for (; i < nv; i += stride) {
+    const floatx4 v = ld4<false>(gb, i);
+    a0 += v * v;
+  }
+  a0 = (a0 + a1) + (a2 + a3);
+  float acc = (a0[0] + a0[1]) + (a0[2] + a0[3]);
+  if (t0 < head) acc += g[t0] * g[t0];
+  if (tail0 + t0 < n) acc += g[tail0 + t0] * g[tail0 + t0];
+  acc = wave_sum(acc);
+  static_assert(kBlock == 256, "the cross-wave sum below adds exactly four waves");
+  __shared__ float w[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+// One workgroup.  Fixed summation order: thread t adds its contiguous run of partials in index
+// order, the 256 run sums meet in a fixed binary tree; all in double.
+// sum_out: write the sum alone (the sharded path's local sum); else finalize `state`.
+__global__ void clip_finalize_kernel(const float* __restrict__ partials, int nparts, const float* __restrict__ ext,
+                                     float* __restrict__ state, float grad_scale, float* __restrict__ sum_out) {
+  __shared__ double red[kBlock];
+  const int per = (nparts + kBlock - 1) / kBlock;
+  const int b = threadIdx.x * per;
+  const int e = b + per < nparts ? b + per : nparts;
+  double acc = 0.0;
+  for (int i = b; i < e; ++i) acc += (double)partials[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = kBlock / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  double sum = red[0];
+  if (ext != nullptr) sum += (double)ext[0];
+  if (sum_out != nullptr) {
+    sum_out[0] = (float)sum;
+    return;
+  }
+  const float norm = (float)((double)grad_scale * sqrt(sum));
+  const bool finite = fabsf(norm) <= 3.402823466e38f;  // false for inf and NaN
+  const float c = finite ? fminf(1.f, state[kClipMaxNorm] / (norm + 1e-6f)) : 0.f;
+  state[kClipCoef] = c;
+  state[kClipSkip] = finite ? 0.f : 1.f;
+  state[kClipNorm] = norm;
+  state[kClipSteps] += 1.f;
+  if (finite && c < 1.f) state[kClipClipped] += 1.f;
+  if (!finite) state[kClipSkipped] += 1.f;
+}
 
 
 int g_opt_max_blocks = 2048;  // optimizer grid cap (set_opt_max_blocks: a narrow side-stream update)
@@ -207,7 +319,7 @@ inline int grid_for(int64_t n4) {
 void set_opt_max_blocks(int n) { g_opt_max_blocks = n > 0 ? n : 2048; }
 
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
-                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr) {
+                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr, const float* clip) {
   if (n <= 0) return hipSuccess;
   if (tr != nullptr && tr->out != nullptr) {
     // (the tile path needs whole 64 x 64 tiles and 16-B aligned transposed rows)
@@ -217,23 +329,59 @@ hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, con
     const int64_t ntiles = (int64_t)(tr->rows / 64) * (tr->cols / 64);
     const int64_t rest = (n - (int64_t)tr->rows * tr->cols + 3) / 4;
     const int grid = (int)ntiles + grid_for(rest);
-    sgd_kernel<true, true><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, *tr);
+    if (clip != nullptr)
+      sgd_kernel<true, true, true><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, *tr,
+                                                           ClipArg<true>{clip});
+    else
+      sgd_kernel<true, true, false><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, *tr,
+                                                            ClipArg<false>{});
     return hipGetLastError();
   }
-  sgd_kernel<true, false><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n,
-                                                                     ShadowT{});
+  const int grid = grid_for((n + 3) / 4);
+  if (clip != nullptr)
+    sgd_kernel<true, false, true><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, ShadowT{},
+                                                          ClipArg<true>{clip});
+  else
+    sgd_kernel<true, false, false><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n,
+                                                           ShadowT{}, ClipArg<false>{});
   return hipGetLastError();
 }
 
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
-                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s) {
+                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip) {
   if (n <= 0) return hipSuccess;
-  adam_kernel<true><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n);
+  const int grid = grid_for((n + 3) / 4);
+  if (clip != nullptr)
+    adam_kernel<true, true><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
+                                                    ClipArg<true>{clip});
+  else
+    adam_kernel<true, false><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
+                                                     ClipArg<false>{});
   return hipGetLastError();
 }
 
-hipError_t bump_step(float* hp, hipStream_t s) {
-  bump_kernel<<<1, 1, 0, s>>>(hp);
+hipError_t bump_step(float* hp, hipStream_t s, const float* clip) {
+  if (clip != nullptr) bump_clip_kernel<<<1, 1, 0, s>>>(hp, clip);
+  else bump_kernel<<<1, 1, 0, s>>>(hp);
+  return hipGetLastError();
+}
+
+int grad_sumsq_parts(int64_t n) { return n <= 0 ? 0 : grid_for((n + 3) / 4); }
+
+hipError_t grad_sumsq(const float* grad, int64_t n, float* partials, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  sumsq_kernel<<<grad_sumsq_parts(n), kBlock, 0, s>>>(grad, n, partials);
+  return hipGetLastError();
+}
+
+hipError_t sumsq_total(const float* partials, int nparts, float* out, hipStream_t s) {
+  clip_finalize_kernel<<<1, kBlock, 0, s>>>(partials, nparts, nullptr, nullptr, 1.f, out);
+  return hipGetLastError();
+}
+
+hipError_t clip_finalize(const float* partials, int nparts, const float* ext, float* state, float grad_scale,
+                         hipStream_t s) {
+  clip_finalize_kernel<<<1, kBlock, 0, s>>>(partials, nparts, ext, state, grad_scale, nullptr);
   return hipGetLastError();
 }
 

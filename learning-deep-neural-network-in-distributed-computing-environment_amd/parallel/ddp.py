@@ -196,6 +196,9 @@ class GradBucketer:
         # step_parts(update): set by a caller that interleaves its own work between the
         # buckets' optimizer updates (GraphedDPStep's per-bucket optimizer graphs)
         self.step_parts = None
+        # clip_phases(norm, local, update): the same for a sharded step with global-norm clipping
+        # (the caller captures the two compute phases and issues the scalar all-reduce of `local`)
+        self.clip_phases = None
         flat.add_ready_hook(self._on_ready)
         if self.shard:
             flat.shard_sync = self
@@ -302,6 +305,19 @@ class GradBucketer:
         out = []
         for i, b in enumerate(self.buckets):
             out.append(self.shard_range(i) if b["sharded"] else (b["begin"], b["end"]))
+        return out
+
+    def norm_ranges(self) -> list[tuple[int, int]]:
+        """Flat ranges whose squared gradients THIS rank adds to the global norm: its shard of
+        every sharded bucket, and -- on rank 0 only -- the replicated tail (every rank holds
+        the same reduced tail, so one rank counts it).  Their sums, all-reduced, cover every
+        element of the reduced gradient exactly once."""
+        out = []
+        for i, b in enumerate(self.buckets):
+            if b["sharded"]:
+                out.append(self.shard_range(i))
+            elif self.rank == 0:
+                out.append((b["begin"], b["end"]))
         return out
 
     def after_update(self):

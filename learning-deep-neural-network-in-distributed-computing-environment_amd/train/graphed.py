@@ -178,7 +178,8 @@ class GraphedStep:
         return loss
 
     def _sync_lr(self, force: bool = False):
-        lrs = [g["lr"] for g in self.optimizer.param_groups]
+        # (the clipping threshold travels like the lr: a device scalar the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm")) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -373,6 +374,7 @@ class GraphedDPStep:
         collective right before its update: the deep buckets update while the last
         bucket's reduce-scatter is still in flight.  (self.g_opts: [(graph, bucket or None)])"""
         self.g_opts = []
+        self._clip_local = None
         order = self.bk.opt_order() if (self.bk.shard and isinstance(self.optimizer, _FlatOptimizer)) else None
 
         def begin(i):
@@ -397,6 +399,29 @@ class GraphedDPStep:
                     self.g_opts[-1] = (self.g_opts[-1][0], i)
                 self.bk.post_collective(i)
                 update(*self.bk.update_range(i))
+
+        if self.optimizer._clip_threshold() is not None:
+            # global-norm clipping: no range may update before the whole norm is known, so the
+            # per-bucket graphs give way to a NORM graph (every bucket's widen + this rank's
+            # sums of squares), the host-issued scalar all-reduce, and an UPDATE graph
+            # (finalize the coefficient, step count, every range update)
+            def phases(norm, local, update):
+                begin(None)
+                for i in order:
+                    self.bk.post_collective(i)
+                norm()
+                self.g_opts[-1][0].capture_end()
+                self._clip_local = local
+                begin("clip")
+                update()
+
+            self.bk.clip_phases = phases
+            try:
+                self.optimizer.step()
+            finally:
+                self.bk.clip_phases = None
+            self.g_opts[-1][0].capture_end()
+            return
 
         begin(None)   # (the optimizer's per-step prologue, e.g. Adam's step count, lands in the first)
         self.bk.step_parts = parts
@@ -442,7 +467,8 @@ class GraphedDPStep:
             self._fire(done)
 
     def _sync_lr(self, force: bool = False):
-        lrs = [g["lr"] for g in self.optimizer.param_groups]
+        # (the clipping threshold travels like the lr: a device scalar the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm")) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -487,6 +513,15 @@ class GraphedDPStep:
         # each gather right after its own update -- measured neutral, 0.34-0.35 vs 0.36 ms
         # exposed, and was removed in round 6.)
         for g, i in self.g_opts:
+            if i == "clip":
+                # the norm graph left this rank's sum of squares in a device scalar: one
+                # all-reduce (stream-ordered with RCCL; a host-staged backend reads it after
+                # a synchronize, like its other collectives), then the update graph
+                if host_staged:
+                    torch.cuda.current_stream().synchronize()
+                self.comm.all_reduce(self._clip_local)
+                g.replay()
+                continue
             for k in (list(works) if i is None else [i]):
                 w = works.pop(k, None)
                 if w is not None:

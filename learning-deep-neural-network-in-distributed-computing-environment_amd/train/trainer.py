@@ -431,6 +431,12 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                 augment=getattr(trainloader, "augment", False), augment_val=bool(getattr(val_loader, "mode", 0)),
                 loader_seed=loader_seed(seed, rank, global_epoch + 1))
         if logger is not None:
+            # gradient clipping counters: device scalars, read once per global epoch
+            clip_stats = getattr(optimizer, "grad_clip_stats", lambda: None)()
+            clip_rec = ({} if clip_stats is None else
+                        {"grad_norm_last": float(clip_stats["last_norm"]),
+                         "grad_clipped_steps": int(clip_stats["clipped"]),
+                         "grad_skipped_steps": int(clip_stats["skipped"])})
             logger.log(kind="global_epoch", global_epoch=global_epoch + 1, duration_s=duration,
                        train_loss=H["global_train_losses"][-1], train_acc=H["global_train_accuracies"][-1],
                        val_loss=H["global_val_losses"][-1], val_acc=H["global_val_accuracies"][-1],
@@ -439,7 +445,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                        samples_per_s=total_samples / max(duration, 1e-12),
                        train_samples_per_s_per_rank=[s_ / max(duration, 1e-12) for s_ in samples_per_rank],
                        **({"scaling_efficiency": total_samples / max(duration, 1e-12) / (N * ref_samples_per_s)}
-                          if ref_samples_per_s else {}))
+                          if ref_samples_per_s else {}), **clip_rec)
         if checkpointer is not None:
             checkpointer.save(global_epoch + 1, model, optimizer, scheduler, H,
                               extra=dict(indices_train=np.asarray(indices_train),

@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the ldnn step from one hipGraph (train.graphed)")
     ap.add_argument("--optimizer", choices=["sgd", "adam"], default="sgd",
                     help="sgd = momentum 0.9; adam = the reference config (BAR/main.py:53, lr 1e-3)")
+    ap.add_argument("--clip", type=float, default=0.0,
+                    help="max_grad_norm of the ldnn optimizer (global-norm clipping; 0 = off, 1e30 = the clipped "
+                         "kernels with unchanged math)")
     a = ap.parse_args()
     from ldnn.ops import _ext as _e
 
@@ -54,7 +57,9 @@ def main():
     m = build_model(a.model)
     xavier_init(m)
     ldnn.prepare(m, "cuda")
-    opt = (Adam(m.parameters(), lr=1e-3) if a.optimizer == "adam" else SGD(m.parameters(), lr=0.01, momentum=0.9))
+    kw = dict(max_grad_norm=a.clip) if a.clip > 0 else {}
+    opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
+           else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
     crit = CrossEntropyLoss()
     xb = x.bfloat16()
 
@@ -72,7 +77,7 @@ def main():
             gs(xb, y)
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if not a.no_stock:
         import torch.nn as nn
 

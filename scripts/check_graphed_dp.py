@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--gossip", type=int, default=0,
                     help="1 / 2: per-step ring / double-ring gossip (DataParallel(gossip=...)): the graphed chain "
                          "must give the parameters of the eager bucketed gossip step (replicas differ by design)")
+    ap.add_argument("--clip", type=float, default=0.0,
+                    help="max_grad_norm of the optimizers (global-norm clipping; 0 = off).  With --shard the "
+                         "sharded run must also give the parameters of the unsharded clipped run")
     a = ap.parse_args()
     ctx = D.setup(a.backend)
     N, r, dev = ctx.world_size, ctx.rank, ctx.device
@@ -60,17 +63,20 @@ def main():
     xs.append(xs[0][: N * (B // 2)])
     ys.append(ys[0][: N * (B // 2)])
 
-    def run(world, rank, comm, graphs=True):
+    def run(world, rank, comm, graphs=True, shard=None):
+        shard = a.shard if shard is None else shard
         torch.manual_seed(0)
         m = build_model(a.model)
         xavier_init(m)
         ldnn.prepare(m, dev)
         cd = torch.bfloat16 if a.comm_dtype == "bf16" else None
-        dp = (DataParallel(m, comm, bucket_cap_mb=0.05, shard_optimizer=a.shard, comm_dtype=cd, gossip=a.gossip,
+        dp = (DataParallel(m, comm, bucket_cap_mb=0.05, shard_optimizer=shard, comm_dtype=cd, gossip=a.gossip,
                            local_weight=0.7 if a.gossip == 2 else None)
               if comm is not None else None)
         # (built after the wrapper: sharding re-lays the flat buffers out)
-        opt = SGD(m.parameters(), lr=0.02, momentum=0.9) if a.optimizer == "sgd" else Adam(m.parameters(), lr=1e-3)
+        kw = dict(max_grad_norm=a.clip) if a.clip > 0 else {}
+        opt = (SGD(m.parameters(), lr=0.02, momentum=0.9, **kw) if a.optimizer == "sgd"
+               else Adam(m.parameters(), lr=1e-3, **kw))
         batches = []
         for x, y in zip(xs, ys):
             b = x.shape[0] // world
@@ -79,9 +85,14 @@ def main():
         loss, acc, bl = train_local_epoch(net, ListLoader(batches), CrossEntropyLoss(), opt, dev, graphs=graphs,
                                           dp=dp)
         if dp is not None:
-            if a.shard:
+            if shard:
                 assert dp.sharded and any(b["sharded"] for b in dp.bucketer.buckets)
             dp.gather_master(opt)   # collective: whole fp32 master on every rank
+            comm.check_schedule("end of run", dev if getattr(comm, "device_collectives", False) else None)
+        if a.clip > 0:
+            st = {k: float(v) for k, v in opt.grad_clip_stats().items()}
+            print(f"rank {rank}/{world}: clip stats {st}", flush=True)
+            assert st["steps"] == len(batches) and st["skipped"] == 0 and st["clipped"] > 0, st
         torch.cuda.synchronize()
         return m, bl
 
@@ -105,6 +116,17 @@ def main():
             print("GRAPHED_DP_OK", flush=True)
         D.teardown(ctx)
         return
+    if a.clip > 0 and a.shard:
+        mu, _ = run(N, r, TorchComm(), shard=False)
+        gotu = torch.cat([p.detach().flatten().cpu() for p in mu.parameters()])
+        torch.manual_seed(0)
+        m0 = build_model(a.model)
+        xavier_init(m0)
+        p0 = torch.cat([p.detach().flatten() for p in m0.parameters()])
+        du, dr = (got - p0).double(), (gotu - p0).double()
+        err = (du - dr).norm().item() / max(dr.norm().item(), 1e-12)
+        print(f"rank {r}: clipped sharded vs unsharded relative update difference {err:.3e}", flush=True)
+        ok = ok and err < (2e-2 if a.comm_dtype == "fp32" else 5e-2)
     if a.oneshot:
         c1 = TorchComm()
         os_ = c1.enable_oneshot(4 << 20, device=dev)
