@@ -56,7 +56,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n_train", type=int, default=None)
     p.add_argument("--n_test", type=int, default=None)
     p.add_argument("--data_root", type=str, default="data")
-    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd"])
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars"],
+                   help="lars: SGD-momentum with layer-wise adaptive rate scaling (per-tensor trust ratios)")
+    p.add_argument("--lars_trust", type=float, default=0.001,
+                   help="--optimizer lars: trust coefficient of the ratio trust * |w| / (|g| + wd * |w| + eps).  "
+                        "metrics.jsonl then logs lars_ratio_min / _median / _max per global epoch")
+    p.add_argument("--lars_eps", type=float, default=1e-8)
+    p.add_argument("--lars_adapt_1d", action="store_true",
+                   help="--optimizer lars: also adapt tensors with dim() < 2 (biases, BatchNorm affine)")
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--clip_grad_norm", type=float, default=0.0,
@@ -166,6 +173,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "clip_grad_norm", 0.0) > 0:
         # the static engine's wgrad-fused optimizer epilogue cannot wait for a whole-model norm
         why = "--clip_grad_norm runs on the autograd path"
+    elif getattr(args, "optimizer", None) == "lars":
+        # ... nor for a tensor's whole gradient
+        why = "--optimizer lars runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -254,7 +264,10 @@ def main(argv=None):
     criterion = CrossEntropyLoss()
     if not use_engine:
         optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
-                                    max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None)
+                                    max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,
+                                    **(dict(lars_trust=args.lars_trust, lars_eps=args.lars_eps,
+                                            lars_exclude_1d=not args.lars_adapt_1d)
+                                       if args.optimizer == "lars" else {}))
     scheduler = StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
 
     os.makedirs(args.out_dir, exist_ok=True)

@@ -555,11 +555,78 @@ void clip_finalize(const at::Tensor& partials, int64_t nparts, const at::Tensor&
         "clip_finalize");
 }
 
+int64_t seg_sumsq(const at::Tensor& master, const at::Tensor& grad, const at::Tensor& chunks,
+                  const at::Tensor& partials, const std::vector<std::pair<int64_t, int64_t>>& ranges,
+                  const std::vector<int64_t>& seg_offsets) {
+  check_dev(master, at::kFloat, "master");
+  check_dev(grad, at::kFloat, "grad");
+  check_dev(chunks, at::kInt, "chunks");
+  check_dev(partials, at::kFloat, "partials");
+  const int64_t n = master.numel();
+  TORCH_CHECK(master.is_contiguous() && grad.is_contiguous() && grad.numel() == n && aligned16(master.data_ptr()) &&
+                  aligned16(grad.data_ptr()),
+              "seg_sumsq: master / grad must be contiguous, equally long and 16-byte aligned");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4 && chunks.is_contiguous() && aligned16(chunks.data_ptr()),
+              "seg_sumsq: chunks must be a dense int32 [nchunks][4] table");
+  // the table addresses 64-element blocks: the ranges it was cut from, and the segments, must
+  // start and end on them (and lie inside the buffers)
+  for (const auto& r : ranges)
+    TORCH_CHECK(r.first % 64 == 0 && r.second % 64 == 0 && 0 <= r.first && r.first <= r.second && r.second <= n,
+                "seg_sumsq: range [", r.first, ", ", r.second, ") must be 64-element aligned and inside [0, ", n, ")");
+  for (const int64_t o : seg_offsets)
+    TORCH_CHECK(o % 64 == 0 && o >= 0 && o <= n, "seg_sumsq: segment offset ", o, " must be a multiple of 64 in [0, ",
+                n, "]");
+  const int64_t nchunks = chunks.size(0);
+  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * nchunks && partials.device() == master.device() &&
+                  chunks.device() == master.device() && grad.device() == master.device(),
+              "seg_sumsq: partials needs 2 slots per chunk (", 2 * nchunks, "), all tensors on one device");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(master.device());
+  check(ldnn::seg_sumsq(master.data_ptr<float>(), grad.data_ptr<float>(), n, chunks.data_ptr<int32_t>(), (int)nchunks,
+                        partials.data_ptr<float>(), cur_stream(master)),
+        "seg_sumsq");
+  return nchunks;
+}
+
+void lars_finalize(const c10::optional<at::Tensor>& partials, const at::Tensor& segtab, const at::Tensor& hdr,
+                   const at::Tensor& ratio, const at::Tensor& w_norm, const at::Tensor& g_norm, double grad_scale,
+                   double weight_decay, const c10::optional<at::Tensor>& ext, const c10::optional<at::Tensor>& clip,
+                   const c10::optional<at::Tensor>& sums_out) {
+  check_dev(segtab, at::kInt, "segtab");
+  check_dev(hdr, at::kFloat, "hdr");
+  TORCH_CHECK(segtab.dim() == 2 && segtab.size(1) == 4 && segtab.is_contiguous() && aligned16(segtab.data_ptr()),
+              "lars_finalize: segtab must be a dense int32 [S][4] table");
+  const int64_t S = segtab.size(0);
+  auto f32 = [&](const at::Tensor& t, int64_t need, const char* name) -> float* {
+    check_dev(t, at::kFloat, name);
+    TORCH_CHECK(t.is_contiguous() && t.numel() >= need && t.device() == segtab.device(), "lars_finalize: ", name,
+                " must hold ", need, " contiguous floats on the table's device");
+    return t.data_ptr<float>();
+  };
+  f32(hdr, 2, "hdr");
+  const float* pp = nullptr;
+  int64_t nchunks = 0;
+  if (partials.has_value()) {
+    pp = f32(*partials, 0, "partials");
+    nchunks = partials->numel() / 2;
+  }
+  float* so = sums_out.has_value() ? f32(*sums_out, 2 * S, "sums_out") : nullptr;
+  float* rp = f32(ratio, so ? 0 : S, "ratio");
+  float* wp = f32(w_norm, so ? 0 : S, "w_norm");
+  float* gp = f32(g_norm, so ? 0 : S, "g_norm");
+  const float* ep = ext.has_value() ? f32(*ext, 2 * S, "ext") : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(segtab.device());
+  check(ldnn::lars_finalize(pp, (int)nchunks, segtab.data_ptr<int32_t>(), (int)S, ep, hdr.data_ptr<float>(),
+                            clip_ptr(clip, segtab), (float)grad_scale, (float)weight_decay, rp, wp, gp, so,
+                            cur_stream(segtab)),
+        "lars_finalize");
+}
+
 void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& mom,
               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double momentum,
               double dampening, double weight_decay, bool nesterov, bool first_step,
               const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, int64_t t_begin,
-              const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip) {
+              const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip,
+              const c10::optional<std::pair<at::Tensor, at::Tensor>>& lars) {
   check_dev(param, at::kFloat, "param");
   check_dev(grad, at::kFloat, "grad");
   check_dev(hp, at::kFloat, "hp");
@@ -592,9 +659,25 @@ void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor&
     tr.cols = (int)t_out->size(0);
     tr.out = bf16_mut(*t_out);
   }
+  const float* lr_ = nullptr;
+  const uint16_t* lm_ = nullptr;
+  if (lars.has_value()) {
+    // (ratio, map): the trust ratios and, per 64-element block of param, the index of its ratio
+    const at::Tensor& ratio = lars->first;
+    const at::Tensor& map = lars->second;
+    check_dev(ratio, at::kFloat, "lars ratio");
+    check_dev(map, at::kUInt16, "lars map");
+    TORCH_CHECK(!t_out.has_value(), "sgd: lars= and t_out= do not go together (the transposed-shadow form has no LARS)");
+    TORCH_CHECK(ratio.is_contiguous() && ratio.numel() == 65536 && map.is_contiguous() &&
+                    map.numel() * 64 >= n && ratio.device() == param.device() && map.device() == param.device(),
+                "sgd: lars needs a contiguous 65536-entry ratio table and one uint16 map entry per 64 elements");
+    TORCH_CHECK(aligned16(param.data_ptr()) && aligned16(grad.data_ptr()), "sgd: lars needs 16-byte aligned ranges");
+    lr_ = ratio.data_ptr<float>();
+    lm_ = map.data_ptr<uint16_t>();
+  }
   check(ldnn::sgd_step(param.data_ptr<float>(), grad.data_ptr<float>(), mp, sh, hp.data_ptr<float>(),
                        (float)grad_scale, sp, n, cur_stream(param), t_out.has_value() ? &tr : nullptr,
-                       clip_ptr(clip, param)),
+                       clip_ptr(clip, param), lr_, lm_),
         "sgd_step");
 }
 
@@ -2064,7 +2147,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("hp"), py::arg("grad_scale"), py::arg("momentum"), py::arg("dampening"),
         py::arg("weight_decay"), py::arg("nesterov"), py::arg("first_step"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("t_begin") = 0,
-        py::arg("t_out") = py::none(), py::arg("clip") = py::none());
+        py::arg("t_out") = py::none(), py::arg("clip") = py::none(), py::arg("lars") = py::none());
+  m.def("seg_sumsq", &seg_sumsq, "per-chunk sums of squares of master and grad (partials[2c], partials[2c + 1]) over a "
+        "device chunk table cut from 64-aligned `ranges` of segments at `seg_offsets`; returns the chunk count",
+        py::arg("master"), py::arg("grad"), py::arg("chunks"), py::arg("partials"), py::arg("ranges"),
+        py::arg("seg_offsets"));
+  m.def("seg_sumsq_chunk", &ldnn::seg_sumsq_chunk, "elements of a seg_sumsq chunk");
+  m.def("lars_finalize", &lars_finalize, "per-segment LARS trust ratios / norms from seg_sumsq's partials (+ ext "
+        "sums); sums_out: the [2S] sums alone", py::arg("partials"), py::arg("segtab"), py::arg("hdr"),
+        py::arg("ratio"), py::arg("w_norm"), py::arg("g_norm"), py::arg("grad_scale"), py::arg("weight_decay"),
+        py::arg("ext") = py::none(), py::arg("clip") = py::none(), py::arg("sums_out") = py::none());
   m.def("adam_step", &adam_step, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),

@@ -393,9 +393,13 @@ struct ShadowT {
 // clip (optional, device fp32 [kClipState]): the global-norm clipping state clip_finalize wrote.
 // The update multiplies grad_scale by clip[kClipCoef]; with clip[kClipSkip] set it touches no
 // master / state / shadow element and only clears the requested gradient zero ranges.
+// lars_ratio / lars_map (optional, both or neither): the LARS trust ratios lars_finalize wrote and,
+// per 64-element block of THIS range, the index of its ratio (alignment gaps point at a slot that
+// holds 1).  The update becomes ratio * (g + weight_decay * p); together with `tr` it is refused.
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
                     float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr = nullptr,
-                    const float* clip = nullptr);
+                    const float* clip = nullptr, const float* lars_ratio = nullptr,
+                    const uint16_t* lars_map = nullptr);
 struct AdamParams {
   float beta1, beta2, eps, weight_decay;
   int decoupled;  // AdamW
@@ -432,6 +436,27 @@ hipError_t sumsq_total(const float* partials, int nparts, float* out, hipStream_
 // bumps the counters of `state`, reading state[kClipMaxNorm]
 hipError_t clip_finalize(const float* partials, int nparts, const float* ext, float* state, float grad_scale,
                          hipStream_t s);
+
+// ---- LARS (You, Gitman, Ginsburg 2017): per-tensor trust ratios over the flat buffers ----
+// elements of a seg_sumsq chunk the table builder (optim/optimizers.py) cuts segments into
+int seg_sumsq_chunk();
+// chunks: device int32 [nchunks][4] = (segment, begin / 64, end / 64, 0), each a run of 64-element
+// blocks inside one segment; a segment's chunks are consecutive.  partials[2c] / [2c + 1] = the
+// sums of squares of master / grad over chunk c (one workgroup per chunk, plain stores, no
+// atomics: bit-reproducible).  Padding inside and between segments is zero in both buffers, so
+// the sums over storage are the sums over the logical tensors.
+hipError_t seg_sumsq(const float* master, const float* grad, int64_t n, const int32_t* chunks, int nchunks,
+                     float* partials, hipStream_t s);
+// segtab: device int32 [S][4] = (first chunk, end chunk, adapted, 0).  Per segment i, in double and a
+// fixed order: (wsq, gsq) = sum of its partials (+ ext[2i], ext[2i + 1]).  sums_out != nullptr:
+// write those [2S] sums alone.  Else wn = sqrt(wsq), gn = clip coef * grad_scale * sqrt(gsq) and
+//   ratio[i] = hdr[0] * wn / (gn + weight_decay * wn + hdr[1])   if adapted, wn > 0 and gn > 0
+//   ratio[i] = 1                                                 otherwise
+// (hdr = [trust_coef, eps], written by the host like the lr; a sum of squares that overflowed fp32
+// gives ratio 0), w_norm[i] = wn, g_norm[i] = gn.  With clip[kClipSkip] set nothing is written.
+hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
+                         const float* hdr, const float* clip, float grad_scale, float weight_decay, float* ratio,
+                         float* w_norm, float* g_norm, float* sums_out, hipStream_t s);
 
 // ---- classifier head (<= 64 classes): fused Linear + softmax-xent, and its wgrad
 struct HeadParams {

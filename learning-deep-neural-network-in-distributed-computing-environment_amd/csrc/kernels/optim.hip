@@ -20,6 +20,7 @@ namespace ldnn {
 namespace {
 
 constexpr int kBlock = 256;
+constexpr int kSegChunk = 4096;  // elements of a seg_sumsq chunk: four float4 per thread and buffer
 
 // NT: streaming (nontemporal) loads / stores -- every optimizer byte is touched once
 // per step, so it need not displace the L2 / Infinity Cache lines the next kernels
@@ -61,6 +62,17 @@ struct ClipArg {
 template <>
 struct ClipArg<false> {};
 
+// LARS: the kernel also takes the per-tensor trust ratios (lars_finalize) and the map from each
+// 64-element block of this launch's range to its ratio slot.  The LARS = false instances carry
+// an empty argument and compile to the code without it.
+template <bool LARS>
+struct LarsArg {
+  const float* ratio;
+  const uint16_t* map;
+};
+template <>
+struct LarsArg<false> {};
+
 // a skipped (non-finite norm) step: only the requested gradient zero ranges are cleared
 __device__ __forceinline__ void clear_only(const GradZero& z, float* grad, int64_t n) {
   if (z.ze[0] <= z.zb[0] && z.ze[1] <= z.zb[1]) return;
@@ -73,14 +85,17 @@ __device__ __forceinline__ void clear_only(const GradZero& z, float* grad, int64
 }
 
 // one float4 of the SGD(-momentum) update: master, momentum, gradient clear; returns the
-// new bf16 shadow values
-template <bool NT>
+// new bf16 shadow values.  LARS: (g + weight_decay * p) is scaled by the trust ratio of the
+// 64-element block the float4 lies in (segments start on 64-element boundaries).
+template <bool NT, bool LARS>
 __device__ __forceinline__ u16x4 sgd4(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mom,
-                                      float lr, float grad_scale, const SgdParams& sp, int64_t i) {
+                                      float lr, float grad_scale, const SgdParams& sp, int64_t i,
+                                      const LarsArg<LARS>& lars) {
   floatx4 p = ld4<NT>(param, i);
   floatx4 g = ld4<NT>(grad, i) * grad_scale;
   clear4(sp.zero, grad, i);
   if (sp.weight_decay != 0.f) g += sp.weight_decay * p;
+  if constexpr (LARS) g *= lars.ratio[lars.map[i >> 4]];
   if (sp.momentum != 0.f) {
     floatx4 b;
     if (sp.first_step) b = g;
@@ -99,10 +114,11 @@ __device__ __forceinline__ u16x4 sgd4(float* __restrict__ param, float* __restri
 // that matrix one 64 x 64 tile each and write the transposed tile through LDS; the rest
 // stride over the remaining elements -- one launch instead of the update plus a
 // transpose pass that re-reads the 32 MB shadow.
-template <bool NT, bool TR, bool CLIP>
+template <bool NT, bool TR, bool CLIP, bool LARS>
 __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mom,
                            bf16_t* __restrict__ shadow, const float* __restrict__ hp, float grad_scale,
-                           SgdParams sp, int64_t n, ShadowT tr, ClipArg<CLIP> clip) {
+                           SgdParams sp, int64_t n, ShadowT tr, ClipArg<CLIP> clip, LarsArg<LARS> lars) {
+  static_assert(!(TR && LARS), "the transposed-shadow form has no LARS instance");
   if constexpr (CLIP) {
     if (clip.st[kClipSkip] != 0.f) {
       clear_only(sp.zero, grad, n);
@@ -124,7 +140,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
       for (int k = 0; k < 4; ++k) {
         const int r = rg * 4 + k;
         const int64_t i = (tr.begin + (int64_t)(r0 + r) * tr.cols + c0 + c4 * 4) >> 2;
-        const u16x4 b = sgd4<NT>(param, grad, mom, lr, grad_scale, sp, i);
+        const u16x4 b = sgd4<NT, LARS>(param, grad, mom, lr, grad_scale, sp, i, lars);
         if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = b;
 #pragma unroll
         for (int q = 0; q < 4; ++q) t[r][c4 * 4 + q] = b[q];
@@ -149,7 +165,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
   const int64_t stride = nblk * blockDim.x;
   for (int64_t j = bid * (int64_t)blockDim.x + threadIdx.x; j < nv - skip_n; j += stride) {
     const int64_t i = (TR && j >= skip_b) ? j + skip_n : j;
-    const u16x4 b = sgd4<NT>(param, grad, mom, lr, grad_scale, sp, i);
+    const u16x4 b = sgd4<NT, LARS>(param, grad, mom, lr, grad_scale, sp, i, lars);
     if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = b;
   }
   for (int64_t i = nv * 4 + bid * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -157,6 +173,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
     float g = grad[i] * grad_scale;
     if (in_zero(sp.zero, i)) grad[i] = 0.f;
     if (sp.weight_decay != 0.f) g += sp.weight_decay * p;
+    if constexpr (LARS) g *= lars.ratio[lars.map[i >> 6]];
     if (sp.momentum != 0.f) {
       const float b = sp.first_step ? g : sp.momentum * mom[i] + (1.f - sp.dampening) * g;
       mom[i] = b;
@@ -306,6 +323,111 @@ __global__ void clip_finalize_kernel(const float* __restrict__ partials, int npa
   if (!finite) state[kClipSkipped] += 1.f;
 }
 
+// Per-segment sums of squares of the master AND the gradient.  chunks[c] = (segment, begin / 64,
+// end / 64, -): a run of whole 64-element blocks inside one segment (a few thousand elements; a
+// range that cuts a segment only changes which chunks exist).  ONE workgroup reduces a whole chunk
+// -- 16-byte loads, four independent accumulators per buffer and thread, wave64 shuffle, LDS -- and
+// stores partials[2c] (master) and partials[2c + 1] (gradient) with plain stores: no atomics, and
+// a chunk's partial does not depend on the grid, so equal inputs give equal bits.  Plain loads:
+// the update re-reads both buffers right after.  A chunk outside [0, n) contributes nothing.
+__global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __restrict__ g,
+                                 const int4* __restrict__ chunks, int nchunks, int64_t n,
+                                 float* __restrict__ partials) {
+  static_assert(kBlock == 256, "the cross-wave sum below adds exactly four waves");
+  __shared__ float red[2][kBlock / 64];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int4 ch = chunks[c];
+    int64_t b = (int64_t)ch.y * 16, e = (int64_t)ch.z * 16;  // in float4s
+    if (ch.y < 0 || ch.z < ch.y || (int64_t)ch.z * 64 > n) b = e = 0;
+    const floatx4 z = {0.f, 0.f, 0.f, 0.f};
+    floatx4 w0 = z, w1 = z, w2 = z, w3 = z, g0 = z, g1 = z, g2 = z, g3 = z;
+    int64_t i = b + threadIdx.x;
+    for (; i + 3 * kBlock < e; i += 4 * kBlock) {
+      const floatx4 a0 = ld4<false>(w, i), a1 = ld4<false>(w, i + kBlock), a2 = ld4<false>(w, i + 2 * kBlock),
+                    a3 = ld4<false>(w, i + 3 * kBlock);
+      const floatx4 b0 = ld4<false>(g, i), b1 = ld4<false>(g, i + kBlock), b2 = ld4<false>(g, i + 2 * kBlock),
+                    b3 = ld4<false>(g, i + 3 * kBlock);
+      w0 += a0 * a0;
+      w1 += a1 * a1;
+      w2 += a2 * a2;
+      w3 += a3 * a3;
+      g0 += b0 * b0;
+      g1 += b1 * b1;
+      g2 += b2 * b2;
+      g3 += b3 * b3;
+    }
+    for (; i < e; i += kBlock) {
+      const floatx4 a = ld4<false>(w, i), bb = ld4<false>(g, i);
+      w0 += a * a;
+      g0 += bb * bb;
+    }
+    w0 = (w0 + w1) + (w2 + w3);
+    g0 = (g0 + g1) + (g2 + g3);
+    const float sw = wave_sum((w0[0] + w0[1]) + (w0[2] + w0[3]));
+    const float sg = wave_sum((g0[0] + g0[1]) + (g0[2] + g0[3]));
+    if ((threadIdx.x & 63) == 0) {
+      red[0][threadIdx.x >> 6] = sw;
+      red[1][threadIdx.x >> 6] = sg;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2)
+      partials[2 * (int64_t)c + threadIdx.x] =
+          (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    __syncthreads();
+  }
+}
+
+// One wave per segment (waves stride over the segments, so any S works).  segtab[s] = (first
+// chunk, end chunk, adapted, -).  Fixed summation order, in double: lane l adds the segment's
+// partials l, l + 64, ... in index order, the 64 lane sums meet in an xor butterfly (every lane
+// ends with the same bits).  ext: [2S] sums added on top (the sharded path's all-reduced vector).
+// sums_out: write the [2S] sums alone; else the ratios (ldnn_kernels.h lars_finalize).
+__global__ void lars_finalize_kernel(const float* __restrict__ partials, int nchunks, const int4* __restrict__ segtab,
+                                     int S, const float* __restrict__ ext, const float* __restrict__ hdr,
+                                     const float* __restrict__ clip, float grad_scale, float weight_decay,
+                                     float* __restrict__ ratio, float* __restrict__ w_norm,
+                                     float* __restrict__ g_norm, float* __restrict__ sums_out) {
+  if (sums_out == nullptr && clip != nullptr && clip[kClipSkip] != 0.f) return;  // a skipped step
+  const int lane = threadIdx.x & 63;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (int s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; s < S; s += nwaves) {
+    const int4 t = segtab[s];
+    double aw = 0.0, ag = 0.0;
+    if (partials != nullptr && t.x >= 0 && t.y <= nchunks) {
+      for (int c = t.x + lane; c < t.y; c += 64) {
+        aw += (double)partials[2 * (int64_t)c];
+        ag += (double)partials[2 * (int64_t)c + 1];
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      aw += __shfl_xor(aw, o, 64);
+      ag += __shfl_xor(ag, o, 64);
+    }
+    if (lane != 0) continue;
+    if (ext != nullptr) {
+      aw += (double)ext[2 * s];
+      ag += (double)ext[2 * s + 1];
+    }
+    if (sums_out != nullptr) {
+      sums_out[2 * s] = (float)aw;
+      sums_out[2 * s + 1] = (float)ag;
+      continue;
+    }
+    const double c = clip != nullptr ? (double)clip[kClipCoef] : 1.0;
+    const double wn = sqrt(aw), gn = c * (double)grad_scale * sqrt(ag);
+    double r = 1.0;
+    if (t.z != 0 && wn > 0.0 && gn > 0.0) {
+      // (a sum of squares that overflowed fp32: ratio 0, the tensor does not move)
+      const bool over = (float)aw > 3.402823466e38f || (float)ag > 3.402823466e38f;
+      r = over ? 0.0 : (double)hdr[0] * wn / (gn + (double)weight_decay * wn + (double)hdr[1]);
+    }
+    ratio[s] = (float)r;
+    w_norm[s] = (float)wn;
+    g_norm[s] = (float)gn;
+  }
+}
+
 
 int g_opt_max_blocks = 2048;  // optimizer grid cap (set_opt_max_blocks: a narrow side-stream update)
 
@@ -318,10 +440,30 @@ inline int grid_for(int64_t n4) {
 
 void set_opt_max_blocks(int n) { g_opt_max_blocks = n > 0 ? n : 2048; }
 
+namespace {
+template <bool TR, bool CLIP, bool LARS>
+void launch_sgd(int grid, float* param, float* grad, float* mom, uint16_t* shadow, const float* hp, float grad_scale,
+                const SgdParams& sp, int64_t n, hipStream_t s, const ShadowT& tr, const float* clip,
+                const float* ratio, const uint16_t* map) {
+  ClipArg<CLIP> ca;
+  if constexpr (CLIP) ca.st = clip;
+  LarsArg<LARS> la;
+  if constexpr (LARS) {
+    la.ratio = ratio;
+    la.map = map;
+  }
+  sgd_kernel<true, TR, CLIP, LARS><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, tr, ca, la);
+}
+}  // namespace
+
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
-                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr, const float* clip) {
+                    float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr, const float* clip,
+                    const float* lars_ratio, const uint16_t* lars_map) {
   if (n <= 0) return hipSuccess;
+  const bool lars = lars_ratio != nullptr;
+  if (lars != (lars_map != nullptr)) return hipErrorInvalidValue;
   if (tr != nullptr && tr->out != nullptr) {
+    if (lars) return hipErrorInvalidValue;  // (only the static engine transposes; it has no LARS)
     // (the tile path needs whole 64 x 64 tiles and 16-B aligned transposed rows)
     if (tr->rows <= 0 || tr->cols <= 0 || tr->rows % 64 || tr->cols % 64 || tr->begin % 4 || tr->begin < 0 ||
         tr->begin + (int64_t)tr->rows * tr->cols > n || ((uintptr_t)tr->out & 15))
@@ -330,20 +472,24 @@ hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, con
     const int64_t rest = (n - (int64_t)tr->rows * tr->cols + 3) / 4;
     const int grid = (int)ntiles + grid_for(rest);
     if (clip != nullptr)
-      sgd_kernel<true, true, true><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, *tr,
-                                                           ClipArg<true>{clip});
+      launch_sgd<true, true, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, *tr, clip, nullptr, nullptr);
     else
-      sgd_kernel<true, true, false><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, *tr,
-                                                            ClipArg<false>{});
+      launch_sgd<true, false, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, *tr, nullptr, nullptr,
+                                     nullptr);
     return hipGetLastError();
   }
   const int grid = grid_for((n + 3) / 4);
-  if (clip != nullptr)
-    sgd_kernel<true, false, true><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, ShadowT{},
-                                                          ClipArg<true>{clip});
-  else
-    sgd_kernel<true, false, false><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n,
-                                                           ShadowT{}, ClipArg<false>{});
+  const ShadowT none{};
+  auto go = [&](auto launch) {
+    launch(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, none, clip, lars_ratio, lars_map);
+  };
+  if (clip != nullptr) {
+    if (lars) go(launch_sgd<false, true, true>);
+    else go(launch_sgd<false, true, false>);
+  } else {
+    if (lars) go(launch_sgd<false, false, true>);
+    else go(launch_sgd<false, false, false>);
+  }
   return hipGetLastError();
 }
 
@@ -382,6 +528,28 @@ hipError_t sumsq_total(const float* partials, int nparts, float* out, hipStream_
 hipError_t clip_finalize(const float* partials, int nparts, const float* ext, float* state, float grad_scale,
                          hipStream_t s) {
   clip_finalize_kernel<<<1, kBlock, 0, s>>>(partials, nparts, ext, state, grad_scale, nullptr);
+  return hipGetLastError();
+}
+
+int seg_sumsq_chunk() { return kSegChunk; }
+
+hipError_t seg_sumsq(const float* master, const float* grad, int64_t n, const int32_t* chunks, int nchunks,
+                     float* partials, hipStream_t s) {
+  if (nchunks <= 0) return hipSuccess;
+  const int grid = nchunks < g_opt_max_blocks ? nchunks : g_opt_max_blocks;
+  seg_sumsq_kernel<<<grid, kBlock, 0, s>>>(master, grad, reinterpret_cast<const int4*>(chunks), nchunks, n, partials);
+  return hipGetLastError();
+}
+
+hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
+                         const float* hdr, const float* clip, float grad_scale, float weight_decay, float* ratio,
+                         float* w_norm, float* g_norm, float* sums_out, hipStream_t s) {
+  if (S <= 0) return hipSuccess;
+  const int waves = kBlock / 64;
+  int grid = (S + waves - 1) / waves;
+  if (grid > 256) grid = 256;
+  lars_finalize_kernel<<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext, hdr,
+                                               clip, grad_scale, weight_decay, ratio, w_norm, g_norm, sums_out);
   return hipGetLastError();
 }
 

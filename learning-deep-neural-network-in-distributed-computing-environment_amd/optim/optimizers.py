@@ -31,6 +31,12 @@ cannot be captured into a graph.  A graph captured with clipping on keeps its cl
 kernels: setting ``max_grad_norm`` to None afterwards makes the replays run them with an
 infinite threshold (coefficient 1, non-finite steps still skipped); a graph captured with
 clipping off never clips, whatever is set later -- capture again.
+
+``SGD(lars_trust=...)`` (default None = off; ``build_optimizer("lars")``) adds LARS: see the
+class.  It is the per-tensor form of the same plumbing -- ``seg_sumsq`` + ``lars_finalize``
+leave one trust ratio per parameter tensor on the device, the fused SGD looks it up per
+64-element block, and the sharded step all-reduces the ``2S`` per-segment sums (clipping's
+scalar behind them) in its one extra collective.
 """
 from __future__ import annotations
 
@@ -59,7 +65,87 @@ def _refuse_partial_sharded(params):
 # slots of the clipping state tensor (csrc/include/ldnn_kernels.h ClipSlot)
 _CLIP_MAX, _CLIP_COEF, _CLIP_SKIP, _CLIP_NORM, _CLIP_STEPS, _CLIP_CLIPPED, _CLIP_SKIPPED, _CLIP_LEN = 0, 1, 2, 3, 4, 5, 6, 8
 # device-only entries of _ls(): rebuilt by an eager step, never saved
-_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local")
+_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars")
+# LARS ratio table: one slot per uint16 map value, so every map entry is in bounds; the slots
+# past the segments are never written and hold 1 (alignment gaps map to the last one)
+_LARS_SLOTS, _LARS_GAP = 65536, 65535
+_CAPTURE_MSG = "run an eager optimizer step before capturing it into a graph"
+
+
+def lars_chunk_table(bounds, ranges, chunk):
+    """The seg_sumsq tables (host lists) for segments ``bounds`` = [(begin, end)] restricted to
+    the flat ``ranges``: ``chunks`` rows (segment, begin / 64, end / 64, 0) of at most ``chunk``
+    elements, never across a segment boundary, a segment's chunks consecutive; ``segs`` rows
+    (first chunk, end chunk) per segment.  Everything must lie on 64-element boundaries."""
+    for lo, hi in list(ranges) + list(bounds):
+        if lo % 64 or hi % 64 or lo < 0 or hi < lo:
+            raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
+    if chunk <= 0 or chunk % 64:
+        raise ValueError(f"LARS: chunk {chunk} must be a positive multiple of 64")
+    rs = sorted((lo, hi) for lo, hi in ranges if hi > lo)
+    chunks, segs = [], []
+    for s, (b, e) in enumerate(bounds):
+        first = len(chunks)
+        for lo, hi in rs:
+            x, y = max(b, lo), min(e, hi)
+            while x < y:
+                z = min(x + chunk, y)
+                chunks.append((s, x // 64, z // 64, 0))
+                x = z
+        segs.append((first, len(chunks)))
+    return chunks, segs
+
+
+class _Lars:
+    """Device state of LARS over one flat buffer (or, ``flat`` None, over loose tensors)."""
+
+    def __init__(self, flat, params, exclude_1d, device):
+        self.flat, self.device, self.exclude_1d = flat, device, exclude_1d
+        if flat is not None:
+            segs = flat.segments
+            self.names = [s.name for s in segs]
+            self.adapt = [not (exclude_1d and s.param.dim() < 2) for s in segs]
+            self.bounds = [(s.offset, s.offset + (s.storage_numel + 63) // 64 * 64) for s in segs]
+            if len(segs) >= _LARS_GAP:
+                raise ValueError(f"LARS: {len(segs)} parameter tensors exceed the uint16 segment map")
+            seg_of = torch.full((flat.numel // 64,), _LARS_GAP, dtype=torch.int64)
+            for i, (b, e) in enumerate(self.bounds):
+                if b % 64 or e > flat.numel:
+                    raise ValueError(f"LARS: segment {self.names[i]} is not 64-element aligned in the flat buffer")
+                seg_of[b // 64: e // 64] = i
+            self.seg_of = seg_of.to(device)               # torch paths index with it
+            self.segmap = seg_of.to(torch.uint16).to(device)   # the fused kernel's map
+        else:
+            self.names = [f"param{i}" for i in range(len(params))]
+            self.adapt = [not (exclude_1d and p.dim() < 2) for p in params]
+        self.S = S = len(self.names)
+        self.adapt_t = torch.tensor(self.adapt, dtype=torch.bool, device=device)
+        self.hdr = torch.zeros(2, dtype=torch.float32, device=device)
+        self.ratio = torch.ones(max(_LARS_SLOTS, S + 1), dtype=torch.float32, device=device)
+        self.w_norm = torch.zeros(S, dtype=torch.float32, device=device)
+        self.g_norm = torch.zeros(S, dtype=torch.float32, device=device)
+        self.local = torch.zeros(2 * S + 1, dtype=torch.float32, device=device)   # sharded: [2S] sums + clip's
+        self.tables = {}
+
+    def table(self, ranges, capturing):
+        """Device chunk tables + partial slots of seg_sumsq over ``ranges`` (built once per set)."""
+        key = tuple(ranges)
+        t = self.tables.get(key)
+        if t is None:
+            if capturing:
+                raise RuntimeError(_CAPTURE_MSG)
+            chunks, segs = lars_chunk_table(self.bounds, ranges, _ext.C().seg_sumsq_chunk())
+            segtab = [(a, b, int(ad), 0) for (a, b), ad in zip(segs, self.adapt)]
+            i32 = dict(dtype=torch.int32, device=self.device)
+            t = dict(ranges=[tuple(r) for r in ranges],
+                     chunks=torch.tensor(chunks, **i32).reshape(-1, 4), segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
+                     partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
+            self.tables[key] = t
+        return t
+
+    def elem_ratio(self, lo, hi):
+        """The ratio of every element of the flat range [lo, hi) (torch paths)."""
+        return self.ratio[self.seg_of[lo // 64: hi // 64]].repeat_interleave(64)
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -169,6 +255,95 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._clip_finalize_torch(cl, total)
         return cl, bool(cl[_CLIP_SKIP].item())
 
+    # ---- LARS: per-tensor trust ratios (SGD) -------------------------------------------
+    def _lars_conf(self):
+        """``(trust_coef, eps, exclude_1d)``, or None when LARS is off.  One setting for the whole
+        optimizer; the keys are read with .get, so state saved before they existed loads."""
+        vals = []
+        for g in self.param_groups:
+            t = g.get("lars_trust")
+            vals.append(None if t is None else (float(t), float(g.get("lars_eps", 1e-8)),
+                                                bool(g.get("lars_exclude_1d", True))))
+        if any(v != vals[0] for v in vals):
+            raise ValueError(f"lars_trust / lars_eps / lars_exclude_1d must be the same in every param group; got {vals}")
+        return vals[0] if vals else None
+
+    def _lars_state(self, flat, params=None, device=None):
+        """The LARS device state, with the current trust coefficient and eps written -- like
+        ``hp``: allocated by an eager step, read by graphs."""
+        trust, eps, excl = self._lars_conf()
+        st = self._ls()
+        L = st.get("lars")
+        device = flat.master.device if flat is not None else device
+        capturing = getattr(self, "_ldnn_capturing", False)
+        if L is None or L.flat is not flat or L.device != device or L.exclude_1d != excl or \
+                (flat is None and L.S != len(params)):
+            if capturing:
+                raise RuntimeError(_CAPTURE_MSG)
+            L = st["lars"] = _Lars(flat, params, excl, device)
+        if not capturing:
+            L.hdr[0].fill_(trust)
+            L.hdr[1].fill_(eps)
+        return L
+
+    def lars_stats(self):
+        """In segment (flat-buffer) order: the device tensors ``ratio`` / ``w_norm`` / ``g_norm`` of
+        the last LARS step, the parameter ``names`` and which tensors are ``adapted`` (reading a
+        tensor syncs); None when LARS is off."""
+        if self._lars_conf() is None:
+            return None
+        L = self._ls().get("lars")
+        if L is None:
+            f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
+            ps = [p for g in self.param_groups for p in g["params"]]
+            L = self._lars_state(f, ps, ps[0].device if ps else torch.device("cpu"))
+        return {"ratio": L.ratio[:L.S], "w_norm": L.w_norm, "g_norm": L.g_norm, "names": list(L.names),
+                "adapted": list(L.adapt)}
+
+    @staticmethod
+    def _lars_sums_torch(L, f, ranges):
+        """seg_sumsq in torch ops: [2][S] fp64 sums of squares of master / grad over ``ranges``."""
+        out = torch.zeros(2, L.S + 1, dtype=torch.float64, device=L.device)
+        for lo, hi in ranges:
+            if lo % 64 or hi % 64:
+                raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
+            if hi <= lo:
+                continue
+            idx = L.seg_of[lo // 64: hi // 64].clamp(max=L.S)
+            for k, buf in enumerate((f.master, f.grad)):
+                out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
+        return out[:, :L.S]
+
+    @staticmethod
+    def _lars_finalize_torch(L, sums, gscale, wd):
+        """lars_finalize in torch ops; ``gscale`` = grad_scale (* the clip coefficient)."""
+        trust, eps = L.hdr.double()
+        wn = sums[0].double().sqrt()
+        gn = sums[1].double().sqrt() * gscale
+        r = trust * wn / (gn + wd * wn + eps)
+        over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
+        r = torch.where(over, torch.zeros_like(r), r)
+        r = torch.where(L.adapt_t & (wn > 0) & (gn > 0), r, torch.ones_like(r))
+        L.ratio[:L.S] = r.float()
+        L.w_norm.copy_(wn)
+        L.g_norm.copy_(gn)
+
+    def _lars_begin(self, f, group, cl):
+        """The ratios of an unsharded flat step, before the update: returns the state (its
+        ``ratio`` / ``segmap`` feed the fused kernel).  ``cl``: the finalized clip state or None."""
+        L = self._lars_state(f)
+        wd = group["weight_decay"]
+        if _ext.use_native(f.master):
+            C = _ext.C()
+            t = L.table([(0, f.numel)], getattr(self, "_ldnn_capturing", False))
+            C.seg_sumsq(f.master, f.grad, t["chunks"], t["partials"], t["ranges"], [b for b, _ in L.bounds])
+            C.lars_finalize(t["partials"], t["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, f.grad_scale, wd,
+                            clip=cl)
+        else:
+            coef = cl[_CLIP_COEF].double() if cl is not None else 1.0
+            self._lars_finalize_torch(L, self._lars_sums_torch(L, f, [(0, f.numel)]), f.grad_scale * coef, wd)
+        return L
+
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         flat_state = state_dict.pop("ldnn_flat_state", {})
@@ -212,8 +387,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     @torch.no_grad()
     def sync_hyperparams(self):
-        """Write the current learning rate (and clipping threshold) into the device
-        hyper-parameter tensors."""
+        """Write the current learning rate (and clipping threshold, LARS trust coefficient and
+        eps) into the device hyper-parameter tensors."""
         hp = self._ls().get("hp")
         if hp is not None:
             hp[0].fill_(self.param_groups[0]["lr"])
@@ -223,6 +398,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
             # captured kernels' coefficient 1; the non-finite guard of that graph stays)
             mx = self._clip_threshold()
             cl[_CLIP_MAX].fill_(mx if mx is not None else float("inf"))
+        L = self._ls().get("lars")
+        conf = self._lars_conf()
+        if L is not None and conf is not None:
+            L.hdr[0].fill_(conf[0])
+            L.hdr[1].fill_(conf[1])
 
     def _buf(self, name, like):
         st = self._ls()
@@ -247,6 +427,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def supports_ranges(self) -> bool:
         if self._clip_threshold() is not None:
             return False   # the whole norm must be known before any range updates
+        if self._lars_conf() is not None:
+            return False   # ... and so must a tensor's whole gradient before any of it moves
         if len(self.param_groups) != 1 or type(self)._update_range is _FlatOptimizer._update_range:
             return False
         f = self._flat_for_group(self.param_groups[0])
@@ -272,7 +454,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             raise RuntimeError("DataParallel(shard_optimizer=True) needs ONE param group holding the whole "
                                f"flat buffer; this optimizer has {len(self.param_groups)}")
         f.finalize_grads()
-        if self._clip_threshold() is not None:
+        if self._clip_threshold() is not None or self._lars_conf() is not None:
             return self._sharded_step_clipped(f, group, sh)
         ctx = self._begin_ranges(f, group)
         parts = getattr(sh, "step_parts", None)
@@ -288,47 +470,73 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return True
 
     def _sharded_step_clipped(self, f, group, sh) -> bool:
-        """The sharded step with global-norm clipping, in three phases: ``norm`` (sums of
-        squares of this rank's shard ranges -- on rank 0 also of the replicated tail, which
-        every rank holds alike, so it is counted once -- into one local scalar), ONE scalar
-        all-reduce, ``update`` (finalize the coefficient, then every range update).  Every
+        """The sharded step with global-norm clipping and / or LARS, in three phases: ``norm``
+        (sums of squares of this rank's shard ranges -- on rank 0 also of the replicated tail,
+        which every rank holds alike, so it is counted once -- into one local vector), ONE
+        all-reduce of that vector, ``update`` (finalize the coefficient / the ratios, then every
+        range update).  The vector is the scalar gradient sum with clipping alone; with LARS
+        the per-segment [master, grad] sums ``[2S]``, followed by clipping's scalar.  Every
         bucket's post_collective has run before.  ``sh.clip_phases(norm, local, update)``: a
         caller that captures the two compute phases into graphs and issues the all-reduce
         itself (GraphedDPStep); else the all-reduce goes through ``sh.comm`` here."""
         native = _ext.use_native(f.master)
+        clipped = self._clip_threshold() is not None
         ranges = [(lo, hi) for lo, hi in sh.norm_ranges() if hi > lo]
         st = self._ls()
+        L = self._lars_state(f) if self._lars_conf() is not None else None
+        cl = None
         if native:
             C = _ext.C()
-            cl = self._clip_state(f.master.device, max(1, sum(C.grad_sumsq_parts(hi - lo) for lo, hi in ranges)))
-        else:
+            if clipped:
+                cl = self._clip_state(f.master.device, max(1, sum(C.grad_sumsq_parts(hi - lo) for lo, hi in ranges)))
+            tab = L.table(ranges, getattr(self, "_ldnn_capturing", False)) if L is not None else None
+        elif clipped:
             cl = self._clip_state(f.master.device)
             if st.get("clip_local") is None or st["clip_local"].device != f.master.device:
                 st["clip_local"] = torch.zeros(1, dtype=torch.float32, device=f.master.device)
-        local = st["clip_local"]
+        local = st["clip_local"] if L is None else L.local
+        clip_local = local[local.numel() - 1:] if clipped else None
+        wd = group["weight_decay"]
 
         def norm():
             if native:
-                sc, slot = st["clip_scratch"], 0
-                for lo, hi in ranges:
-                    slot += C.grad_sumsq(f.grad[lo:hi], sc, slot)
-                C.sumsq_total(sc, slot, local)
+                if clipped:
+                    sc, slot = st["clip_scratch"], 0
+                    for lo, hi in ranges:
+                        slot += C.grad_sumsq(f.grad[lo:hi], sc, slot)
+                    C.sumsq_total(sc, slot, clip_local)
+                if L is not None:
+                    C.seg_sumsq(f.master, f.grad, tab["chunks"], tab["partials"], tab["ranges"],
+                                [b for b, _ in L.bounds])
+                    C.lars_finalize(tab["partials"], tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, 1.0, 0.0,
+                                    sums_out=local)
             else:
-                tot = torch.zeros((), dtype=torch.float64, device=f.master.device)
-                for lo, hi in ranges:
-                    tot = tot + f.grad[lo:hi].double().square().sum()
-                local.copy_(tot.reshape(1))
+                if clipped:
+                    tot = torch.zeros((), dtype=torch.float64, device=f.master.device)
+                    for lo, hi in ranges:
+                        tot = tot + f.grad[lo:hi].double().square().sum()
+                    clip_local.copy_(tot.reshape(1))
+                if L is not None:
+                    local[:2 * L.S].copy_(self._lars_sums_torch(L, f, ranges).t().reshape(-1))
 
         def update():
+            skip = None
             if native:
-                C.clip_finalize(st["clip_scratch"], 0, cl, f.grad_scale, ext=local)
-                skip = None
-            else:
-                self._clip_finalize_torch(cl, local, f.grad_scale)
+                if clipped:
+                    C.clip_finalize(st["clip_scratch"], 0, cl, f.grad_scale, ext=clip_local)
+                if L is not None:
+                    C.lars_finalize(None, tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, f.grad_scale, wd,
+                                    ext=local, clip=cl)
+            elif clipped:
+                self._clip_finalize_torch(cl, clip_local, f.grad_scale)
                 skip = bool(cl[_CLIP_SKIP].item())
             if skip:   # (torch path: decided on the host; the fused kernels read the flag themselves)
                 return
-            ctx = self._begin_ranges(f, group, clip=(cl, skip))
+            if L is not None and not native:
+                coef = cl[_CLIP_COEF].double() if clipped else 1.0
+                self._lars_finalize_torch(L, local[:2 * L.S].view(L.S, 2).t(), f.grad_scale * coef, wd)
+            kw = {} if L is None else {"lars": L}
+            ctx = self._begin_ranges(f, group, clip=(cl, skip) if clipped else None, **kw)
             for lo, hi in sh.update_ranges():
                 if hi > lo:
                     self._update_range(f, group, ctx, lo, hi)
@@ -360,10 +568,26 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
 
 class SGD(_FlatOptimizer):
+    """SGD (momentum / dampening / nesterov / weight decay), optionally with LARS: with
+    ``lars_trust`` set (None = off) tensor i's update ``g_i + weight_decay * w_i`` is scaled by
+    ``lars_trust * |w_i| / (|g_i| + weight_decay * |w_i| + lars_eps)`` before it enters the
+    momentum chain (You, Gitman, Ginsburg 2017); ``g_i`` is the reduced, scaled and -- with
+    ``max_grad_norm`` -- clipped gradient.  The ratio is 1 for a tensor whose weight or gradient
+    norm is zero and, with ``lars_exclude_1d`` (default), for tensors with ``dim() < 2`` (biases,
+    BatchNorm affine).  On the flat GPU path ``seg_sumsq`` + ``lars_finalize`` leave the ratios
+    on the device and the fused kernel looks them up per 64-element block; the trust
+    coefficient and eps are device scalars written like the lr, so a captured graph follows a
+    schedule on them.  No non-finite guard of its own: NaN norms fail the ``> 0`` tests (ratio 1)
+    and the NaN elements propagate as in torch; a per-tensor sum of squares that overflows
+    fp32 gives that tensor ratio 0.  ``lars_stats()`` reports the last ratios and norms."""
+
     def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, lars_trust=None, lars_eps=1e-8, lars_exclude_1d=True):
+        if lars_trust is not None and lars_trust <= 0:
+            raise ValueError(f"lars_trust must be positive (None: LARS off); got {lars_trust}")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                      nesterov=nesterov, max_grad_norm=max_grad_norm))
+                                      nesterov=nesterov, max_grad_norm=max_grad_norm, lars_trust=lars_trust,
+                                      lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d))
 
     @torch.no_grad()
     def step(self, closure=None, clear_grads: bool = False):
@@ -373,6 +597,8 @@ class SGD(_FlatOptimizer):
         loss = closure() if closure is not None else None
         clip = self._clip_begin()
         cl, skip = clip if clip is not None else (None, None)
+        lars = self._lars_conf()
+        loose = None   # LARS over tensors outside a flat buffer: [param index, rows of (ratio, wn, gn)]
         for group in self.param_groups:
             lr, mu, damp, wd, nest = (group[k] for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"))
             f = self._flat_for_group(group)
@@ -384,14 +610,18 @@ class SGD(_FlatOptimizer):
                 first = st.get("step", 0) == 0
                 mom = self._buf("momentum", f.master) if mu != 0 else f.master
                 if _ext.use_native(f.master):
+                    dcl = cl.to(f.master.device) if cl is not None else None
+                    L = self._lars_begin(f, group, dcl) if lars is not None else None
                     _ext.C().sgd_step(f.master, f.grad, mom, f.shadow, self._hp(f, lr), f.grad_scale, mu, damp, wd,
                                       nest, first, zero_ranges=[(0, f.grad.numel())] if clear_grads else [],
-                                      clip=cl.to(f.master.device) if cl is not None else None)
+                                      clip=dcl, lars=(L.ratio, L.segmap) if L is not None else None)
                 else:
                     if not skip:
                         g = f.grad * f.grad_scale
+                        L = self._lars_begin(f, group, cl) if lars is not None else None
                         self._sgd_torch(f.master, g if cl is None else g * cl[_CLIP_COEF], mom if mu != 0 else None,
-                                        lr, mu, damp, wd, nest, first)
+                                        lr, mu, damp, wd, nest, first,
+                                        ratio=L.elem_ratio(0, f.numel) if L is not None else None)
                         if f.shadow is not None:
                             f.shadow.copy_(f.master)
                     if clear_grads:
@@ -402,7 +632,13 @@ class SGD(_FlatOptimizer):
             else:
                 if skip:
                     continue
+                if lars is not None and loose is None:
+                    ps_all = [p for g_ in self.param_groups for p in g_["params"]]
+                    loose = [0, self._lars_state(None, ps_all, ps_all[0].device)]
                 for p in group["params"]:
+                    if loose is not None:
+                        k = loose[0]
+                        loose[0] += 1
                     if p.grad is None:
                         continue
                     if cl is not None:
@@ -411,35 +647,51 @@ class SGD(_FlatOptimizer):
                     first = "momentum_buffer" not in ps
                     if mu != 0 and first:
                         ps["momentum_buffer"] = torch.zeros_like(p)
-                    self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first)
+                    ratio = None
+                    if loose is not None:
+                        L = loose[1]
+                        wn, gn = float(p.detach().double().norm()), float(p.grad.double().norm())
+                        ratio = 1.0
+                        if L.adapt[k] and wn > 0 and gn > 0:
+                            ratio = lars[0] * wn / (gn + wd * wn + lars[1])
+                        L.ratio[k], L.w_norm[k], L.g_norm[k] = ratio, wn, gn
+                    self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first,
+                                    ratio=ratio)
         return loss
 
-    def _begin_ranges(self, f, group, clip=None):
+    def _begin_ranges(self, f, group, clip=None, lars=None):
         mu = group["momentum"]
         hp = self._hp(f, group["lr"]) if _ext.use_native(f.master) else None
         return dict(hp=hp, first=self._ls().get("step", 0) == 0, clip=clip[0] if clip is not None else None,
-                    mom=self._buf("momentum", f.master) if mu != 0 else f.master)
+                    mom=self._buf("momentum", f.master) if mu != 0 else f.master, lars=lars)
 
     def _update_range(self, f, group, ctx, lo, hi):
         sh = f.shadow[lo:hi] if f.shadow is not None else None
+        L = ctx.get("lars")
         if not _ext.use_native(f.master):
             mu = group["momentum"]
             g = f.grad[lo:hi] * f.grad_scale
             if ctx["clip"] is not None:
                 g = g * ctx["clip"][_CLIP_COEF]
             self._sgd_torch(f.master[lo:hi], g, ctx["mom"][lo:hi] if mu != 0 else None,
-                            group["lr"], mu, group["dampening"], group["weight_decay"], group["nesterov"], ctx["first"])
+                            group["lr"], mu, group["dampening"], group["weight_decay"], group["nesterov"], ctx["first"],
+                            ratio=L.elem_ratio(lo, hi) if L is not None else None)
             if sh is not None:
                 sh.copy_(f.master[lo:hi])
             return
+        if L is not None and (lo % 64 or hi % 64):
+            raise ValueError(f"LARS: the update range [{lo}, {hi}) is not 64-element aligned")
         _ext.C().sgd_step(f.master[lo:hi], f.grad[lo:hi], ctx["mom"][lo:hi], sh, ctx["hp"], f.grad_scale,
                           group["momentum"], group["dampening"], group["weight_decay"], group["nesterov"],
-                          ctx["first"], clip=ctx["clip"])
+                          ctx["first"], clip=ctx["clip"],
+                          lars=(L.ratio, L.segmap[lo // 64: hi // 64]) if L is not None else None)
 
     @staticmethod
-    def _sgd_torch(p, g, buf, lr, mu, damp, wd, nest, first):
+    def _sgd_torch(p, g, buf, lr, mu, damp, wd, nest, first, ratio=None):
         if wd != 0:
             g = g + wd * p
+        if ratio is not None:
+            g = g * ratio
         if mu != 0:
             if first:
                 buf.copy_(g)
@@ -554,13 +806,21 @@ class AdamW(Adam):
 
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
-                    max_grad_norm: float | None = None):
-    """max_grad_norm: clip by the global L2 norm (None or <= 0: off)."""
+                    max_grad_norm: float | None = None, **lars):
+    """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  "lars": SGD with
+    ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
+    "sgd" takes them too); Adam and AdamW refuse them."""
     name = name.lower()
     if max_grad_norm is not None and max_grad_norm <= 0:
         max_grad_norm = None
+    bad = set(lars) - {"lars_trust", "lars_eps", "lars_exclude_1d"}
+    if bad or (lars and name in ("adam", "adamw")):
+        raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad or lars)}")
+    if name == "lars":
+        lars.setdefault("lars_trust", 0.001)
+        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
     if name == "sgd":
-        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
     if name == "adam":
         return Adam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     if name == "adamw":

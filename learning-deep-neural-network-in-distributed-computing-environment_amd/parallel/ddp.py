@@ -197,7 +197,8 @@ class GradBucketer:
         # buckets' optimizer updates (GraphedDPStep's per-bucket optimizer graphs)
         self.step_parts = None
         # clip_phases(norm, local, update): the same for a sharded step with global-norm clipping
-        # (the caller captures the two compute phases and issues the scalar all-reduce of `local`)
+        # and / or LARS (the caller captures the two compute phases and issues the all-reduce of
+        # `local`: clipping's scalar, or LARS's per-segment sums with that scalar behind them)
         self.clip_phases = None
         flat.add_ready_hook(self._on_ready)
         if self.shard:

@@ -178,8 +178,10 @@ class GraphedStep:
         return loss
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold travels like the lr: a device scalar the captured kernels read)
-        lrs = [(g["lr"], g.get("max_grad_norm")) for g in self.optimizer.param_groups]
+        # (the clipping threshold and LARS's trust coefficient / eps travel like the lr: device
+        # scalars the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"))
+               for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -400,11 +402,12 @@ class GraphedDPStep:
                 self.bk.post_collective(i)
                 update(*self.bk.update_range(i))
 
-        if self.optimizer._clip_threshold() is not None:
-            # global-norm clipping: no range may update before the whole norm is known, so the
-            # per-bucket graphs give way to a NORM graph (every bucket's widen + this rank's
-            # sums of squares), the host-issued scalar all-reduce, and an UPDATE graph
-            # (finalize the coefficient, step count, every range update)
+        if self.optimizer._clip_threshold() is not None or self.optimizer._lars_conf() is not None:
+            # global-norm clipping / LARS: no range may update before the whole norm (every
+            # tensor's norms) is known, so the per-bucket graphs give way to a NORM graph (every
+            # bucket's widen + this rank's sums of squares), the host-issued all-reduce of the
+            # local sum (LARS: the vector of per-segment sums, clipping's scalar behind it), and
+            # an UPDATE graph (finalize the coefficient / ratios, step count, every range update)
             def phases(norm, local, update):
                 begin(None)
                 for i in order:
@@ -467,8 +470,10 @@ class GraphedDPStep:
             self._fire(done)
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold travels like the lr: a device scalar the captured kernels read)
-        lrs = [(g["lr"], g.get("max_grad_norm")) for g in self.optimizer.param_groups]
+        # (the clipping threshold and LARS's trust coefficient / eps travel like the lr: device
+        # scalars the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"))
+               for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()

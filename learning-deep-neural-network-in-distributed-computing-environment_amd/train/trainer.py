@@ -437,6 +437,13 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                         {"grad_norm_last": float(clip_stats["last_norm"]),
                          "grad_clipped_steps": int(clip_stats["clipped"]),
                          "grad_skipped_steps": int(clip_stats["skipped"])})
+            # LARS trust ratios of the last step, over the adapted tensors (one read per global epoch)
+            lars_stats = getattr(optimizer, "lars_stats", lambda: None)()
+            if lars_stats is not None:
+                r = lars_stats["ratio"].detach().float().cpu()[torch.tensor(lars_stats["adapted"], dtype=torch.bool)]
+                if r.numel():
+                    clip_rec.update(lars_ratio_min=float(r.min()), lars_ratio_median=float(r.median()),
+                                    lars_ratio_max=float(r.max()))
             logger.log(kind="global_epoch", global_epoch=global_epoch + 1, duration_s=duration,
                        train_loss=H["global_train_losses"][-1], train_acc=H["global_train_accuracies"][-1],
                        val_loss=H["global_val_losses"][-1], val_acc=H["global_val_accuracies"][-1],

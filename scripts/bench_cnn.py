@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--clip", type=float, default=0.0,
                     help="max_grad_norm of the ldnn optimizer (global-norm clipping; 0 = off, 1e30 = the clipped "
                          "kernels with unchanged math)")
+    ap.add_argument("--lars", type=float, default=0.0,
+                    help="lars_trust of the ldnn SGD (LARS trust ratios; 0 = off)")
     a = ap.parse_args()
     from ldnn.ops import _ext as _e
 
@@ -58,6 +60,9 @@ def main():
     xavier_init(m)
     ldnn.prepare(m, "cuda")
     kw = dict(max_grad_norm=a.clip) if a.clip > 0 else {}
+    if a.lars > 0:
+        assert a.optimizer == "sgd", "--lars goes with --optimizer sgd"
+        kw["lars_trust"] = a.lars
     opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
            else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
     crit = CrossEntropyLoss()
@@ -77,7 +82,11 @@ def main():
             gs(xb, y)
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
+        ls = opt.lars_stats()
+        r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
+        rec["lars_ratio_median"] = round(float(r.median()), 4)
     if not a.no_stock:
         import torch.nn as nn
 

@@ -51,7 +51,11 @@ def main():
     ap.add_argument("--clip", type=float, default=0.0,
                     help="max_grad_norm of the optimizers (global-norm clipping; 0 = off).  With --shard the "
                          "sharded run must also give the parameters of the unsharded clipped run")
+    ap.add_argument("--lars", type=float, default=0.0,
+                    help="lars_trust of the SGD (LARS trust ratios; 0 = off).  With --shard the sharded run must "
+                         "also give the parameters of the unsharded LARS run")
     a = ap.parse_args()
+    assert a.lars <= 0 or a.optimizer == "sgd", "--lars goes with --optimizer sgd"
     ctx = D.setup(a.backend)
     N, r, dev = ctx.world_size, ctx.rank, ctx.device
     B = a.batch
@@ -75,6 +79,8 @@ def main():
               if comm is not None else None)
         # (built after the wrapper: sharding re-lays the flat buffers out)
         kw = dict(max_grad_norm=a.clip) if a.clip > 0 else {}
+        if a.lars > 0:
+            kw.update(lars_trust=a.lars, weight_decay=1e-4)
         opt = (SGD(m.parameters(), lr=0.02, momentum=0.9, **kw) if a.optimizer == "sgd"
                else Adam(m.parameters(), lr=1e-3, **kw))
         batches = []
@@ -93,6 +99,13 @@ def main():
             st = {k: float(v) for k, v in opt.grad_clip_stats().items()}
             print(f"rank {rank}/{world}: clip stats {st}", flush=True)
             assert st["steps"] == len(batches) and st["skipped"] == 0 and st["clipped"] > 0, st
+        if a.lars > 0:
+            ls = opt.lars_stats()
+            ad = torch.tensor(ls["adapted"])
+            rt = ls["ratio"].cpu()
+            print(f"rank {rank}/{world}: lars ratios {[round(v, 5) for v in rt.tolist()]}", flush=True)
+            assert bool(torch.isfinite(rt).all()) and bool((rt[ad] > 0).all()) and bool((rt[~ad] == 1).all()), rt
+            assert bool((rt[ad] != 1).any()), rt
         torch.cuda.synchronize()
         return m, bl
 
@@ -116,7 +129,7 @@ def main():
             print("GRAPHED_DP_OK", flush=True)
         D.teardown(ctx)
         return
-    if a.clip > 0 and a.shard:
+    if (a.clip > 0 or a.lars > 0) and a.shard:
         mu, _ = run(N, r, TorchComm(), shard=False)
         gotu = torch.cat([p.detach().flatten().cpu() for p in mu.parameters()])
         torch.manual_seed(0)
@@ -125,7 +138,7 @@ def main():
         p0 = torch.cat([p.detach().flatten() for p in m0.parameters()])
         du, dr = (got - p0).double(), (gotu - p0).double()
         err = (du - dr).norm().item() / max(dr.norm().item(), 1e-12)
-        print(f"rank {r}: clipped sharded vs unsharded relative update difference {err:.3e}", flush=True)
+        print(f"rank {r}: clipped / LARS sharded vs unsharded relative update difference {err:.3e}", flush=True)
         ok = ok and err < (2e-2 if a.comm_dtype == "fp32" else 5e-2)
     if a.oneshot:
         c1 = TorchComm()
