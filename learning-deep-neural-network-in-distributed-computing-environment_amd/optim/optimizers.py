@@ -48,8 +48,6 @@ from ..ops import _ext
 from ..utils.flat_params import owner_of
 
 
-
-
 def _refuse_partial_sharded(params):
     """A param group that does not map onto one whole FlatParams would take the per-tensor
     update path; on a sharded DataParallel buffer (only this rank's shard of flat.grad is
@@ -70,6 +68,22 @@ _TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars")
 # past the segments are never written and hold 1 (alignment gaps map to the last one)
 _LARS_SLOTS, _LARS_GAP = 65536, 65535
 _CAPTURE_MSG = "run an eager optimizer step before capturing it into a graph"
+# lengths of the fp32 device vectors of _ls() (clip_scratch: as many slots as the ranges need)
+_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1}
+
+
+def _graph_state(store: dict, key, capturing: bool, make):
+    """(Re)build ``store[key]``, device state that an eager step allocates and a captured graph
+    reads -- which a capture must not do: it asks for an eager step first."""
+    if capturing:
+        raise RuntimeError(_CAPTURE_MSG)
+    store[key] = v = make()
+    return v
+
+
+def _cut(sl, *ts):
+    """``t[sl]`` of every tensor (None stays None); ``sl`` None: the whole buffers, no views to build."""
+    return ts if sl is None else tuple(t[sl] if t is not None else None for t in ts)
 
 
 def lars_chunk_table(bounds, ranges, chunk):
@@ -129,23 +143,237 @@ class _Lars:
 
     def table(self, ranges, capturing):
         """Device chunk tables + partial slots of seg_sumsq over ``ranges`` (built once per set)."""
-        key = tuple(ranges)
-        t = self.tables.get(key)
-        if t is None:
-            if capturing:
-                raise RuntimeError(_CAPTURE_MSG)
+        def make():
             chunks, segs = lars_chunk_table(self.bounds, ranges, _ext.C().seg_sumsq_chunk())
             segtab = [(a, b, int(ad), 0) for (a, b), ad in zip(segs, self.adapt)]
             i32 = dict(dtype=torch.int32, device=self.device)
-            t = dict(ranges=[tuple(r) for r in ranges],
-                     chunks=torch.tensor(chunks, **i32).reshape(-1, 4), segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
-                     partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
-            self.tables[key] = t
-        return t
+            return dict(ranges=[tuple(r) for r in ranges], chunks=torch.tensor(chunks, **i32).reshape(-1, 4),
+                        segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
+                        partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
+        key = tuple(ranges)
+        return self.tables.get(key) or _graph_state(self.tables, key, capturing, make)
 
     def elem_ratio(self, lo, hi):
         """The ratio of every element of the flat range [lo, hi) (torch paths)."""
         return self.ratio[self.seg_of[lo // 64: hi // 64]].repeat_interleave(64)
+
+    def sums_torch(self, f, ranges):
+        """seg_sumsq in torch ops: [2][S] fp64 sums of squares of master / grad over ``ranges``."""
+        out = torch.zeros(2, self.S + 1, dtype=torch.float64, device=self.device)
+        for lo, hi in ranges:
+            if lo % 64 or hi % 64:
+                raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
+            if hi <= lo:
+                continue
+            idx = self.seg_of[lo // 64: hi // 64].clamp(max=self.S)
+            for k, buf in enumerate((f.master, f.grad)):
+                out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
+        return out[:, :self.S]
+
+    def finalize_torch(self, sums, gscale, wd):
+        """lars_finalize in torch ops; ``gscale`` = grad_scale (* the clip coefficient)."""
+        trust, eps = self.hdr.double()
+        wn = sums[0].double().sqrt()
+        gn = sums[1].double().sqrt() * gscale
+        r = trust * wn / (gn + wd * wn + eps)
+        over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
+        r = torch.where(over, torch.zeros_like(r), r)
+        r = torch.where(self.adapt_t & (wn > 0) & (gn > 0), r, torch.ones_like(r))
+        self.ratio[:self.S] = r.float()
+        self.w_norm.copy_(wn)
+        self.g_norm.copy_(gn)
+
+
+def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
+    """clip_finalize's math in torch ops: ``total_sq`` = the sum of squares (0-d / 1-element)."""
+    norm = (total_sq.reshape(()).double().sqrt() * grad_scale).float()
+    finite = torch.isfinite(norm)
+    coef = torch.where(finite, (cl[_CLIP_MAX] / (norm + 1e-6)).clamp(max=1.0), torch.zeros_like(norm))
+    cl[_CLIP_COEF] = coef
+    cl[_CLIP_SKIP] = (~finite).float()
+    cl[_CLIP_NORM] = norm
+    cl[_CLIP_STEPS] += 1
+    cl[_CLIP_CLIPPED] += (finite & (coef < 1)).float()
+    cl[_CLIP_SKIPPED] += (~finite).float()
+
+
+class _FlatStep:
+    """ONE optimizer step of one flat buffer ``f``, as the stages every driver runs in this order:
+
+        norm(ranges) -> [all-reduce ``local``] -> finalize(reduced) -> update(lo, hi) ... -> end()
+
+    ``local``: the fp32 vector that must be all-reduced between ``norm`` and ``finalize`` -- None
+    unless the buffer is sharded and clipping or LARS is on.  With clipping alone it is the
+    1-element sum of squares; with LARS the per-segment [master, grad] sums ``[2S]`` with
+    clipping's scalar behind them.  Building the step allocates (an eager step) or looks up (a
+    capture) every piece of device state and, when not capturing, writes the hyper-parameters.
+
+    Skipping (a non-finite norm): the native kernels read the flag on the device, so every
+    launch is issued and the host step count advances (Adam's device count does not); on the
+    torch paths ``skip`` is a host bool after ``finalize`` and nothing changes.
+
+    ``clip``: ``(state, skip)`` of a norm taken outside (several groups / loose tensors).
+
+    The stages hand their results on in the object, so the order is a precondition: when the
+    step takes a norm (``normed``: its own clipping, or LARS), ``norm`` comes before ``finalize``;
+    ``finalize`` comes before any ``update``.  With neither, ``norm`` may be left out."""
+
+    # what a plain step (no clipping, no LARS) never sets
+    own_clip = normed = False
+    cl = skip = L = hp = local = tab = sumsq = ctx = None
+    ranges, nparts = (), 0
+
+    def __init__(self, opt, f, group, clip=None, sharded=False):
+        self.opt, self.f, self.group = opt, f, group
+        self.st = st = opt._ls()
+        self.native = native = _ext.use_native(f.master)
+        dev = f.master.device
+        thr, lars = opt._clip_threshold(), opt._lars_conf()
+        if clip is not None or thr is not None or lars is not None:
+            self._norm_state(clip, thr, lars, dev, sharded)
+        if native:
+            hp = st.get("hp")
+            self.hp = hp if hp is not None and hp.device == dev else opt._state("hp", dev)
+        if not opt._ldnn_capturing:
+            # inside a hipGraph capture the writes are NOT recorded: the graph reads the tensors,
+            # and GraphedStep refreshes them (sync_hyperparams) whenever a value changes
+            opt._write_hyperparams(group["lr"], (thr, lars))
+
+    def _norm_state(self, clip, thr, lars, dev, sharded):
+        opt = self.opt
+        if clip is not None:
+            self.cl, self.skip = (clip[0].to(dev), None) if self.native else clip
+        elif thr is not None:
+            self.own_clip, self.cl = True, opt._state("clip", dev)
+        if lars is not None:
+            self.L = opt._lars_state(lars[2], self.f)
+        self.normed = self.own_clip or self.L is not None
+        if sharded and self.normed:
+            self.local = self.L.local if self.L is not None else opt._state("clip_local", dev)
+
+    def _seg_sums(self):
+        L, f = self.L, self.f
+        self.tab = t = L.table(self.ranges, self.opt._ldnn_capturing)
+        _ext.C().seg_sumsq(f.master, f.grad, t["chunks"], t["partials"], t["ranges"], [b for b, _ in L.bounds])
+
+    def norm(self, ranges):
+        """The sums of squares over ``ranges`` (of a sharded buffer: this rank's shard ranges, on
+        rank 0 also the replicated tail, which every rank holds alike and one rank counts):
+        clipping's per-workgroup partials, one range after the other in the scratch slots, and --
+        where they have to travel (``local``) -- their total and LARS's per-segment sums."""
+        if not self.normed:
+            return
+        f, L, local = self.f, self.L, self.local
+        self.ranges = ranges = [(lo, hi) for lo, hi in ranges if hi > lo]
+        if self.native:
+            C = _ext.C()
+            if self.own_clip:
+                sc = self.opt._state("clip_scratch", f.master.device,
+                                     max(1, sum(C.grad_sumsq_parts(hi - lo) for lo, hi in ranges)))
+                self.nparts = 0
+                for lo, hi in ranges:
+                    g = f.grad if lo == 0 and hi == f.numel else f.grad[lo:hi]    # (the whole buffer: no view to build)
+                    self.nparts += C.grad_sumsq(g, sc, self.nparts)
+                if local is not None:
+                    C.sumsq_total(sc, self.nparts, local[-1:])
+            if L is not None and local is not None:
+                self._seg_sums()
+                C.lars_finalize(self.tab["partials"], self.tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, 1.0, 0.0,
+                                sums_out=local)
+            return
+        if self.own_clip:
+            scale = f.grad_scale if local is None else 1.0    # (a reduced sum is scaled when finalized)
+            self.sumsq = torch.zeros((), dtype=torch.float64, device=f.master.device)
+            for lo, hi in ranges:
+                self.sumsq = self.sumsq + (f.grad[lo:hi].double() * scale).square().sum()
+            if local is not None:
+                local[-1:].copy_(self.sumsq.reshape(1))
+        if L is not None and local is not None:
+            local[:2 * L.S].copy_(L.sums_torch(f, ranges).t().reshape(-1))
+
+    def finalize(self, reduced: bool):
+        """The clip state, then the LARS ratios (which use the clip coefficient), then the
+        optimizer's per-step prologue.  ``reduced``: the sums come from the all-reduced ``local``;
+        else straight from ``norm``'s partials (LARS's are taken here: nothing waited for them)."""
+        if self.normed:
+            self._finalize_norms(reduced)
+        if not self.skip:
+            self.ctx = self.opt._begin_ranges(self)
+
+    def _finalize_norms(self, reduced):
+        f, L, cl, local = self.f, self.L, self.cl, self.local
+        gs, wd = f.grad_scale, self.group["weight_decay"]
+        if self.native:
+            C = _ext.C()
+            if self.own_clip:
+                sc = self.st["clip_scratch"]
+                if reduced:
+                    C.clip_finalize(sc, 0, cl, gs, ext=local[-1:])
+                else:
+                    C.clip_finalize(sc, self.nparts, cl, gs)
+            if L is not None:
+                if reduced:
+                    C.lars_finalize(None, self.tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, gs, wd,
+                                    ext=local, clip=cl)
+                else:
+                    self._seg_sums()
+                    C.lars_finalize(self.tab["partials"], self.tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, gs,
+                                    wd, clip=cl)
+        else:
+            if self.own_clip:
+                if reduced:
+                    _clip_finalize_torch(cl, local[-1:], gs)
+                else:
+                    _clip_finalize_torch(cl, self.sumsq)
+                self.skip = bool(cl[_CLIP_SKIP].item())
+            if self.skip:
+                return
+            if L is not None:
+                sums = local[:2 * L.S].view(L.S, 2).t() if reduced else L.sums_torch(f, self.ranges)
+                L.finalize_torch(sums, gs * (cl[_CLIP_COEF].double() if cl is not None else 1.0), wd)
+
+    def update(self, lo: int, hi: int, zero=()):
+        """Update flat elements [lo, hi): one fused launch (which also zeroes the flat gradient
+        ranges ``zero``), or the same math in torch ops."""
+        if hi <= lo:
+            return
+        f, L = self.f, self.L
+        sl = None if lo == 0 and hi == f.numel else slice(lo, hi)    # (None: the whole buffer, no views to build)
+        if self.native:
+            if L is not None and (lo % 64 or hi % 64):
+                raise ValueError(f"LARS: the update range [{lo}, {hi}) is not 64-element aligned")
+            self.opt._update_native(self, sl, zero if lo == 0 else [(a - lo, b - lo) for a, b in zero])
+            return
+        if not self.skip:
+            p, g, shadow = _cut(sl, f.master, f.grad, f.shadow)
+            g = g * f.grad_scale
+            if self.cl is not None:
+                g = g * self.cl[_CLIP_COEF]
+            self.opt._update_torch(self, sl, p, g, L.elem_ratio(lo, hi) if L is not None else None)
+            if shadow is not None:
+                shadow.copy_(p)
+        for a, b in zero:
+            f.grad[a:b].zero_()
+
+    def end(self):
+        if not self.skip:
+            st = self.st
+            st["step"] = st.get("step", 0) + 1
+
+
+class _RangeStep(_FlatStep):
+    """``range_updater``'s form: driven from outside ``step()``, and its ranges must cover the buffer."""
+    done = 0
+
+    @torch.no_grad()
+    def update(self, lo: int, hi: int, zero=()):
+        self.done += max(hi - lo, 0)
+        super().update(lo, hi, zero)
+
+    def end(self):
+        if self.done != self.f.numel:
+            raise RuntimeError(f"range updates covered {self.done} of {self.f.numel} flat elements")
+        super().end()
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -164,37 +392,86 @@ class _FlatOptimizer(torch.optim.Optimizer):
         sd["ldnn_flat_state"] = flat
         return sd
 
+    # ---- device state an eager step allocates and a captured graph reads ---------------
+    _ldnn_capturing = False    # set on the instance by GraphedStep / GraphedDPStep around their capture
+
+    def _state(self, key, device, n=None):
+        """The fp32 device vector ``key`` of ``_ls()``, at least ``n`` long: ``hp`` [lr, Adam's
+        step count], ``clip`` [max_norm, coef, skip, last_norm, steps, clipped, skipped, -],
+        ``clip_scratch`` (grad_sumsq's partial slots), ``clip_local`` (the 1-element local sum)."""
+        st = self._ls()
+        t = st.get(key)
+        n = n or _STATE_LEN[key]
+        if t is None or t.device != device or t.numel() < n:
+            t = _graph_state(st, key, self._ldnn_capturing, lambda: torch.zeros(n, dtype=torch.float32, device=device))
+            if key == "hp":
+                t[1] = float(st.get("step", 0))
+        return t
+
+    def _lars_state(self, excl, flat, params=None, device=None):
+        """The LARS device state over ``flat`` (None: over the loose ``params``)."""
+        st = self._ls()
+        device = flat.master.device if flat is not None else device
+        L = st.get("lars")
+        if L is None or L.flat is not flat or L.device != device or L.exclude_1d != excl or \
+                (flat is None and L.S != len(params)):
+            L = _graph_state(st, "lars", self._ldnn_capturing, lambda: _Lars(flat, params, excl, device))
+        return L
+
+    def _write_hyperparams(self, lr=None, conf=None):
+        """Write the learning rate, the clipping threshold and LARS's trust coefficient and eps
+        into whichever of their device tensors exist.  ``conf``: ``(_clip_threshold(),
+        _lars_conf())`` where the caller has them already."""
+        st = self._ls()
+        hp, cl, L = st.get("hp"), st.get("clip"), st.get("lars")
+        if hp is not None:
+            hp[0].fill_(self.param_groups[0]["lr"] if lr is None else lr)
+        if cl is None and L is None:
+            return
+        mx, lars = conf if conf is not None else (self._clip_threshold(), self._lars_conf())
+        if cl is not None:
+            # (clipping switched off after a graph was captured: an infinite threshold makes the
+            # captured kernels' coefficient 1; the non-finite guard of that graph stays)
+            cl[_CLIP_MAX].fill_(mx if mx is not None else float("inf"))
+        if L is not None and lars is not None:
+            L.hdr[0].fill_(lars[0])
+            L.hdr[1].fill_(lars[1])
+
+    @torch.no_grad()
+    def sync_hyperparams(self):
+        """Write the current learning rate (and clipping threshold, LARS trust coefficient and
+        eps) into the device hyper-parameter tensors."""
+        self._write_hyperparams()
+
+    def _buf(self, name, like):
+        st = self._ls()
+        b = st.get(name)
+        if b is None or b.shape != like.shape or b.device != like.device:
+            b = torch.zeros_like(like)
+            st[name] = b
+        return b
+
     # ---- global-norm gradient clipping ------------------------------------------------
+    def _same_in_groups(self, read, what):
+        """``read(group)``, which must be the same in every param group (None without groups)."""
+        groups = self.param_groups
+        if not groups:
+            return None
+        v = read(groups[0])
+        for g in groups[1:]:
+            if read(g) != v:
+                raise ValueError(f"{what}; got {[read(g_) for g_ in groups]}")
+        return v
+
+    @staticmethod
+    def _group_threshold(g):
+        v = g.get("max_grad_norm")
+        return None if v is None or float(v) <= 0 else float(v)
+
     def _clip_threshold(self):
         """The clipping threshold (None: off).  One threshold for the whole optimizer."""
-        vals = [g.get("max_grad_norm") for g in self.param_groups]
-        vals = [None if v is None or float(v) <= 0 else float(v) for v in vals]
-        if any(v != vals[0] for v in vals):
-            raise ValueError(f"max_grad_norm must be the same in every param group (the norm is global); got {vals}")
-        return vals[0] if vals else None
-
-    def _clip_state(self, device, scratch: int = 0):
-        """The device clipping state [max_norm, coef, skip, last_norm, steps, clipped, skipped, -]
-        (and ``scratch`` partial slots + the 1-element local sum for the native kernels), with
-        the current threshold written -- like ``hp``: allocated by an eager step, read by graphs."""
-        st = self._ls()
-        cl = st.get("clip")
-        capturing = getattr(self, "_ldnn_capturing", False)
-        if cl is None or cl.device != device:
-            if capturing:
-                raise RuntimeError("run an eager optimizer step before capturing it into a graph")
-            cl = torch.zeros(_CLIP_LEN, dtype=torch.float32, device=device)
-            st["clip"] = cl
-        if scratch:
-            sc = st.get("clip_scratch")
-            if sc is None or sc.device != device or sc.numel() < scratch:
-                if capturing:
-                    raise RuntimeError("run an eager optimizer step before capturing it into a graph")
-                st["clip_scratch"] = torch.zeros(scratch, dtype=torch.float32, device=device)
-                st["clip_local"] = torch.zeros(1, dtype=torch.float32, device=device)
-        if not capturing:
-            cl[_CLIP_MAX].fill_(self._clip_threshold())
-        return cl
+        return self._same_in_groups(self._group_threshold,
+                                    "max_grad_norm must be the same in every param group (the norm is global)")
 
     def grad_clip_stats(self):
         """Device scalars ``last_norm`` / ``steps`` / ``clipped`` / ``skipped`` of the clipped
@@ -204,41 +481,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
         cl = self._ls().get("clip")
         if cl is None:
             ps = self.param_groups[0]["params"]
-            cl = self._clip_state(ps[0].device if ps else torch.device("cpu"))
+            cl = self._state("clip", ps[0].device if ps else torch.device("cpu"))
+            self._write_hyperparams()
         return {"last_norm": cl[_CLIP_NORM], "steps": cl[_CLIP_STEPS], "clipped": cl[_CLIP_CLIPPED],
                 "skipped": cl[_CLIP_SKIPPED]}
 
-    @staticmethod
-    def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
-        """clip_finalize's math in torch ops: ``total_sq`` = the sum of squares (0-d / 1-element)."""
-        norm = (total_sq.reshape(()).double().sqrt() * grad_scale).float()
-        finite = torch.isfinite(norm)
-        coef = torch.where(finite, (cl[_CLIP_MAX] / (norm + 1e-6)).clamp(max=1.0), torch.zeros_like(norm))
-        cl[_CLIP_COEF] = coef
-        cl[_CLIP_SKIP] = (~finite).float()
-        cl[_CLIP_NORM] = norm
-        cl[_CLIP_STEPS] += 1
-        cl[_CLIP_CLIPPED] += (finite & (coef < 1)).float()
-        cl[_CLIP_SKIPPED] += (~finite).float()
-
-    def _clip_begin(self):
-        """Start of a clipped step: the global norm over EVERY group's gradient, before any
-        update.  Returns None (off, or a sharded flat buffer: ``_sharded_step`` does it with
-        its scalar all-reduce), else ``(state, skip)`` -- ``skip`` None on the fused path
-        (the kernels read the flag on the device), a host bool on the torch paths."""
-        if self._clip_threshold() is None:
-            return None
-        flats = [self._flat_for_group(g) for g in self.param_groups]
-        f = flats[0] if len(flats) == 1 else None
-        if f is not None and getattr(f, "shard_sync", None) is not None:
-            return None
-        if f is not None and _ext.use_native(f.master):
-            f.finalize_grads()
-            C = _ext.C()
-            cl = self._clip_state(f.master.device, C.grad_sumsq_parts(f.grad.numel()))
-            sc = self._ls()["clip_scratch"]
-            C.clip_finalize(sc, C.grad_sumsq(f.grad, sc, 0), cl, f.grad_scale)
-            return cl, None
+    def _loose_clip(self, flats):
+        """The clipped step of several groups, or of tensors outside a flat buffer: the global
+        norm over EVERY group's gradient in torch ops, before any update.  Returns ``(state,
+        skip)`` with the skip flag read on the host (a sync per step; such an optimizer cannot be
+        captured), or None when no gradient exists."""
         total, dev = None, None
         for g, fl in zip(self.param_groups, flats):
             if fl is not None:
@@ -251,40 +503,25 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 total = t if total is None else total + t.to(dev)
         if total is None:
             return None
-        cl = self._clip_state(dev)
-        self._clip_finalize_torch(cl, total)
+        cl = self._state("clip", dev)
+        if not self._ldnn_capturing:
+            self._write_hyperparams()
+        _clip_finalize_torch(cl, total)
         return cl, bool(cl[_CLIP_SKIP].item())
 
     # ---- LARS: per-tensor trust ratios (SGD) -------------------------------------------
+    @staticmethod
+    def _group_lars(g):
+        t = g.get("lars_trust")
+        return None if t is None else (float(t), float(g.get("lars_eps", 1e-8)), bool(g.get("lars_exclude_1d", True)))
+
     def _lars_conf(self):
         """``(trust_coef, eps, exclude_1d)``, or None when LARS is off.  One setting for the whole
         optimizer; the keys are read with .get, so state saved before they existed loads."""
-        vals = []
-        for g in self.param_groups:
-            t = g.get("lars_trust")
-            vals.append(None if t is None else (float(t), float(g.get("lars_eps", 1e-8)),
-                                                bool(g.get("lars_exclude_1d", True))))
-        if any(v != vals[0] for v in vals):
-            raise ValueError(f"lars_trust / lars_eps / lars_exclude_1d must be the same in every param group; got {vals}")
-        return vals[0] if vals else None
-
-    def _lars_state(self, flat, params=None, device=None):
-        """The LARS device state, with the current trust coefficient and eps written -- like
-        ``hp``: allocated by an eager step, read by graphs."""
-        trust, eps, excl = self._lars_conf()
-        st = self._ls()
-        L = st.get("lars")
-        device = flat.master.device if flat is not None else device
-        capturing = getattr(self, "_ldnn_capturing", False)
-        if L is None or L.flat is not flat or L.device != device or L.exclude_1d != excl or \
-                (flat is None and L.S != len(params)):
-            if capturing:
-                raise RuntimeError(_CAPTURE_MSG)
-            L = st["lars"] = _Lars(flat, params, excl, device)
-        if not capturing:
-            L.hdr[0].fill_(trust)
-            L.hdr[1].fill_(eps)
-        return L
+        if "lars_trust" not in self.defaults:    # (Adam / AdamW take no LARS settings)
+            return None
+        return self._same_in_groups(self._group_lars,
+                                    "lars_trust / lars_eps / lars_exclude_1d must be the same in every param group")
 
     def lars_stats(self):
         """In segment (flat-buffer) order: the device tensors ``ratio`` / ``w_norm`` / ``g_norm`` of
@@ -296,53 +533,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if L is None:
             f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
             ps = [p for g in self.param_groups for p in g["params"]]
-            L = self._lars_state(f, ps, ps[0].device if ps else torch.device("cpu"))
+            L = self._lars_state(self._lars_conf()[2], f, ps, ps[0].device if ps else torch.device("cpu"))
+            self._write_hyperparams()
         return {"ratio": L.ratio[:L.S], "w_norm": L.w_norm, "g_norm": L.g_norm, "names": list(L.names),
                 "adapted": list(L.adapt)}
-
-    @staticmethod
-    def _lars_sums_torch(L, f, ranges):
-        """seg_sumsq in torch ops: [2][S] fp64 sums of squares of master / grad over ``ranges``."""
-        out = torch.zeros(2, L.S + 1, dtype=torch.float64, device=L.device)
-        for lo, hi in ranges:
-            if lo % 64 or hi % 64:
-                raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
-            if hi <= lo:
-                continue
-            idx = L.seg_of[lo // 64: hi // 64].clamp(max=L.S)
-            for k, buf in enumerate((f.master, f.grad)):
-                out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
-        return out[:, :L.S]
-
-    @staticmethod
-    def _lars_finalize_torch(L, sums, gscale, wd):
-        """lars_finalize in torch ops; ``gscale`` = grad_scale (* the clip coefficient)."""
-        trust, eps = L.hdr.double()
-        wn = sums[0].double().sqrt()
-        gn = sums[1].double().sqrt() * gscale
-        r = trust * wn / (gn + wd * wn + eps)
-        over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
-        r = torch.where(over, torch.zeros_like(r), r)
-        r = torch.where(L.adapt_t & (wn > 0) & (gn > 0), r, torch.ones_like(r))
-        L.ratio[:L.S] = r.float()
-        L.w_norm.copy_(wn)
-        L.g_norm.copy_(gn)
-
-    def _lars_begin(self, f, group, cl):
-        """The ratios of an unsharded flat step, before the update: returns the state (its
-        ``ratio`` / ``segmap`` feed the fused kernel).  ``cl``: the finalized clip state or None."""
-        L = self._lars_state(f)
-        wd = group["weight_decay"]
-        if _ext.use_native(f.master):
-            C = _ext.C()
-            t = L.table([(0, f.numel)], getattr(self, "_ldnn_capturing", False))
-            C.seg_sumsq(f.master, f.grad, t["chunks"], t["partials"], t["ranges"], [b for b, _ in L.bounds])
-            C.lars_finalize(t["partials"], t["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, f.grad_scale, wd,
-                            clip=cl)
-        else:
-            coef = cl[_CLIP_COEF].double() if cl is not None else 1.0
-            self._lars_finalize_torch(L, self._lars_sums_torch(L, f, [(0, f.numel)]), f.grad_scale * coef, wd)
-        return L
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
@@ -370,187 +564,101 @@ class _FlatOptimizer(torch.optim.Optimizer):
             return None
         return f
 
-    def _hp(self, flat, lr):
-        st = self._ls()
-        hp = st.get("hp")
-        if hp is None or hp.device != flat.master.device:
-            if getattr(self, "_ldnn_capturing", False):
-                raise RuntimeError("run an eager optimizer step before capturing it into a graph")
-            hp = torch.zeros(2, dtype=torch.float32, device=flat.master.device)
-            hp[1] = float(st.get("step", 0))
-            st["hp"] = hp
-        # inside a hipGraph capture the lr write is NOT recorded: the graph reads hp,
-        # and GraphedStep refreshes it (sync_hyperparams) whenever the lr changes
-        if not getattr(self, "_ldnn_capturing", False):
-            hp[0].fill_(lr)
-        return hp
-
+    # ---- the step ---------------------------------------------------------------------
     @torch.no_grad()
-    def sync_hyperparams(self):
-        """Write the current learning rate (and clipping threshold, LARS trust coefficient and
-        eps) into the device hyper-parameter tensors."""
-        hp = self._ls().get("hp")
-        if hp is not None:
-            hp[0].fill_(self.param_groups[0]["lr"])
-        cl = self._ls().get("clip")
-        if cl is not None:
-            # (clipping switched off after a graph was captured: an infinite threshold makes the
-            # captured kernels' coefficient 1; the non-finite guard of that graph stays)
-            mx = self._clip_threshold()
-            cl[_CLIP_MAX].fill_(mx if mx is not None else float("inf"))
-        L = self._ls().get("lars")
-        conf = self._lars_conf()
-        if L is not None and conf is not None:
-            L.hdr[0].fill_(conf[0])
-            L.hdr[1].fill_(conf[1])
+    def step(self, closure=None, clear_grads: bool = False):
+        """clear_grads: the update kernel also zeroes the flat gradient after reading it
+        (one pass instead of a later zero_grad fill; on MI355X the zero writes inside
+        the bandwidth-bound update cost about what the fill launch does)."""
+        loss = closure() if closure is not None else None
+        groups = self.param_groups
+        flats = [self._flat_for_group(g) for g in groups]
+        clip = None
+        if len(flats) != 1 or flats[0] is None:
+            # several groups / loose tensors: one norm over all of them in torch ops; and one LARS
+            # setting for every group, or a ValueError, before any update
+            if self._clip_threshold() is not None:
+                clip = self._loose_clip(flats)
+            self._lars_conf()
+        loose = {}           # what the per-tensor updates of this step share
+        for group, f in zip(groups, flats):
+            if f is not None:
+                self._flat_step(f, group, clip, clear_grads)
+            elif clip is None or not clip[1]:
+                self._loose_update(group, clip[0] if clip is not None else None, loose)
+        return loss
 
-    def _buf(self, name, like):
-        st = self._ls()
-        b = st.get(name)
-        if b is None or b.shape != like.shape or b.device != like.device:
-            b = torch.zeros_like(like)
-            st[name] = b
-        return b
+    def _flat_step(self, f, group, clip, clear_grads):
+        """One ``_FlatStep`` over the whole flat buffer; when DataParallel(shard_optimizer=True)
+        owns ``f`` (``f.shard_sync``, a GradBucketer), over this rank's flat ranges (its shard of
+        every reduce-scattered bucket + the replicated tail) with ONE all-reduce of ``local``
+        between the norm and the update, after which the wrapper starts the weight all-gathers.
+        ``shard_sync.step_driver(step)`` replaces the sharded sequence (GraphedDPStep's capture)."""
+        sh = getattr(f, "shard_sync", None)
+        if sh is not None and len(self.param_groups) != 1:
+            # the full-replica update would read flat.grad, of which only this rank's shards hold
+            # reduced values, and no weight all-gather would follow: replicas would silently diverge
+            raise RuntimeError("DataParallel(shard_optimizer=True) needs ONE param group holding the whole "
+                               f"flat buffer; this optimizer has {len(self.param_groups)}")
+        f.finalize_grads()
+        s = _FlatStep(self, f, group, clip, sh is not None)
+        if sh is None:
+            n = f.numel
+            if s.normed:
+                s.norm(((0, n),))
+            s.finalize(False)
+            s.update(0, n, ((0, n),) if clear_grads else ())
+            s.end()
+            return
+        if sh.step_driver is not None:
+            sh.step_driver(s)
+        else:
+            if s.local is not None:
+                s.norm(sh.norm_ranges())
+                sh.comm.all_reduce(s.local)
+            s.finalize(reduced=s.local is not None)
+            for lo, hi in sh.update_ranges():
+                s.update(lo, hi)
+            s.end()
+        sh.after_update()
 
-    # ---- range updates (optimizer overlapped with the backward, train/graphed.py) ----
     def range_updater(self):
-        """A ``_RangeUpdate`` for ONE step of a single flat-buffer group on the GPU
-        (None when the optimizer cannot update by ranges: several groups, no
-        FlatParams, CPU).  ``update(lo, hi)`` runs the fused kernel on flat elements
-        [lo, hi) on the current stream; ``end()`` closes the step.  Every element must
-        be covered exactly once per step."""
+        """A ``_FlatStep``, finalized, for ONE step of a single flat-buffer group on the GPU
+        applied as several range launches (None when the optimizer cannot update by ranges:
+        several groups, no FlatParams, CPU, clipping or LARS).  ``update(lo, hi)`` runs the fused
+        kernel on flat elements [lo, hi) on the current stream; ``end()`` closes the step.  Every
+        element must be covered exactly once per step.  (The sharded step and GraphedDPStep's
+        per-bucket optimizer graphs drive the same object.)"""
         if not self.supports_ranges():
             return None
         group = self.param_groups[0]
-        return _RangeUpdate(self, self._flat_for_group(group), group)
+        s = _RangeStep(self, self._flat_for_group(group), group)
+        s.finalize(reduced=False)
+        return s
 
     def supports_ranges(self) -> bool:
         if self._clip_threshold() is not None:
             return False   # the whole norm must be known before any range updates
         if self._lars_conf() is not None:
             return False   # ... and so must a tensor's whole gradient before any of it moves
-        if len(self.param_groups) != 1 or type(self)._update_range is _FlatOptimizer._update_range:
+        if len(self.param_groups) != 1 or type(self)._update_native is _FlatOptimizer._update_native:
             return False
         f = self._flat_for_group(self.param_groups[0])
         return f is not None and _ext.use_native(f.master)
 
-    def _begin_ranges(self, f, group, clip=None):  # per-step setup on the current stream (subclasses)
+    # ---- what an optimizer supplies (``s``: the _FlatStep; ``sl``: the flat slice, None = whole) ----
+    def _begin_ranges(self, s) -> dict:
+        """Per-step prologue on the current stream, before any range: returns ``s.ctx``."""
         return {}
 
-    def _update_range(self, f, group, ctx, lo, hi):
+    def _update_native(self, s, sl, zero):
         raise NotImplementedError
 
-    def _sharded_step(self, f, group) -> bool:
-        """DataParallel(shard_optimizer=True) owns ``f``: update only this rank's flat
-        ranges (its shard of every reduce-scattered bucket + the replicated tail), then
-        let the data-parallel wrapper start the weight all-gathers.  False otherwise."""
-        sh = getattr(f, "shard_sync", None)
-        if sh is None:
-            return False
-        if len(self.param_groups) != 1:
-            # the full-replica update below would read flat.grad, of which only this rank's
-            # shards hold reduced values, and no weight all-gather would follow: replicas
-            # would silently diverge
-            raise RuntimeError("DataParallel(shard_optimizer=True) needs ONE param group holding the whole "
-                               f"flat buffer; this optimizer has {len(self.param_groups)}")
-        f.finalize_grads()
-        if self._clip_threshold() is not None or self._lars_conf() is not None:
-            return self._sharded_step_clipped(f, group, sh)
-        ctx = self._begin_ranges(f, group)
-        parts = getattr(sh, "step_parts", None)
-        if parts is not None:   # the caller interleaves its own work per bucket (GraphedDPStep capture)
-            parts(lambda lo, hi: self._update_range(f, group, ctx, lo, hi) if hi > lo else None)
-        else:
-            for lo, hi in sh.update_ranges():
-                if hi > lo:
-                    self._update_range(f, group, ctx, lo, hi)
-        st = self._ls()
-        st["step"] = st.get("step", 0) + 1
-        sh.after_update()
-        return True
+    def _update_torch(self, s, sl, p, g, ratio):
+        raise NotImplementedError
 
-    def _sharded_step_clipped(self, f, group, sh) -> bool:
-        """The sharded step with global-norm clipping and / or LARS, in three phases: ``norm``
-        (sums of squares of this rank's shard ranges -- on rank 0 also of the replicated tail,
-        which every rank holds alike, so it is counted once -- into one local vector), ONE
-        all-reduce of that vector, ``update`` (finalize the coefficient / the ratios, then every
-        range update).  The vector is the scalar gradient sum with clipping alone; with LARS
-        the per-segment [master, grad] sums ``[2S]``, followed by clipping's scalar.  Every
-        bucket's post_collective has run before.  ``sh.clip_phases(norm, local, update)``: a
-        caller that captures the two compute phases into graphs and issues the all-reduce
-        itself (GraphedDPStep); else the all-reduce goes through ``sh.comm`` here."""
-        native = _ext.use_native(f.master)
-        clipped = self._clip_threshold() is not None
-        ranges = [(lo, hi) for lo, hi in sh.norm_ranges() if hi > lo]
-        st = self._ls()
-        L = self._lars_state(f) if self._lars_conf() is not None else None
-        cl = None
-        if native:
-            C = _ext.C()
-            if clipped:
-                cl = self._clip_state(f.master.device, max(1, sum(C.grad_sumsq_parts(hi - lo) for lo, hi in ranges)))
-            tab = L.table(ranges, getattr(self, "_ldnn_capturing", False)) if L is not None else None
-        elif clipped:
-            cl = self._clip_state(f.master.device)
-            if st.get("clip_local") is None or st["clip_local"].device != f.master.device:
-                st["clip_local"] = torch.zeros(1, dtype=torch.float32, device=f.master.device)
-        local = st["clip_local"] if L is None else L.local
-        clip_local = local[local.numel() - 1:] if clipped else None
-        wd = group["weight_decay"]
-
-        def norm():
-            if native:
-                if clipped:
-                    sc, slot = st["clip_scratch"], 0
-                    for lo, hi in ranges:
-                        slot += C.grad_sumsq(f.grad[lo:hi], sc, slot)
-                    C.sumsq_total(sc, slot, clip_local)
-                if L is not None:
-                    C.seg_sumsq(f.master, f.grad, tab["chunks"], tab["partials"], tab["ranges"],
-                                [b for b, _ in L.bounds])
-                    C.lars_finalize(tab["partials"], tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, 1.0, 0.0,
-                                    sums_out=local)
-            else:
-                if clipped:
-                    tot = torch.zeros((), dtype=torch.float64, device=f.master.device)
-                    for lo, hi in ranges:
-                        tot = tot + f.grad[lo:hi].double().square().sum()
-                    clip_local.copy_(tot.reshape(1))
-                if L is not None:
-                    local[:2 * L.S].copy_(self._lars_sums_torch(L, f, ranges).t().reshape(-1))
-
-        def update():
-            skip = None
-            if native:
-                if clipped:
-                    C.clip_finalize(st["clip_scratch"], 0, cl, f.grad_scale, ext=clip_local)
-                if L is not None:
-                    C.lars_finalize(None, tab["segtab"], L.hdr, L.ratio, L.w_norm, L.g_norm, f.grad_scale, wd,
-                                    ext=local, clip=cl)
-            elif clipped:
-                self._clip_finalize_torch(cl, clip_local, f.grad_scale)
-                skip = bool(cl[_CLIP_SKIP].item())
-            if skip:   # (torch path: decided on the host; the fused kernels read the flag themselves)
-                return
-            if L is not None and not native:
-                coef = cl[_CLIP_COEF].double() if clipped else 1.0
-                self._lars_finalize_torch(L, local[:2 * L.S].view(L.S, 2).t(), f.grad_scale * coef, wd)
-            kw = {} if L is None else {"lars": L}
-            ctx = self._begin_ranges(f, group, clip=(cl, skip) if clipped else None, **kw)
-            for lo, hi in sh.update_ranges():
-                if hi > lo:
-                    self._update_range(f, group, ctx, lo, hi)
-            st["step"] = st.get("step", 0) + 1
-
-        phases = getattr(sh, "clip_phases", None)
-        if phases is not None:
-            phases(norm, local, update)
-        else:
-            norm()
-            sh.comm.all_reduce(local)
-            update()
-        sh.after_update()
-        return True
+    def _loose_update(self, group, cl, loose):
+        raise NotImplementedError
 
     def zero_grad(self, set_to_none: bool = True):
         for group in self.param_groups:
@@ -589,102 +697,55 @@ class SGD(_FlatOptimizer):
                                       nesterov=nesterov, max_grad_norm=max_grad_norm, lars_trust=lars_trust,
                                       lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d))
 
-    @torch.no_grad()
-    def step(self, closure=None, clear_grads: bool = False):
-        """clear_grads: the update kernel also zeroes the flat gradient after reading it
-        (one pass instead of a later zero_grad fill; on MI355X the zero writes inside
-        the bandwidth-bound update cost about what the fill launch does)."""
-        loss = closure() if closure is not None else None
-        clip = self._clip_begin()
-        cl, skip = clip if clip is not None else (None, None)
+    def _begin_ranges(self, s):
+        # (``first`` is host-driven: the very first step seeds the momentum)
+        return s.st.get("step", 0) == 0, self._buf("momentum", s.f.master) if s.group["momentum"] != 0 else s.f.master
+
+    def _update_native(self, s, sl, zero):
+        f, g, L = s.f, s.group, s.L
+        first, mom = s.ctx
+        p, grad, mom, shadow = _cut(sl, f.master, f.grad, mom, f.shadow)
+        lars = None
+        if L is not None:
+            lars = (L.ratio, L.segmap if sl is None else L.segmap[sl.start // 64: sl.stop // 64])
+        _ext.C().sgd_step(p, grad, mom, shadow, s.hp, f.grad_scale, g["momentum"], g["dampening"], g["weight_decay"],
+                          g["nesterov"], first, zero_ranges=zero, clip=s.cl, lars=lars)
+
+    def _update_torch(self, s, sl, p, g_, ratio):
+        g, mu = s.group, s.group["momentum"]
+        first, mom = s.ctx
+        self._sgd_torch(p, g_, _cut(sl, mom)[0] if mu != 0 else None, g["lr"], mu, g["dampening"],
+                        g["weight_decay"], g["nesterov"], first, ratio=ratio)
+
+    def _loose_update(self, group, cl, loose):
+        lr, mu, damp, wd, nest = (group[k] for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"))
         lars = self._lars_conf()
-        loose = None   # LARS over tensors outside a flat buffer: [param index, rows of (ratio, wn, gn)]
-        for group in self.param_groups:
-            lr, mu, damp, wd, nest = (group[k] for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"))
-            f = self._flat_for_group(group)
-            if f is not None and self._sharded_step(f, group):
+        if lars is not None and not loose:
+            # LARS over tensors outside a flat buffer: the next parameter's index, rows of (ratio, wn, gn)
+            ps_all = [p for g_ in self.param_groups for p in g_["params"]]
+            loose.update(k=0, L=self._lars_state(lars[2], None, ps_all, ps_all[0].device))
+            self._write_hyperparams()
+        for p in group["params"]:
+            if loose:
+                k = loose["k"]
+                loose["k"] += 1
+            if p.grad is None:
                 continue
-            if f is not None:
-                f.finalize_grads()
-                st = self._ls()
-                first = st.get("step", 0) == 0
-                mom = self._buf("momentum", f.master) if mu != 0 else f.master
-                if _ext.use_native(f.master):
-                    dcl = cl.to(f.master.device) if cl is not None else None
-                    L = self._lars_begin(f, group, dcl) if lars is not None else None
-                    _ext.C().sgd_step(f.master, f.grad, mom, f.shadow, self._hp(f, lr), f.grad_scale, mu, damp, wd,
-                                      nest, first, zero_ranges=[(0, f.grad.numel())] if clear_grads else [],
-                                      clip=dcl, lars=(L.ratio, L.segmap) if L is not None else None)
-                else:
-                    if not skip:
-                        g = f.grad * f.grad_scale
-                        L = self._lars_begin(f, group, cl) if lars is not None else None
-                        self._sgd_torch(f.master, g if cl is None else g * cl[_CLIP_COEF], mom if mu != 0 else None,
-                                        lr, mu, damp, wd, nest, first,
-                                        ratio=L.elem_ratio(0, f.numel) if L is not None else None)
-                        if f.shadow is not None:
-                            f.shadow.copy_(f.master)
-                    if clear_grads:
-                        f.grad.zero_()
-                    if skip:
-                        continue
-                st["step"] = st.get("step", 0) + 1
-            else:
-                if skip:
-                    continue
-                if lars is not None and loose is None:
-                    ps_all = [p for g_ in self.param_groups for p in g_["params"]]
-                    loose = [0, self._lars_state(None, ps_all, ps_all[0].device)]
-                for p in group["params"]:
-                    if loose is not None:
-                        k = loose[0]
-                        loose[0] += 1
-                    if p.grad is None:
-                        continue
-                    if cl is not None:
-                        p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
-                    ps = self.state.setdefault(p, {})
-                    first = "momentum_buffer" not in ps
-                    if mu != 0 and first:
-                        ps["momentum_buffer"] = torch.zeros_like(p)
-                    ratio = None
-                    if loose is not None:
-                        L = loose[1]
-                        wn, gn = float(p.detach().double().norm()), float(p.grad.double().norm())
-                        ratio = 1.0
-                        if L.adapt[k] and wn > 0 and gn > 0:
-                            ratio = lars[0] * wn / (gn + wd * wn + lars[1])
-                        L.ratio[k], L.w_norm[k], L.g_norm[k] = ratio, wn, gn
-                    self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first,
-                                    ratio=ratio)
-        return loss
-
-    def _begin_ranges(self, f, group, clip=None, lars=None):
-        mu = group["momentum"]
-        hp = self._hp(f, group["lr"]) if _ext.use_native(f.master) else None
-        return dict(hp=hp, first=self._ls().get("step", 0) == 0, clip=clip[0] if clip is not None else None,
-                    mom=self._buf("momentum", f.master) if mu != 0 else f.master, lars=lars)
-
-    def _update_range(self, f, group, ctx, lo, hi):
-        sh = f.shadow[lo:hi] if f.shadow is not None else None
-        L = ctx.get("lars")
-        if not _ext.use_native(f.master):
-            mu = group["momentum"]
-            g = f.grad[lo:hi] * f.grad_scale
-            if ctx["clip"] is not None:
-                g = g * ctx["clip"][_CLIP_COEF]
-            self._sgd_torch(f.master[lo:hi], g, ctx["mom"][lo:hi] if mu != 0 else None,
-                            group["lr"], mu, group["dampening"], group["weight_decay"], group["nesterov"], ctx["first"],
-                            ratio=L.elem_ratio(lo, hi) if L is not None else None)
-            if sh is not None:
-                sh.copy_(f.master[lo:hi])
-            return
-        if L is not None and (lo % 64 or hi % 64):
-            raise ValueError(f"LARS: the update range [{lo}, {hi}) is not 64-element aligned")
-        _ext.C().sgd_step(f.master[lo:hi], f.grad[lo:hi], ctx["mom"][lo:hi], sh, ctx["hp"], f.grad_scale,
-                          group["momentum"], group["dampening"], group["weight_decay"], group["nesterov"],
-                          ctx["first"], clip=ctx["clip"],
-                          lars=(L.ratio, L.segmap[lo // 64: hi // 64]) if L is not None else None)
+            if cl is not None:
+                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+            ps = self.state.setdefault(p, {})
+            first = "momentum_buffer" not in ps
+            if mu != 0 and first:
+                ps["momentum_buffer"] = torch.zeros_like(p)
+            ratio = None
+            if loose:
+                L = loose["L"]
+                wn, gn = float(p.detach().double().norm()), float(p.grad.double().norm())
+                ratio = 1.0
+                if L.adapt[k] and wn > 0 and gn > 0:
+                    ratio = lars[0] * wn / (gn + wd * wn + lars[1])
+                L.ratio[k], L.w_norm[k], L.g_norm[k] = ratio, wn, gn
+            self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first, ratio=ratio)
 
     @staticmethod
     def _sgd_torch(p, g, buf, lr, mu, damp, wd, nest, first, ratio=None):
@@ -708,81 +769,37 @@ class Adam(_FlatOptimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm))
 
-    @torch.no_grad()
-    def step(self, closure=None, clear_grads: bool = False):
-        """clear_grads: as SGD.step."""
-        loss = closure() if closure is not None else None
-        clip = self._clip_begin()
-        cl, skip = clip if clip is not None else (None, None)
-        for group in self.param_groups:
-            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-            f = self._flat_for_group(group)
-            if f is not None and self._sharded_step(f, group):
+    def _begin_ranges(self, s):
+        if s.native:
+            _ext.C().bump_step(s.hp, clip=s.cl)   # once per step, before any range reads the step count
+        m = s.f.master
+        return self._buf("exp_avg", m), self._buf("exp_avg_sq", m), s.st.get("step", 0) + 1
+
+    def _update_native(self, s, sl, zero):
+        f, g = s.f, s.group
+        p, grad, m, v, shadow = _cut(sl, f.master, f.grad, s.ctx[0], s.ctx[1], f.shadow)
+        _ext.C().adam_step(p, grad, m, v, shadow, s.hp, f.grad_scale, *g["betas"], g["eps"], g["weight_decay"],
+                           self.decoupled, zero_ranges=zero, clip=s.cl)
+
+    def _update_torch(self, s, sl, p, g_, ratio):
+        g = s.group
+        m, v = _cut(sl, s.ctx[0], s.ctx[1])
+        self._adam_torch(p, g_, m, v, s.ctx[2], g["lr"], *g["betas"], g["eps"], g["weight_decay"])
+
+    def _loose_update(self, group, cl, loose):
+        lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        for p in group["params"]:
+            if p.grad is None:
                 continue
-            if f is not None:
-                f.finalize_grads()
-                st = self._ls()
-                m, v = self._buf("exp_avg", f.master), self._buf("exp_avg_sq", f.master)
-                if _ext.use_native(f.master):
-                    hp = self._hp(f, lr)
-                    dcl = cl.to(f.master.device) if cl is not None else None
-                    _ext.C().bump_step(hp, clip=dcl)
-                    _ext.C().adam_step(f.master, f.grad, m, v, f.shadow, hp, f.grad_scale, b1, b2, eps, wd,
-                                       self.decoupled, zero_ranges=[(0, f.grad.numel())] if clear_grads else [],
-                                       clip=dcl)
-                    st["step"] = st.get("step", 0) + 1
-                else:
-                    if not skip:
-                        st["step"] = st.get("step", 0) + 1
-                        g = f.grad * f.grad_scale
-                        self._adam_torch(f.master, g if cl is None else g * cl[_CLIP_COEF], m, v, st["step"], lr, b1,
-                                         b2, eps, wd)
-                        if f.shadow is not None:
-                            f.shadow.copy_(f.master)
-                    if clear_grads:
-                        f.grad.zero_()
-            else:
-                if skip:
-                    continue
-                for p in group["params"]:
-                    if p.grad is None:
-                        continue
-                    if cl is not None:
-                        p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
-                    ps = self.state.setdefault(p, {})
-                    if "exp_avg" not in ps:
-                        ps["exp_avg"] = torch.zeros_like(p)
-                        ps["exp_avg_sq"] = torch.zeros_like(p)
-                        ps["step"] = 0
-                    ps["step"] += 1
-                    self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps,
-                                     wd)
-        return loss
-
-    def _begin_ranges(self, f, group, clip=None):
-        hp = None
-        cl = clip[0] if clip is not None else None
-        if _ext.use_native(f.master):
-            hp = self._hp(f, group["lr"])
-            _ext.C().bump_step(hp, clip=cl)   # once per step, before any range reads the step count
-        return dict(hp=hp, clip=cl, m=self._buf("exp_avg", f.master), v=self._buf("exp_avg_sq", f.master),
-                    t=self._ls().get("step", 0) + 1)
-
-    def _update_range(self, f, group, ctx, lo, hi):
-        b1, b2 = group["betas"]
-        sh = f.shadow[lo:hi] if f.shadow is not None else None
-        if not _ext.use_native(f.master):
-            g = f.grad[lo:hi] * f.grad_scale
-            if ctx["clip"] is not None:
-                g = g * ctx["clip"][_CLIP_COEF]
-            self._adam_torch(f.master[lo:hi], g, ctx["m"][lo:hi], ctx["v"][lo:hi],
-                             ctx["t"], group["lr"], b1, b2, group["eps"], group["weight_decay"])
-            if sh is not None:
-                sh.copy_(f.master[lo:hi])
-            return
-        _ext.C().adam_step(f.master[lo:hi], f.grad[lo:hi], ctx["m"][lo:hi], ctx["v"][lo:hi], sh, ctx["hp"],
-                           f.grad_scale, b1, b2, group["eps"], group["weight_decay"], self.decoupled,
-                           clip=ctx["clip"])
+            if cl is not None:
+                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+            ps = self.state.setdefault(p, {})
+            if "exp_avg" not in ps:
+                ps["exp_avg"] = torch.zeros_like(p)
+                ps["exp_avg_sq"] = torch.zeros_like(p)
+                ps["step"] = 0
+            ps["step"] += 1
+            self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps, wd)
 
     def _adam_torch(self, p, g, m, v, t, lr, b1, b2, eps, wd):
         if wd != 0:
@@ -826,25 +843,3 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     if name == "adamw":
         return AdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     raise ValueError(f"unknown optimizer {name!r}")
-
-
-class _RangeUpdate:
-    """One optimizer step applied as several flat-range launches (see
-    ``_FlatOptimizer.range_updater``)."""
-
-    def __init__(self, opt, flat, group):
-        self.opt, self.flat, self.group = opt, flat, group
-        self.ctx = opt._begin_ranges(flat, group)
-        self.done = 0
-
-    @torch.no_grad()
-    def update(self, lo: int, hi: int):
-        if hi > lo:
-            self.opt._update_range(self.flat, self.group, self.ctx, lo, hi)
-            self.done += hi - lo
-
-    def end(self):
-        if self.done != self.flat.numel:
-            raise RuntimeError(f"range updates covered {self.done} of {self.flat.numel} flat elements")
-        st = self.opt._ls()
-        st["step"] = st.get("step", 0) + 1

@@ -193,13 +193,9 @@ class GradBucketer:
         self._gathers: dict = {}   # sharded bucket -> its in-flight weight all-gather
         self.active = False
         self.master_whole = True
-        # step_parts(update): set by a caller that interleaves its own work between the
-        # buckets' optimizer updates (GraphedDPStep's per-bucket optimizer graphs)
-        self.step_parts = None
-        # clip_phases(norm, local, update): the same for a sharded step with global-norm clipping
-        # and / or LARS (the caller captures the two compute phases and issues the all-reduce of
-        # `local`: clipping's scalar, or LARS's per-segment sums with that scalar behind them)
-        self.clip_phases = None
+        # step_driver(step): set by a caller that runs the stages of the sharded optimizer step
+        # (optim.optimizers._FlatStep) itself, with its own work in between (GraphedDPStep's capture)
+        self.step_driver = None
         flat.add_ready_hook(self._on_ready)
         if self.shard:
             flat.shard_sync = self

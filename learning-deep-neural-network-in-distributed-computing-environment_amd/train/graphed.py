@@ -392,46 +392,43 @@ class GraphedDPStep:
             self.g_opts[-1][0].capture_end()
             return
 
-        def parts(update):
-            for k, i in enumerate(order):
-                if k > 0:
-                    self.g_opts[-1][0].capture_end()
-                    begin(i)
-                else:
-                    self.g_opts[-1] = (self.g_opts[-1][0], i)
-                self.bk.post_collective(i)
-                update(*self.bk.update_range(i))
-
-        if self.optimizer._clip_threshold() is not None or self.optimizer._lars_conf() is not None:
-            # global-norm clipping / LARS: no range may update before the whole norm (every
-            # tensor's norms) is known, so the per-bucket graphs give way to a NORM graph (every
-            # bucket's widen + this rank's sums of squares), the host-issued all-reduce of the
-            # local sum (LARS: the vector of per-segment sums, clipping's scalar behind it), and
-            # an UPDATE graph (finalize the coefficient / ratios, step count, every range update)
-            def phases(norm, local, update):
+        def driver(step):
+            if step.local is None:
+                step.finalize(reduced=False)   # (the per-step prologue, e.g. Adam's step count, lands in the first)
+                for k, i in enumerate(order):
+                    if k > 0:
+                        self.g_opts[-1][0].capture_end()
+                        begin(i)
+                    else:
+                        self.g_opts[-1] = (self.g_opts[-1][0], i)
+                    self.bk.post_collective(i)
+                    step.update(*self.bk.update_range(i))
+            else:
+                # global-norm clipping / LARS: no range may update before the whole norm (every
+                # tensor's norms) is known, so the per-bucket graphs give way to a NORM graph (every
+                # bucket's widen + this rank's sums of squares), the host-issued all-reduce of the
+                # local sum (LARS: the vector of per-segment sums, clipping's scalar behind it), and
+                # an UPDATE graph (finalize the coefficient / ratios, step count, every range update)
                 begin(None)
                 for i in order:
                     self.bk.post_collective(i)
-                norm()
+                step.norm(self.bk.norm_ranges())
                 self.g_opts[-1][0].capture_end()
-                self._clip_local = local
+                self._clip_local = step.local
                 begin("clip")
-                update()
+                step.finalize(reduced=True)
+                for lo, hi in self.bk.update_ranges():
+                    step.update(lo, hi)
+            step.end()
 
-            self.bk.clip_phases = phases
-            try:
-                self.optimizer.step()
-            finally:
-                self.bk.clip_phases = None
-            self.g_opts[-1][0].capture_end()
-            return
-
-        begin(None)   # (the optimizer's per-step prologue, e.g. Adam's step count, lands in the first)
-        self.bk.step_parts = parts
+        opt = self.optimizer
+        if opt._clip_threshold() is None and opt._lars_conf() is None:
+            begin(None)   # (before step(): what it launches ahead of the driver lands in the first graph too)
+        self.bk.step_driver = driver
         try:
             self.optimizer.step()
         finally:
-            self.bk.step_parts = None
+            self.bk.step_driver = None
         self.g_opts[-1][0].capture_end()
 
     def _fire(self, idx):

@@ -235,14 +235,14 @@ class FlatParams:
             self.grad[b:e].zero_()
         self._stale = set(self._native)
 
-    @torch.no_grad()
     def finalize_grads(self):
         """Clear gradients still marked zero (their op did not run this step) before a
         consumer reads the flat buffer (optimizer, aggregation)."""
-        if self._stale:
-            for s in self.segments:
-                if id(s.param) in self._stale:
-                    self.storage_view(s, self.grad).zero_()
+        if self._stale:    # (checked first: every optimizer step calls this, usually for nothing)
+            with torch.no_grad():
+                for s in self.segments:
+                    if id(s.param) in self._stale:
+                        self.storage_view(s, self.grad).zero_()
             self._stale.clear()
 
     def reattach_grads(self):
