@@ -56,8 +56,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n_train", type=int, default=None)
     p.add_argument("--n_test", type=int, default=None)
     p.add_argument("--data_root", type=str, default="data")
-    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars"],
-                   help="lars: SGD-momentum with layer-wise adaptive rate scaling (per-tensor trust ratios)")
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars", "lamb"],
+                   help="lars: SGD-momentum with layer-wise adaptive rate scaling (per-tensor trust ratios); "
+                        "lamb: Adam's direction with per-tensor trust ratios |w| / |u| (metrics.jsonl then logs "
+                        "lamb_ratio_min / _median / _max per global epoch)")
+    p.add_argument("--lamb_adapt_1d", action="store_true",
+                   help="--optimizer lamb: also adapt tensors with dim() < 2 (biases, BatchNorm affine)")
     p.add_argument("--lars_trust", type=float, default=0.001,
                    help="--optimizer lars: trust coefficient of the ratio trust * |w| / (|g| + wd * |w| + eps).  "
                         "metrics.jsonl then logs lars_ratio_min / _median / _max per global epoch")
@@ -176,6 +180,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "optimizer", None) == "lars":
         # ... nor for a tensor's whole gradient
         why = "--optimizer lars runs on the autograd path"
+    elif getattr(args, "optimizer", None) == "lamb":
+        # ... nor for a tensor's whole Adam direction
+        why = "--optimizer lamb runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -267,7 +274,9 @@ def main(argv=None):
                                     max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,
                                     **(dict(lars_trust=args.lars_trust, lars_eps=args.lars_eps,
                                             lars_exclude_1d=not args.lars_adapt_1d)
-                                       if args.optimizer == "lars" else {}))
+                                       if args.optimizer == "lars" else
+                                       dict(lamb_exclude_1d=not args.lamb_adapt_1d)
+                                       if args.optimizer == "lamb" else {}))
     scheduler = StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
 
     os.makedirs(args.out_dir, exist_ok=True)

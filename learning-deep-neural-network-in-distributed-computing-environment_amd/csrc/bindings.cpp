@@ -621,6 +621,121 @@ void lars_finalize(const c10::optional<at::Tensor>& partials, const at::Tensor& 
         "lars_finalize");
 }
 
+// LAMB.  Everything is checked here, before any launch: a refused call leaves every buffer as it was.
+int64_t lamb_moments(const at::Tensor& master, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
+                     const at::Tensor& chunks, const at::Tensor& partials, const at::Tensor& hp, double grad_scale,
+                     double beta1, double beta2, double eps, double weight_decay,
+                     const std::vector<std::pair<int64_t, int64_t>>& ranges, const std::vector<int64_t>& seg_offsets,
+                     const c10::optional<at::Tensor>& clip, int64_t policy) {
+  check_dev(master, at::kFloat, "master");
+  check_dev(grad, at::kFloat, "grad");
+  check_dev(m, at::kFloat, "exp_avg");
+  check_dev(v, at::kFloat, "exp_avg_sq");
+  check_dev(chunks, at::kInt, "chunks");
+  check_dev(partials, at::kFloat, "partials");
+  check_dev(hp, at::kFloat, "hp");
+  const int64_t n = master.numel();
+  TORCH_CHECK(master.is_contiguous() && grad.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
+                  grad.numel() == n && m.numel() == n && v.numel() == n && aligned16(master.data_ptr()) &&
+                  aligned16(grad.data_ptr()) && aligned16(m.data_ptr()) && aligned16(v.data_ptr()),
+              "lamb_moments: master / grad / exp_avg / exp_avg_sq must be contiguous, equally long and 16-byte aligned");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4 && chunks.is_contiguous() && aligned16(chunks.data_ptr()),
+              "lamb_moments: chunks must be a dense int32 [nchunks][4] table");
+  for (const auto& r : ranges)
+    TORCH_CHECK(r.first % 64 == 0 && r.second % 64 == 0 && 0 <= r.first && r.first <= r.second && r.second <= n,
+                "lamb_moments: range [", r.first, ", ", r.second, ") must be 64-element aligned and inside [0, ", n,
+                ")");
+  for (const int64_t o : seg_offsets)
+    TORCH_CHECK(o % 64 == 0 && o >= 0 && o <= n, "lamb_moments: segment offset ", o,
+                " must be a multiple of 64 in [0, ", n, "]");
+  const int64_t nchunks = chunks.size(0);
+  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * nchunks, "lamb_moments: partials needs 2 slots per chunk (",
+              2 * nchunks, ")");
+  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2, "lamb_moments: hp must hold [lr, step]");
+  TORCH_CHECK(policy >= 0 && policy <= 2, "lamb_moments: access policy must be 0, 1 or 2");
+  for (const at::Tensor* t : {&grad, &m, &v, &chunks, &partials, &hp})
+    TORCH_CHECK(t->device() == master.device(), "lamb_moments: all tensors must be on one device");
+  const float* cp = clip_ptr(clip, master);
+  ldnn::LambParams lp{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, ldnn::GradZero{}};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(master.device());
+  check(ldnn::lamb_moments(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+                           n, chunks.data_ptr<int32_t>(), (int)nchunks, hp.data_ptr<float>(), (float)grad_scale, lp,
+                           partials.data_ptr<float>(), cur_stream(master), cp, (int)policy),
+        "lamb_moments");
+  return nchunks;
+}
+
+void lamb_finalize(const c10::optional<at::Tensor>& partials, const at::Tensor& segtab, const at::Tensor& ratio,
+                   const at::Tensor& w_norm, const at::Tensor& u_norm, const c10::optional<at::Tensor>& ext,
+                   const c10::optional<at::Tensor>& clip, const c10::optional<at::Tensor>& sums_out) {
+  check_dev(segtab, at::kInt, "segtab");
+  TORCH_CHECK(segtab.dim() == 2 && segtab.size(1) == 4 && segtab.is_contiguous() && aligned16(segtab.data_ptr()),
+              "lamb_finalize: segtab must be a dense int32 [S][4] table");
+  const int64_t S = segtab.size(0);
+  auto f32 = [&](const at::Tensor& t, int64_t need, const char* name) -> float* {
+    check_dev(t, at::kFloat, name);
+    TORCH_CHECK(t.is_contiguous() && t.numel() >= need && t.device() == segtab.device(), "lamb_finalize: ", name,
+                " must hold ", need, " contiguous floats on the table's device");
+    return t.data_ptr<float>();
+  };
+  const float* pp = nullptr;
+  int64_t nchunks = 0;
+  if (partials.has_value()) {
+    pp = f32(*partials, 0, "partials");
+    nchunks = partials->numel() / 2;
+  }
+  float* so = sums_out.has_value() ? f32(*sums_out, 2 * S, "sums_out") : nullptr;
+  float* rp = f32(ratio, so ? 0 : S, "ratio");
+  float* wp = f32(w_norm, so ? 0 : S, "w_norm");
+  float* up = f32(u_norm, so ? 0 : S, "u_norm");
+  const float* ep = ext.has_value() ? f32(*ext, 2 * S, "ext") : nullptr;
+  const float* cp = clip_ptr(clip, segtab);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(segtab.device());
+  check(ldnn::lamb_finalize(pp, (int)nchunks, segtab.data_ptr<int32_t>(), (int)S, ep, cp, rp, wp, up, so,
+                            cur_stream(segtab)),
+        "lamb_finalize");
+}
+
+void lamb_apply(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
+                const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double beta1, double beta2, double eps,
+                double weight_decay, const at::Tensor& ratio, const at::Tensor& map,
+                const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, const c10::optional<at::Tensor>& clip) {
+  check_dev(param, at::kFloat, "param");
+  check_dev(grad, at::kFloat, "grad");
+  check_dev(m, at::kFloat, "exp_avg");
+  check_dev(v, at::kFloat, "exp_avg_sq");
+  check_dev(hp, at::kFloat, "hp");
+  check_dev(ratio, at::kFloat, "lamb ratio");
+  check_dev(map, at::kUInt16, "lamb map");
+  const int64_t n = param.numel();
+  TORCH_CHECK(param.is_contiguous() && grad.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
+                  grad.numel() == n && m.numel() == n && v.numel() == n,
+              "lamb_apply: param / grad / exp_avg / exp_avg_sq must be contiguous and equally long");
+  TORCH_CHECK(n % 64 == 0 && aligned16(param.data_ptr()) && aligned16(grad.data_ptr()) && aligned16(m.data_ptr()) &&
+                  aligned16(v.data_ptr()),
+              "lamb_apply: the range must be 64-element aligned (", n, " elements) and 16-byte aligned");
+  TORCH_CHECK(ratio.is_contiguous() && ratio.numel() == 65536 && map.is_contiguous() && map.numel() * 64 >= n,
+              "lamb_apply: needs a contiguous 65536-entry ratio table and one uint16 map entry per 64 elements");
+  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2, "lamb_apply: hp must hold [lr, step]");
+  for (const at::Tensor* t : {&grad, &m, &v, &hp, &ratio, &map})
+    TORCH_CHECK(t->device() == param.device(), "lamb_apply: all tensors must be on one device");
+  uint16_t* sh = nullptr;
+  if (shadow.has_value()) {
+    check_dev(*shadow, at::kBFloat16, "shadow");
+    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == n && shadow->device() == param.device() &&
+                    (reinterpret_cast<uintptr_t>(shadow->data_ptr()) & 7) == 0,
+                "lamb_apply: bad shadow");
+    sh = bf16_mut(*shadow);
+  }
+  const float* cp = clip_ptr(clip, param);
+  ldnn::LambParams lp{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, grad_zero(zero_ranges, n)};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(param.device());
+  check(ldnn::lamb_apply(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sh,
+                         hp.data_ptr<float>(), lp, n, ratio.data_ptr<float>(), map.data_ptr<uint16_t>(),
+                         cur_stream(param), cp),
+        "lamb_apply");
+}
+
 void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& mom,
               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double momentum,
               double dampening, double weight_decay, bool nesterov, bool first_step,
@@ -2157,6 +2272,21 @@ PYBIND11_MODULE(_C, m) {
         "sums); sums_out: the [2S] sums alone", py::arg("partials"), py::arg("segtab"), py::arg("hdr"),
         py::arg("ratio"), py::arg("w_norm"), py::arg("g_norm"), py::arg("grad_scale"), py::arg("weight_decay"),
         py::arg("ext") = py::none(), py::arg("clip") = py::none(), py::arg("sums_out") = py::none());
+  m.def("lamb_moments", &lamb_moments, "LAMB moments pass over a chunk table (segment, begin / 64, end / 64, counted): "
+        "updates exp_avg / exp_avg_sq and leaves per-chunk sums of w^2 and u^2 (partials[2c], partials[2c + 1]; 0 for an "
+        "uncounted chunk); returns the chunk count", py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("chunks"), py::arg("partials"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("ranges"), py::arg("seg_offsets"),
+        py::arg("clip") = py::none(), py::arg("policy") = (int64_t)1);
+  m.def("lamb_finalize", &lamb_finalize, "per-segment LAMB trust ratios |w| / |u| and norms from lamb_moments' partials "
+        "(+ ext sums); sums_out: the [2S] sums alone", py::arg("partials"), py::arg("segtab"), py::arg("ratio"),
+        py::arg("w_norm"), py::arg("u_norm"), py::arg("ext") = py::none(), py::arg("clip") = py::none(),
+        py::arg("sums_out") = py::none());
+  m.def("lamb_apply", &lamb_apply, "LAMB apply pass: w -= lr * ratio * u over a 64-aligned range (+ bf16 shadow, "
+        "gradient zero ranges)", py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("hp"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("ratio"),
+        py::arg("map"), py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{},
+        py::arg("clip") = py::none());
   m.def("adam_step", &adam_step, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),

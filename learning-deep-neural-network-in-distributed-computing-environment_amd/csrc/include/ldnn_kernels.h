@@ -458,6 +458,35 @@ hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segt
                          const float* hdr, const float* clip, float grad_scale, float weight_decay, float* ratio,
                          float* w_norm, float* g_norm, float* sums_out, hipStream_t s);
 
+// ---- LAMB (You et al. 2020): per-tensor trust ratios |w| / |u| on the Adam direction ----
+//   m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2          (g = grad * grad_scale * clip coef)
+//   u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay * w       (t = hp[1])
+//   w -= lr * ratio[segment] * u
+struct LambParams {
+  float beta1, beta2, eps, weight_decay;
+  GradZero zero;  // lamb_apply clears these (lamb_moments only reads the gradient)
+};
+// The moments pass over a seg_sumsq-style chunk table whose fourth field says whether the chunk
+// is COUNTED: m, v of every chunk are updated, partials[2c] / [2c + 1] = the chunk's sums of w^2 /
+// u^2 (0, 0 for an uncounted chunk; w before this step's write).  One workgroup per chunk, plain
+// stores, no atomics: a chunk's partials do not depend on the grid.  With clip[kClipSkip] set
+// nothing is written.  policy: 1 = nontemporal gradient loads, the rest plain (what every step uses);
+// 0 = everything plain, 2 = everything nontemporal (scripts/bench_lamb.py's A/B).
+hipError_t lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const int32_t* chunks,
+                        int nchunks, const float* hp, float grad_scale, LambParams lp, float* partials,
+                        hipStream_t s, const float* clip = nullptr, int policy = 1);
+// lars_finalize's reduction over (w^2, u^2) partials (+ ext): ratio[i] = wn / un if adapted, wn > 0
+// and un > 0, else 1 (a sum beyond fp32: 0); the clip state lends its skip flag only.
+hipError_t lamb_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
+                         const float* clip, float* ratio, float* w_norm, float* u_norm, float* sums_out,
+                         hipStream_t s);
+// The apply pass over [0, n), n a multiple of 64: u from the stored moments, the ratio through the
+// per-64-element map (as sgd_step's lars_map), master + bf16 shadow written, zero ranges cleared.
+// With clip[kClipSkip] set only the zero ranges are cleared.
+hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v, uint16_t* shadow, const float* hp,
+                      LambParams lp, int64_t n, const float* ratio, const uint16_t* map, hipStream_t s,
+                      const float* clip = nullptr);
+
 // ---- classifier head (<= 64 classes): fused Linear + softmax-xent, and its wgrad
 struct HeadParams {
   const uint16_t* h;      // [B][ldh] bf16 input features

@@ -382,6 +382,9 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __res
 // partials l, l + 64, ... in index order, the 64 lane sums meet in an xor butterfly (every lane
 // ends with the same bits).  ext: [2S] sums added on top (the sharded path's all-reduced vector).
 // sums_out: write the [2S] sums alone; else the ratios (ldnn_kernels.h lars_finalize).
+// LAMB: the same sums (master, Adam direction u) give ratio = wn / un: no header, and the clip state
+// lends its skip flag only (the coefficient went into the moments before u was formed).
+template <bool LAMB>
 __global__ void lars_finalize_kernel(const float* __restrict__ partials, int nchunks, const int4* __restrict__ segtab,
                                      int S, const float* __restrict__ ext, const float* __restrict__ hdr,
                                      const float* __restrict__ clip, float grad_scale, float weight_decay,
@@ -414,17 +417,150 @@ __global__ void lars_finalize_kernel(const float* __restrict__ partials, int nch
       sums_out[2 * s + 1] = (float)ag;
       continue;
     }
-    const double c = clip != nullptr ? (double)clip[kClipCoef] : 1.0;
-    const double wn = sqrt(aw), gn = c * (double)grad_scale * sqrt(ag);
+    const double c = (!LAMB && clip != nullptr) ? (double)clip[kClipCoef] : 1.0;
+    const double wn = sqrt(aw), gn = LAMB ? sqrt(ag) : c * (double)grad_scale * sqrt(ag);
     double r = 1.0;
     if (t.z != 0 && wn > 0.0 && gn > 0.0) {
       // (a sum of squares that overflowed fp32: ratio 0, the tensor does not move)
       const bool over = (float)aw > 3.402823466e38f || (float)ag > 3.402823466e38f;
-      r = over ? 0.0 : (double)hdr[0] * wn / (gn + (double)weight_decay * wn + (double)hdr[1]);
+      if constexpr (LAMB) r = over ? 0.0 : wn / gn;
+      else r = over ? 0.0 : (double)hdr[0] * wn / (gn + (double)weight_decay * wn + (double)hdr[1]);
     }
     ratio[s] = (float)r;
     w_norm[s] = (float)wn;
     g_norm[s] = (float)gn;
+  }
+}
+
+// ---- LAMB (You et al. 2020): the Adam direction u, scaled per tensor by |w| / |u| ----
+// The norm of u needs this step's moments, so the step is two passes: lamb_moments (moment update +
+// per-chunk sums of w^2 and u^2), the finalize above, and lamb_apply, which recomputes u from the
+// stored moments with THIS function (both passes move 42 B per element either way, and u parked
+// in the gradient buffer would change what a caller sees in .grad after step()).
+// rbc1 = 1 / (1 - beta1^t), rbc2 = 1 / (1 - beta2^t)
+__device__ __forceinline__ float lamb_u(float w, float m, float v, float rbc1, float rbc2, const LambParams& lp) {
+  return (m * rbc1) / (sqrtf(v * rbc2) + lp.eps) + lp.weight_decay * w;
+}
+
+// one float4 of the moments pass: new m, v stored; returns u (wq: the weights read).  POL, the access
+// policy: 0 everything plain; 1 (what every step uses) the gradient with nontemporal loads -- it is
+// dead after this pass -- and w, m, v plain, since lamb_apply re-reads all three right after; 2
+// everything nontemporal.  Whole LAMB step (moments + finalize + apply) on ResNet-18's / EnhancedCNN's
+// flat buffers, us, policy 0 / 1 / 2: warm 91.4 / 93.6 / 100.2 and 343.8 / 330.4 / 332.7; with 512 MiB
+// streamed through the cache before every iteration 120.9 / 112.1 / 104.8 and 370.0 / 355.6 / 353.5.
+// Policy 2 makes the moments pass itself faster where the buffers are cold (55 against 70 us) but
+// hands part of it back in the apply pass; 1 is the best or within 1 % of it in three of the four
+// (scripts/bench_lamb.py, profiles/r9/lamb_ab.jsonl).
+template <int POL>
+__device__ __forceinline__ floatx4 lamb_mom4(const float* __restrict__ w, const float* __restrict__ g,
+                                             float* __restrict__ mm, float* __restrict__ vv, int64_t i, float gs,
+                                             float rbc1, float rbc2, const LambParams& lp, floatx4& wq) {
+  constexpr bool NTG = POL >= 1, NTA = POL == 2;
+  wq = ld4<NTA>(w, i);
+  const floatx4 gq = ld4<NTG>(g, i) * gs;
+  floatx4 m = ld4<NTA>(mm, i), v = ld4<NTA>(vv, i), u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    m[j] = lp.beta1 * m[j] + (1.f - lp.beta1) * gq[j];
+    v[j] = lp.beta2 * v[j] + (1.f - lp.beta2) * gq[j] * gq[j];
+    u[j] = lamb_u(wq[j], m[j], v[j], rbc1, rbc2, lp);
+  }
+  st4<NTA>(mm, i, m);
+  st4<NTA>(vv, i, v);
+  return u;
+}
+
+// chunks[c] = (segment, begin / 64, end / 64, counted) as for seg_sumsq_kernel, ONE workgroup per
+// chunk (the grid strides over the chunks): partials[2c] = sum w^2, partials[2c + 1] = sum u^2 over
+// the chunk, plain stores, no atomics, independent of the grid.  An uncounted chunk (another rank
+// counts these elements) updates its moments and stores 0, 0.  A chunk outside [0, n) does nothing.
+template <bool CLIP, int POL>
+__global__ void lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mm,
+                                    float* __restrict__ vv, const int4* __restrict__ chunks, int nchunks, int64_t n,
+                                    const float* __restrict__ hp, float grad_scale, LambParams lp,
+                                    float* __restrict__ partials, ClipArg<CLIP> clip) {
+  static_assert(kBlock == 256, "the cross-wave sum below adds exactly four waves");
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) return;  // a skipped step: moments and partials stay
+    grad_scale *= clip.st[kClipCoef];
+  }
+  const float t = hp[1];
+  const float rbc1 = 1.f / (1.f - powf(lp.beta1, t)), rbc2 = 1.f / (1.f - powf(lp.beta2, t));
+  __shared__ float red[2][kBlock / 64];
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int4 ch = chunks[c];
+    int64_t b = (int64_t)ch.y * 16, e = (int64_t)ch.z * 16;  // in float4s
+    if (ch.y < 0 || ch.z < ch.y || (int64_t)ch.z * 64 > n) b = e = 0;
+    const floatx4 z = {0.f, 0.f, 0.f, 0.f};
+    floatx4 w0 = z, w1 = z, w2 = z, w3 = z, u0 = z, u1 = z, u2 = z, u3 = z;
+    int64_t i = b + threadIdx.x;
+    for (; i + 3 * kBlock < e; i += 4 * kBlock) {
+      floatx4 a0, a1, a2, a3;
+      const floatx4 b0 = lamb_mom4<POL>(w, g, mm, vv, i, grad_scale, rbc1, rbc2, lp, a0);
+      const floatx4 b1 = lamb_mom4<POL>(w, g, mm, vv, i + kBlock, grad_scale, rbc1, rbc2, lp, a1);
+      const floatx4 b2 = lamb_mom4<POL>(w, g, mm, vv, i + 2 * kBlock, grad_scale, rbc1, rbc2, lp, a2);
+      const floatx4 b3 = lamb_mom4<POL>(w, g, mm, vv, i + 3 * kBlock, grad_scale, rbc1, rbc2, lp, a3);
+      w0 += a0 * a0;
+      w1 += a1 * a1;
+      w2 += a2 * a2;
+      w3 += a3 * a3;
+      u0 += b0 * b0;
+      u1 += b1 * b1;
+      u2 += b2 * b2;
+      u3 += b3 * b3;
+    }
+    for (; i < e; i += kBlock) {
+      floatx4 a;
+      const floatx4 bb = lamb_mom4<POL>(w, g, mm, vv, i, grad_scale, rbc1, rbc2, lp, a);
+      w0 += a * a;
+      u0 += bb * bb;
+    }
+    w0 = (w0 + w1) + (w2 + w3);
+    u0 = (u0 + u1) + (u2 + u3);
+    const float sw = wave_sum((w0[0] + w0[1]) + (w0[2] + w0[3]));
+    const float su = wave_sum((u0[0] + u0[1]) + (u0[2] + u0[3]));
+    if ((threadIdx.x & 63) == 0) {
+      red[0][threadIdx.x >> 6] = sw;
+      red[1][threadIdx.x >> 6] = su;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      const float s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+      partials[2 * (int64_t)c + threadIdx.x] = ch.w != 0 ? s : 0.f;
+    }
+    __syncthreads();
+  }
+}
+
+// w -= lr * ratio * u over [0, n) (n a multiple of 64), u recomputed from the moments this step's
+// lamb_moments stored; refreshes the bf16 shadow and clears the gradient zero ranges.  w, m, v: NT
+// (nothing reads them again this step).  CLIP: the skip flag alone (clear the zero ranges only).
+template <bool CLIP>
+__global__ void lamb_apply_kernel(float* __restrict__ param, float* __restrict__ grad, const float* __restrict__ mm,
+                                  const float* __restrict__ vv, bf16_t* __restrict__ shadow,
+                                  const float* __restrict__ hp, LambParams lp, int64_t n,
+                                  const float* __restrict__ ratio, const uint16_t* __restrict__ map,
+                                  ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) {
+      clear_only(lp.zero, grad, n);
+      return;
+    }
+  }
+  const float lr = hp[0], t = hp[1];
+  const float rbc1 = 1.f / (1.f - powf(lp.beta1, t)), rbc2 = 1.f / (1.f - powf(lp.beta2, t));
+  const bool clear = lp.zero.ze[0] > lp.zero.zb[0] || lp.zero.ze[1] > lp.zero.zb[1];
+  const int64_t nv = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += stride) {
+    floatx4 p = ld4<true>(param, i);
+    const floatx4 m = ld4<true>(mm, i), v = ld4<true>(vv, i);
+    if (clear) clear4(lp.zero, grad, i);
+    const float s = lr * ratio[map[i >> 4]];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] -= s * lamb_u(p[j], m[j], v[j], rbc1, rbc2, lp);
+    st4<true>(param, i, p);
+    if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = u16x4{f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
   }
 }
 
@@ -548,8 +684,63 @@ hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segt
   const int waves = kBlock / 64;
   int grid = (S + waves - 1) / waves;
   if (grid > 256) grid = 256;
-  lars_finalize_kernel<<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext, hdr,
+  lars_finalize_kernel<false><<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext, hdr,
                                                clip, grad_scale, weight_decay, ratio, w_norm, g_norm, sums_out);
+  return hipGetLastError();
+}
+
+namespace {
+template <bool LAMB_CLIP>
+void launch_lamb_moments(int grid, int policy, const float* w, const float* g, float* m, float* v, const int4* chunks,
+                         int nchunks, int64_t n, const float* hp, float gs, const LambParams& lp, float* partials,
+                         ClipArg<LAMB_CLIP> ca, hipStream_t s) {
+  if (policy == 1)
+    lamb_moments_kernel<LAMB_CLIP, 1><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
+  else if (policy == 2)
+    lamb_moments_kernel<LAMB_CLIP, 2><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
+  else
+    lamb_moments_kernel<LAMB_CLIP, 0><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
+}
+}  // namespace
+
+hipError_t lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const int32_t* chunks,
+                        int nchunks, const float* hp, float grad_scale, LambParams lp, float* partials,
+                        hipStream_t s, const float* clip, int policy) {
+  if (nchunks <= 0) return hipSuccess;
+  if (policy < 0 || policy > 2) return hipErrorInvalidValue;
+  const int grid = nchunks < g_opt_max_blocks ? nchunks : g_opt_max_blocks;
+  const int4* ct = reinterpret_cast<const int4*>(chunks);
+  if (clip != nullptr)
+    launch_lamb_moments<true>(grid, policy, master, grad, m, v, ct, nchunks, n, hp, grad_scale, lp, partials,
+                              ClipArg<true>{clip}, s);
+  else
+    launch_lamb_moments<false>(grid, policy, master, grad, m, v, ct, nchunks, n, hp, grad_scale, lp, partials,
+                               ClipArg<false>{}, s);
+  return hipGetLastError();
+}
+
+hipError_t lamb_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
+                         const float* clip, float* ratio, float* w_norm, float* u_norm, float* sums_out,
+                         hipStream_t s) {
+  if (S <= 0) return hipSuccess;
+  const int waves = kBlock / 64;
+  int grid = (S + waves - 1) / waves;
+  if (grid > 256) grid = 256;
+  lars_finalize_kernel<true><<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext,
+                                                     nullptr, clip, 1.f, 0.f, ratio, w_norm, u_norm, sums_out);
+  return hipGetLastError();
+}
+
+hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v, uint16_t* shadow, const float* hp,
+                      LambParams lp, int64_t n, const float* ratio, const uint16_t* map, hipStream_t s,
+                      const float* clip) {
+  if (n <= 0) return hipSuccess;
+  if (n % 64 || ratio == nullptr || map == nullptr) return hipErrorInvalidValue;
+  const int grid = grid_for(n / 4);
+  if (clip != nullptr)
+    lamb_apply_kernel<true><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ClipArg<true>{clip});
+  else
+    lamb_apply_kernel<false><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ClipArg<false>{});
   return hipGetLastError();
 }
 

@@ -37,6 +37,13 @@ class.  It is the per-tensor form of the same plumbing -- ``seg_sumsq`` + ``lars
 leave one trust ratio per parameter tensor on the device, the fused SGD looks it up per
 64-element block, and the sharded step all-reduces the ``2S`` per-segment sums (clipping's
 scalar behind them) in its one extra collective.
+
+``Lamb`` (``build_optimizer("lamb")``) is the Adam-side counterpart: see the class.  Its trust
+ratio needs the norm of the Adam direction formed from THIS step's moments, so the step has a
+second reduce stage (``_FlatStep.moments`` / ``ratios``): ``lamb_moments`` updates the moments and
+reduces per tensor, ``lamb_finalize`` leaves the ratios on the device, ``lamb_apply`` writes the
+weights; the sharded step all-reduces the ``2S`` sums in a collective of its own after the
+moments -- they depend on the clip coefficient, which depends on the first reduction.
 """
 from __future__ import annotations
 
@@ -63,7 +70,7 @@ def _refuse_partial_sharded(params):
 # slots of the clipping state tensor (csrc/include/ldnn_kernels.h ClipSlot)
 _CLIP_MAX, _CLIP_COEF, _CLIP_SKIP, _CLIP_NORM, _CLIP_STEPS, _CLIP_CLIPPED, _CLIP_SKIPPED, _CLIP_LEN = 0, 1, 2, 3, 4, 5, 6, 8
 # device-only entries of _ls(): rebuilt by an eager step, never saved
-_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars")
+_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb")
 # LARS ratio table: one slot per uint16 map value, so every map entry is in bounds; the slots
 # past the segments are never written and hold 1 (alignment gaps map to the last one)
 _LARS_SLOTS, _LARS_GAP = 65536, 65535
@@ -106,6 +113,40 @@ def lars_chunk_table(bounds, ranges, chunk):
                 z = min(x + chunk, y)
                 chunks.append((s, x // 64, z // 64, 0))
                 x = z
+        segs.append((first, len(chunks)))
+    return chunks, segs
+
+
+def lamb_chunk_table(bounds, ranges, counted, chunk):
+    """``lars_chunk_table`` for lamb_moments: the chunks cover ``ranges``, and a chunk's fourth
+    field says whether it lies inside the flat ranges ``counted`` (its sums enter this rank's
+    norms) -- the chunks are cut at the edges of ``counted`` so each is wholly in or out."""
+    for lo, hi in counted:
+        if lo % 64 or hi % 64 or lo < 0 or hi < lo:
+            raise ValueError(f"LAMB: the counted range [{lo}, {hi}) is not 64-element aligned")
+    for lo, hi in ranges:
+        if lo % 64 or hi % 64 or lo < 0 or hi < lo:
+            raise ValueError(f"LAMB: the flat range [{lo}, {hi}) is not 64-element aligned")
+    cs = sorted((lo, hi) for lo, hi in counted if hi > lo)
+    pieces = []          # ``ranges`` cut into (lo, hi, counted) runs
+    for lo, hi in sorted((lo, hi) for lo, hi in ranges if hi > lo):
+        x = lo
+        for a, b in cs:
+            a, b = max(a, x), min(b, hi)
+            if b <= a:
+                continue
+            if a > x:
+                pieces.append((x, a, 0))
+            pieces.append((a, b, 1))
+            x = b
+        if x < hi:
+            pieces.append((x, hi, 0))
+    chunks, segs = [], []
+    for s, (b, e) in enumerate(bounds):
+        first = len(chunks)
+        for flag in (1, 0):
+            part, _ = lars_chunk_table([(b, e)], [(lo, hi) for lo, hi, c in pieces if c == flag], chunk)
+            chunks += [(s, x, y, flag) for _, x, y, _ in part]
         segs.append((first, len(chunks)))
     return chunks, segs
 
@@ -184,6 +225,51 @@ class _Lars:
         self.g_norm.copy_(gn)
 
 
+class _Lamb(_Lars):
+    """Device state of LAMB: LARS's layout (segment map, ratio table, norm vectors; ``g_norm``
+    holds |u|), chunk tables per (moments ranges, counted ranges), ``local`` = the [2S] sums a
+    sharded step all-reduces.  ``u``: the torch paths' Adam direction between moments and update."""
+    u = None
+
+    def __init__(self, flat, params, exclude_1d, device):
+        super().__init__(flat, params, exclude_1d, device)
+        self.local = torch.zeros(2 * self.S, dtype=torch.float32, device=device)
+
+    def table(self, ranges, counted, capturing):
+        def make():
+            chunks, segs = lamb_chunk_table(self.bounds, ranges, counted, _ext.C().seg_sumsq_chunk())
+            segtab = [(a, b, int(ad), 0) for (a, b), ad in zip(segs, self.adapt)]
+            i32 = dict(dtype=torch.int32, device=self.device)
+            return dict(ranges=[tuple(r) for r in ranges], chunks=torch.tensor(chunks, **i32).reshape(-1, 4),
+                        segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
+                        partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
+        key = (tuple(ranges), tuple(counted))
+        return self.tables.get(key) or _graph_state(self.tables, key, capturing, make)
+
+    def sums_torch(self, f, ranges):
+        """[2][S] fp64 sums of squares of master / u over ``ranges``."""
+        out = torch.zeros(2, self.S + 1, dtype=torch.float64, device=self.device)
+        for lo, hi in ranges:
+            if lo % 64 or hi % 64:
+                raise ValueError(f"LAMB: the flat range [{lo}, {hi}) is not 64-element aligned")
+            if hi <= lo:
+                continue
+            idx = self.seg_of[lo // 64: hi // 64].clamp(max=self.S)
+            for k, buf in enumerate((f.master, self.u)):
+                out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
+        return out[:, :self.S]
+
+    def finalize_torch(self, sums):
+        """lamb_finalize in torch ops."""
+        wn, un = sums[0].double().sqrt(), sums[1].double().sqrt()
+        over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
+        r = torch.where(over, torch.zeros_like(wn), wn / un)
+        r = torch.where(self.adapt_t & (wn > 0) & (un > 0), r, torch.ones_like(r))
+        self.ratio[:self.S] = r.float()
+        self.w_norm.copy_(wn)
+        self.g_norm.copy_(un)
+
+
 def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
     """clip_finalize's math in torch ops: ``total_sq`` = the sum of squares (0-d / 1-element)."""
     norm = (total_sq.reshape(()).double().sqrt() * grad_scale).float()
@@ -200,7 +286,15 @@ def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
 class _FlatStep:
     """ONE optimizer step of one flat buffer ``f``, as the stages every driver runs in this order:
 
-        norm(ranges) -> [all-reduce ``local``] -> finalize(reduced) -> update(lo, hi) ... -> end()
+        norm(ranges) -> [all-reduce ``local``] -> finalize(reduced)
+            -> moments(update_ranges, counted_ranges) -> [all-reduce ``local2``] -> ratios(reduced)
+            -> update(lo, hi) ... -> end()
+
+    The second line exists only for LAMB (``M``): its trust ratios need the norm of the Adam
+    direction, which needs this step's moments, which need the clip coefficient of the first
+    reduction.  ``moments`` runs over every range this rank updates and counts the sums of those
+    inside ``counted_ranges``; ``local2`` (sharded only) is the [2S] vector of per-segment
+    [master, direction] sums.
 
     ``local``: the fp32 vector that must be all-reduced between ``norm`` and ``finalize`` -- None
     unless the buffer is sharded and clipping or LARS is on.  With clipping alone it is the
@@ -220,17 +314,20 @@ class _FlatStep:
 
     # what a plain step (no clipping, no LARS) never sets
     own_clip = normed = False
-    cl = skip = L = hp = local = tab = sumsq = ctx = None
-    ranges, nparts = (), 0
+    cl = skip = L = M = hp = local = local2 = tab = mtab = sumsq = ctx = None
+    ranges, counted, nparts = (), (), 0
 
     def __init__(self, opt, f, group, clip=None, sharded=False):
         self.opt, self.f, self.group = opt, f, group
         self.st = st = opt._ls()
         self.native = native = _ext.use_native(f.master)
         dev = f.master.device
-        thr, lars = opt._clip_threshold(), opt._lars_conf()
+        thr, lars, lamb = opt._clip_threshold(), opt._lars_conf(), opt._lamb_conf()
         if clip is not None or thr is not None or lars is not None:
             self._norm_state(clip, thr, lars, dev, sharded)
+        if lamb is not None:
+            self.M = opt._lamb_state(lamb, f)
+            self.local2 = self.M.local if sharded else None
         if native:
             hp = st.get("hp")
             self.hp = hp if hp is not None and hp.device == dev else opt._state("hp", dev)
@@ -332,6 +429,47 @@ class _FlatStep:
                 sums = local[:2 * L.S].view(L.S, 2).t() if reduced else L.sums_torch(f, self.ranges)
                 L.finalize_torch(sums, gs * (cl[_CLIP_COEF].double() if cl is not None else 1.0), wd)
 
+    def moments(self, ranges, counted):
+        """LAMB: the moment update over ``ranges`` and the per-segment sums of squares of master
+        and direction over ``counted`` (a subset of ``ranges``); sharded, the sums go to ``local2``."""
+        M, f = self.M, self.f
+        if M is None or self.skip:
+            return
+        ranges = [(lo, hi) for lo, hi in ranges if hi > lo]
+        counted = [(lo, hi) for lo, hi in counted if hi > lo]
+        if self.native:
+            C = _ext.C()
+            self.mtab = t = M.table(ranges, counted, self.opt._ldnn_capturing)
+            g = self.group
+            C.lamb_moments(f.master, f.grad, self.ctx[0], self.ctx[1], t["chunks"], t["partials"], self.hp, f.grad_scale,
+                           *g["betas"], g["eps"], g["weight_decay"], t["ranges"], [b for b, _ in M.bounds], clip=self.cl)
+            if self.local2 is not None:
+                C.lamb_finalize(t["partials"], t["segtab"], M.ratio, M.w_norm, M.g_norm, sums_out=self.local2)
+            return
+        if M.u is None or M.u.shape != f.master.shape or M.u.device != f.master.device:
+            M.u = torch.zeros_like(f.master)
+        coef = self.cl[_CLIP_COEF] if self.cl is not None else 1.0
+        for lo, hi in ranges:
+            M.u[lo:hi] = self.opt._moments_torch(self, f.master[lo:hi], f.grad[lo:hi] * f.grad_scale * coef,
+                                                 self.ctx[0][lo:hi], self.ctx[1][lo:hi])
+        self.counted = counted
+        if self.local2 is not None:
+            self.local2.copy_(M.sums_torch(f, counted).t().reshape(-1))
+
+    def ratios(self, reduced: bool):
+        """LAMB: the trust ratios from the all-reduced ``local2`` or from ``moments``' own sums."""
+        M = self.M
+        if M is None or self.skip:
+            return
+        if self.native:
+            t = self.mtab
+            if reduced:
+                _ext.C().lamb_finalize(None, t["segtab"], M.ratio, M.w_norm, M.g_norm, ext=self.local2, clip=self.cl)
+            else:
+                _ext.C().lamb_finalize(t["partials"], t["segtab"], M.ratio, M.w_norm, M.g_norm, clip=self.cl)
+            return
+        M.finalize_torch(self.local2.view(M.S, 2).t() if reduced else M.sums_torch(self.f, self.counted))
+
     def update(self, lo: int, hi: int, zero=()):
         """Update flat elements [lo, hi): one fused launch (which also zeroes the flat gradient
         ranges ``zero``), or the same math in torch ops."""
@@ -340,8 +478,9 @@ class _FlatStep:
         f, L = self.f, self.L
         sl = None if lo == 0 and hi == f.numel else slice(lo, hi)    # (None: the whole buffer, no views to build)
         if self.native:
-            if L is not None and (lo % 64 or hi % 64):
-                raise ValueError(f"LARS: the update range [{lo}, {hi}) is not 64-element aligned")
+            if (L is not None or self.M is not None) and (lo % 64 or hi % 64):
+                raise ValueError(f"{'LARS' if L is not None else 'LAMB'}: the update range [{lo}, {hi}) is not "
+                                 "64-element aligned")
             self.opt._update_native(self, sl, zero if lo == 0 else [(a - lo, b - lo) for a, b in zero])
             return
         if not self.skip:
@@ -349,6 +488,7 @@ class _FlatStep:
             g = g * f.grad_scale
             if self.cl is not None:
                 g = g * self.cl[_CLIP_COEF]
+            L = L if L is not None else self.M
             self.opt._update_torch(self, sl, p, g, L.elem_ratio(lo, hi) if L is not None else None)
             if shadow is not None:
                 shadow.copy_(p)
@@ -538,6 +678,39 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return {"ratio": L.ratio[:L.S], "w_norm": L.w_norm, "g_norm": L.g_norm, "names": list(L.names),
                 "adapted": list(L.adapt)}
 
+    # ---- LAMB: per-tensor trust ratios (Lamb) -------------------------------------------
+    def _lamb_conf(self):
+        """``exclude_1d``, or None on every optimizer but Lamb."""
+        if "lamb_exclude_1d" not in self.defaults:
+            return None
+        return self._same_in_groups(lambda g: bool(g.get("lamb_exclude_1d", True)),
+                                    "lamb_exclude_1d must be the same in every param group")
+
+    def _lamb_state(self, excl, flat, params=None, device=None):
+        """The LAMB device state over ``flat`` (None: over the loose ``params``)."""
+        st = self._ls()
+        device = flat.master.device if flat is not None else device
+        M = st.get("lamb")
+        if M is None or M.flat is not flat or M.device != device or M.exclude_1d != excl or \
+                (flat is None and M.S != len(params)):
+            M = _graph_state(st, "lamb", self._ldnn_capturing, lambda: _Lamb(flat, params, excl, device))
+        return M
+
+    def lamb_stats(self):
+        """In segment (flat-buffer) order: the device tensors ``ratio`` / ``w_norm`` / ``u_norm`` of
+        the last LAMB step, the parameter ``names`` and which tensors are ``adapted`` (reading a
+        tensor syncs); None on the other optimizers."""
+        excl = self._lamb_conf()
+        if excl is None:
+            return None
+        M = self._ls().get("lamb")
+        if M is None:
+            f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
+            ps = [p for g in self.param_groups for p in g["params"]]
+            M = self._lamb_state(excl, f, ps, ps[0].device if ps else torch.device("cpu"))
+        return {"ratio": M.ratio[:M.S], "w_norm": M.w_norm, "u_norm": M.g_norm, "names": list(M.names),
+                "adapted": list(M.adapt)}
+
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         flat_state = state_dict.pop("ldnn_flat_state", {})
@@ -607,6 +780,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
             if s.normed:
                 s.norm(((0, n),))
             s.finalize(False)
+            if s.M is not None:
+                s.moments(((0, n),), ((0, n),))
+                s.ratios(False)
             s.update(0, n, ((0, n),) if clear_grads else ())
             s.end()
             return
@@ -617,6 +793,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 s.norm(sh.norm_ranges())
                 sh.comm.all_reduce(s.local)
             s.finalize(reduced=s.local is not None)
+            if s.M is not None:
+                s.moments(sh.update_ranges(), sh.norm_ranges())
+                sh.comm.all_reduce(s.local2)
+                s.ratios(reduced=True)
             for lo, hi in sh.update_ranges():
                 s.update(lo, hi)
             s.end()
@@ -639,8 +819,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def supports_ranges(self) -> bool:
         if self._clip_threshold() is not None:
             return False   # the whole norm must be known before any range updates
-        if self._lars_conf() is not None:
-            return False   # ... and so must a tensor's whole gradient before any of it moves
+        if self._lars_conf() is not None or self._lamb_conf() is not None:
+            return False   # ... and so must a tensor's whole gradient (LAMB: direction) before any of it moves
         if len(self.param_groups) != 1 or type(self)._update_native is _FlatOptimizer._update_native:
             return False
         f = self._flat_for_group(self.param_groups[0])
@@ -822,17 +1002,98 @@ class AdamW(Adam):
         super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm)
 
 
+class Lamb(_FlatOptimizer):
+    """LAMB (You et al. 2020): Adam's direction with a per-tensor trust ratio,
+
+        m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay * w
+        w -= lr * r_i * u,   r_i = |w_i| / |u_i|  (1 when either norm is 0)
+
+    ``g`` is the reduced, scaled and -- with ``max_grad_norm`` -- clipped gradient; the norms are
+    taken before the weight write.  With ``lamb_exclude_1d`` (default) tensors with ``dim() < 2``
+    keep ratio 1 (weight decay still applies to them).  No coefficient and no clamp on the ratio.
+    On the flat GPU path ``lamb_moments`` updates the moments and reduces |w|, |u| per tensor,
+    ``lamb_finalize`` leaves the ratios on the device and ``lamb_apply`` recomputes u from the
+    moments and writes the weights and the bf16 shadow; sharded, the [2S] sums travel in one
+    all-reduce after the moments (behind clipping's scalar all-reduce, if any).  Edge behaviour is
+    LARS's: a per-tensor sum of squares beyond fp32 gives ratio 0, NaN norms give ratio 1 and the
+    NaN propagates, and there is no non-finite guard without ``max_grad_norm``.  State keys are
+    Adam's (``exp_avg``, ``exp_avg_sq``, ``step``); ``lamb_stats()`` reports the last ratios."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_grad_norm=None,
+                 lamb_exclude_1d=True):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d))
+
+    _begin_ranges = Adam._begin_ranges
+
+    def _update_native(self, s, sl, zero):
+        f, g, M = s.f, s.group, s.M
+        p, grad, m, v, shadow = _cut(sl, f.master, f.grad, s.ctx[0], s.ctx[1], f.shadow)
+        _ext.C().lamb_apply(p, grad, m, v, shadow, s.hp, *g["betas"], g["eps"], g["weight_decay"], M.ratio,
+                            M.segmap if sl is None else M.segmap[sl.start // 64: sl.stop // 64], zero_ranges=zero,
+                            clip=s.cl)
+
+    @staticmethod
+    def _direction(p, m, v, t, b1, b2, eps, wd):
+        return (m / (1 - b1 ** t)) / ((v / (1 - b2 ** t)).sqrt() + eps) + wd * p
+
+    def _moments_torch(self, s, p, g_, m, v):
+        """The moment update of one flat range in torch ops; returns u."""
+        g = s.group
+        b1, b2 = g["betas"]
+        m.mul_(b1).add_(g_, alpha=1 - b1)
+        v.mul_(b2).addcmul_(g_, g_, value=1 - b2)
+        return self._direction(p, m, v, s.ctx[2], b1, b2, g["eps"], g["weight_decay"])
+
+    def _update_torch(self, s, sl, p, g_, ratio):
+        p.sub_(s.group["lr"] * ratio * _cut(sl, s.M.u)[0])
+
+    def _loose_update(self, group, cl, loose):
+        lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        if not loose:
+            ps_all = [p for g_ in self.param_groups for p in g_["params"]]
+            loose.update(k=0, M=self._lamb_state(self._lamb_conf(), None, ps_all, ps_all[0].device))
+        M = loose["M"]
+        for p in group["params"]:
+            k = loose["k"]
+            loose["k"] += 1
+            if p.grad is None:
+                continue
+            if cl is not None:
+                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+            ps = self.state.setdefault(p, {})
+            if "exp_avg" not in ps:
+                ps["exp_avg"] = torch.zeros_like(p)
+                ps["exp_avg_sq"] = torch.zeros_like(p)
+                ps["step"] = 0
+            ps["step"] += 1
+            m, v = ps["exp_avg"], ps["exp_avg_sq"]
+            m.mul_(b1).add_(p.grad, alpha=1 - b1)
+            v.mul_(b2).addcmul_(p.grad, p.grad, value=1 - b2)
+            u = self._direction(p.data, m, v, ps["step"], b1, b2, eps, wd)
+            wn, un = float(p.detach().double().norm()), float(u.double().norm())
+            ratio = wn / un if (M.adapt[k] and wn > 0 and un > 0) else 1.0
+            M.ratio[k], M.w_norm[k], M.g_norm[k] = ratio, wn, un
+            p.data.add_(u, alpha=-lr * ratio)
+
+
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     max_grad_norm: float | None = None, **lars):
     """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  "lars": SGD with
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
-    "sgd" takes them too); Adam and AdamW refuse them."""
+    "sgd" takes them too); Adam and AdamW refuse them.  "lamb": Lamb, which takes
+    ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords."""
     name = name.lower()
     if max_grad_norm is not None and max_grad_norm <= 0:
         max_grad_norm = None
-    bad = set(lars) - {"lars_trust", "lars_eps", "lars_exclude_1d"}
-    if bad or (lars and name in ("adam", "adamw")):
-        raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad or lars)}")
+    allowed = {"lamb_exclude_1d"} if name == "lamb" else \
+        set() if name in ("adam", "adamw") else {"lars_trust", "lars_eps", "lars_exclude_1d"}
+    bad = set(lars) - allowed
+    if bad:
+        raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
+    if name == "lamb":
+        return Lamb(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
     if name == "lars":
         lars.setdefault("lars_trust", 0.001)
         return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)

@@ -376,7 +376,7 @@ class GraphedDPStep:
         collective right before its update: the deep buckets update while the last
         bucket's reduce-scatter is still in flight.  (self.g_opts: [(graph, bucket or None)])"""
         self.g_opts = []
-        self._clip_local = None
+        self._reduce = {}     # a labelled graph's device vector: all-reduced before that graph replays
         order = self.bk.opt_order() if (self.bk.shard and isinstance(self.optimizer, _FlatOptimizer)) else None
 
         def begin(i):
@@ -393,7 +393,7 @@ class GraphedDPStep:
             return
 
         def driver(step):
-            if step.local is None:
+            if step.local is None and step.M is None:
                 step.finalize(reduced=False)   # (the per-step prologue, e.g. Adam's step count, lands in the first)
                 for k, i in enumerate(order):
                     if k > 0:
@@ -409,20 +409,30 @@ class GraphedDPStep:
                 # bucket's widen + this rank's sums of squares), the host-issued all-reduce of the
                 # local sum (LARS: the vector of per-segment sums, clipping's scalar behind it), and
                 # an UPDATE graph (finalize the coefficient / ratios, step count, every range update)
+                # LAMB's ratios need the norm of a direction made from this step's moments, which
+                # need the clip coefficient: its [2S] sums travel in a collective of their own after
+                # the moments, and the graph behind it ("lamb") holds the ratios and every range update
                 begin(None)
                 for i in order:
                     self.bk.post_collective(i)
-                step.norm(self.bk.norm_ranges())
-                self.g_opts[-1][0].capture_end()
-                self._clip_local = step.local
-                begin("clip")
-                step.finalize(reduced=True)
+                if step.local is not None:
+                    step.norm(self.bk.norm_ranges())
+                    self.g_opts[-1][0].capture_end()
+                    self._reduce["clip"] = step.local
+                    begin("clip")
+                step.finalize(reduced=step.local is not None)
+                if step.M is not None:
+                    step.moments(self.bk.update_ranges(), self.bk.norm_ranges())
+                    self.g_opts[-1][0].capture_end()
+                    self._reduce["lamb"] = step.local2
+                    begin("lamb")
+                    step.ratios(reduced=True)
                 for lo, hi in self.bk.update_ranges():
                     step.update(lo, hi)
             step.end()
 
         opt = self.optimizer
-        if opt._clip_threshold() is None and opt._lars_conf() is None:
+        if opt._clip_threshold() is None and opt._lars_conf() is None and opt._lamb_conf() is None:
             begin(None)   # (before step(): what it launches ahead of the driver lands in the first graph too)
         self.bk.step_driver = driver
         try:
@@ -515,13 +525,14 @@ class GraphedDPStep:
         # each gather right after its own update -- measured neutral, 0.34-0.35 vs 0.36 ms
         # exposed, and was removed in round 6.)
         for g, i in self.g_opts:
-            if i == "clip":
-                # the norm graph left this rank's sum of squares in a device scalar: one
+            if i in self._reduce:
+                # the graph before left this rank's sums (clipping's sum of squares / LARS's
+                # per-segment sums under "clip", LAMB's under "lamb") in a device vector: one
                 # all-reduce (stream-ordered with RCCL; a host-staged backend reads it after
-                # a synchronize, like its other collectives), then the update graph
+                # a synchronize, like its other collectives), then the graph that uses it
                 if host_staged:
                     torch.cuda.current_stream().synchronize()
-                self.comm.all_reduce(self._clip_local)
+                self.comm.all_reduce(self._reduce[i])
                 g.replay()
                 continue
             for k in (list(works) if i is None else [i]):

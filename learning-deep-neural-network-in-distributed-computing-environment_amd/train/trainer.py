@@ -444,6 +444,13 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                 if r.numel():
                     clip_rec.update(lars_ratio_min=float(r.min()), lars_ratio_median=float(r.median()),
                                     lars_ratio_max=float(r.max()))
+            # LAMB likewise
+            lamb_stats = getattr(optimizer, "lamb_stats", lambda: None)()
+            if lamb_stats is not None:
+                r = lamb_stats["ratio"].detach().float().cpu()[torch.tensor(lamb_stats["adapted"], dtype=torch.bool)]
+                if r.numel():
+                    clip_rec.update(lamb_ratio_min=float(r.min()), lamb_ratio_median=float(r.median()),
+                                    lamb_ratio_max=float(r.max()))
             logger.log(kind="global_epoch", global_epoch=global_epoch + 1, duration_s=duration,
                        train_loss=H["global_train_losses"][-1], train_acc=H["global_train_accuracies"][-1],
                        val_loss=H["global_val_losses"][-1], val_acc=H["global_val_accuracies"][-1],

@@ -14,7 +14,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ldnn  # noqa: E402
 from ldnn.models import CrossEntropyLoss, build_model, xavier_init  # noqa: E402
-from ldnn.optim import SGD, Adam  # noqa: E402
+from ldnn.optim import SGD, Adam, Lamb  # noqa: E402
 from ldnn.parallel.comm import TorchComm  # noqa: E402
 from ldnn.parallel.ddp import DataParallel  # noqa: E402
 from ldnn.train.trainer import train_local_epoch  # noqa: E402
@@ -43,7 +43,9 @@ def main():
                          "the same parameters as with it off")
     ap.add_argument("--shard", action="store_true",
                     help="DataParallel(shard_optimizer=True): reduce-scatter + sharded optimizer + weight all-gather")
-    ap.add_argument("--optimizer", choices=["sgd", "adam"], default="sgd")
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "lamb"], default="sgd",
+                    help="lamb: Lamb(lr=1e-3, weight_decay=1e-2).  With --shard the sharded run must also give the "
+                         "parameters of the unsharded LAMB run")
     ap.add_argument("--comm-dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--gossip", type=int, default=0,
                     help="1 / 2: per-step ring / double-ring gossip (DataParallel(gossip=...)): the graphed chain "
@@ -82,6 +84,7 @@ def main():
         if a.lars > 0:
             kw.update(lars_trust=a.lars, weight_decay=1e-4)
         opt = (SGD(m.parameters(), lr=0.02, momentum=0.9, **kw) if a.optimizer == "sgd"
+               else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
                else Adam(m.parameters(), lr=1e-3, **kw))
         batches = []
         for x, y in zip(xs, ys):
@@ -104,6 +107,13 @@ def main():
             ad = torch.tensor(ls["adapted"])
             rt = ls["ratio"].cpu()
             print(f"rank {rank}/{world}: lars ratios {[round(v, 5) for v in rt.tolist()]}", flush=True)
+            assert bool(torch.isfinite(rt).all()) and bool((rt[ad] > 0).all()) and bool((rt[~ad] == 1).all()), rt
+            assert bool((rt[ad] != 1).any()), rt
+        if a.optimizer == "lamb":
+            ls = opt.lamb_stats()
+            ad = torch.tensor(ls["adapted"])
+            rt = ls["ratio"].cpu()
+            print(f"rank {rank}/{world}: lamb ratios {[round(v, 5) for v in rt.tolist()]}", flush=True)
             assert bool(torch.isfinite(rt).all()) and bool((rt[ad] > 0).all()) and bool((rt[~ad] == 1).all()), rt
             assert bool((rt[ad] != 1).any()), rt
         torch.cuda.synchronize()
@@ -129,7 +139,7 @@ def main():
             print("GRAPHED_DP_OK", flush=True)
         D.teardown(ctx)
         return
-    if (a.clip > 0 or a.lars > 0) and a.shard:
+    if (a.clip > 0 or a.lars > 0 or a.optimizer == "lamb") and a.shard:
         mu, _ = run(N, r, TorchComm(), shard=False)
         gotu = torch.cat([p.detach().flatten().cpu() for p in mu.parameters()])
         torch.manual_seed(0)
@@ -138,7 +148,7 @@ def main():
         p0 = torch.cat([p.detach().flatten() for p in m0.parameters()])
         du, dr = (got - p0).double(), (gotu - p0).double()
         err = (du - dr).norm().item() / max(dr.norm().item(), 1e-12)
-        print(f"rank {r}: clipped / LARS sharded vs unsharded relative update difference {err:.3e}", flush=True)
+        print(f"rank {r}: clipped / LARS / LAMB sharded vs unsharded relative update difference {err:.3e}", flush=True)
         ok = ok and err < (2e-2 if a.comm_dtype == "fp32" else 5e-2)
     if a.oneshot:
         c1 = TorchComm()
