@@ -555,31 +555,120 @@ void clip_finalize(const at::Tensor& partials, int64_t nparts, const at::Tensor&
         "clip_finalize");
 }
 
-int64_t seg_sumsq(const at::Tensor& master, const at::Tensor& grad, const at::Tensor& chunks,
-                  const at::Tensor& partials, const std::vector<std::pair<int64_t, int64_t>>& ranges,
-                  const std::vector<int64_t>& seg_offsets) {
-  check_dev(master, at::kFloat, "master");
-  check_dev(grad, at::kFloat, "grad");
-  check_dev(chunks, at::kInt, "chunks");
+// ---- argument checks the optimizer entry points share (fn: the entry point's name, for the messages) ----
+using Ranges = std::vector<std::pair<int64_t, int64_t>>;
+struct Named {
+  const at::Tensor& t;
+  const char* name;
+};
+
+// contiguous fp32 GPU buffers as long as the first one, whose length is returned; one_dev: all on
+// its device; align16: all 16-byte aligned
+int64_t f32_bufs(const char* fn, std::initializer_list<Named> ts, bool one_dev, bool align16) {
+  const at::Tensor& first = ts.begin()->t;
+  bool ok = true;
+  for (const Named& x : ts) {
+    check_dev(x.t, at::kFloat, x.name);
+    ok = ok && x.t.is_contiguous() && x.t.numel() == first.numel() && (!one_dev || x.t.device() == first.device()) &&
+         (!align16 || aligned16(x.t.data_ptr()));
+  }
+  if (!ok) {
+    std::string names;
+    for (const Named& x : ts) names += (names.empty() ? "" : " / ") + std::string(x.name);
+    TORCH_CHECK(false, fn, ": ", names, " must be contiguous", one_dev ? ", on one device" : "", " and equally long",
+                align16 ? " and 16-byte aligned" : "");
+  }
+  return first.numel();
+}
+
+// the optional bf16 shadow of the n elements of `param` (nullptr without); strict: also on its device
+// and 8-byte aligned
+uint16_t* shadow_ptr(const char* fn, const c10::optional<at::Tensor>& shadow, const at::Tensor& param, bool strict) {
+  if (!shadow.has_value()) return nullptr;
+  check_dev(*shadow, at::kBFloat16, "shadow");
+  TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == param.numel() &&
+                  (!strict || (shadow->device() == param.device() &&
+                               (reinterpret_cast<uintptr_t>(shadow->data_ptr()) & 7) == 0)),
+              fn, ": bad shadow");
+  return bf16_mut(*shadow);
+}
+
+// hp = [lr, step] on the device of `like`
+const float* hp_ptr(const char* fn, const at::Tensor& hp, const at::Tensor& like) {
+  check_dev(hp, at::kFloat, "hp");
+  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2 && hp.device() == like.device(), fn,
+              ": hp must hold [lr, step] on the parameters' device");
+  return hp.data_ptr<float>();
+}
+
+// a dense int32 [rows][4] table; returns rows
+int64_t int4_table(const char* fn, const at::Tensor& t, const char* name, const char* rows) {
+  check_dev(t, at::kInt, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(1) == 4 && t.is_contiguous() && aligned16(t.data_ptr()), fn, ": ", name,
+              " must be a dense int32 [", rows, "][4] table");
+  return t.size(0);
+}
+
+// a chunk table over the n-element buffer `master` with its partials; returns nchunks.  The table
+// addresses 64-element blocks: the ranges it was cut from, and the segments, must start and end on
+// them (and lie inside the buffers)
+int64_t chunk_args(const char* fn, const at::Tensor& chunks, const at::Tensor& partials, const Ranges& ranges,
+                   const std::vector<int64_t>& seg_offsets, const at::Tensor& master) {
+  const int64_t n = master.numel(), nchunks = int4_table(fn, chunks, "chunks", "nchunks");
   check_dev(partials, at::kFloat, "partials");
-  const int64_t n = master.numel();
-  TORCH_CHECK(master.is_contiguous() && grad.is_contiguous() && grad.numel() == n && aligned16(master.data_ptr()) &&
-                  aligned16(grad.data_ptr()),
-              "seg_sumsq: master / grad must be contiguous, equally long and 16-byte aligned");
-  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4 && chunks.is_contiguous() && aligned16(chunks.data_ptr()),
-              "seg_sumsq: chunks must be a dense int32 [nchunks][4] table");
-  // the table addresses 64-element blocks: the ranges it was cut from, and the segments, must
-  // start and end on them (and lie inside the buffers)
   for (const auto& r : ranges)
-    TORCH_CHECK(r.first % 64 == 0 && r.second % 64 == 0 && 0 <= r.first && r.first <= r.second && r.second <= n,
-                "seg_sumsq: range [", r.first, ", ", r.second, ") must be 64-element aligned and inside [0, ", n, ")");
+    TORCH_CHECK(r.first % 64 == 0 && r.second % 64 == 0 && 0 <= r.first && r.first <= r.second && r.second <= n, fn,
+                ": range [", r.first, ", ", r.second, ") must be 64-element aligned and inside [0, ", n, ")");
   for (const int64_t o : seg_offsets)
-    TORCH_CHECK(o % 64 == 0 && o >= 0 && o <= n, "seg_sumsq: segment offset ", o, " must be a multiple of 64 in [0, ",
-                n, "]");
-  const int64_t nchunks = chunks.size(0);
+    TORCH_CHECK(o % 64 == 0 && o >= 0 && o <= n, fn, ": segment offset ", o, " must be a multiple of 64 in [0, ", n,
+                "]");
   TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * nchunks && partials.device() == master.device() &&
-                  chunks.device() == master.device() && grad.device() == master.device(),
-              "seg_sumsq: partials needs 2 slots per chunk (", 2 * nchunks, "), all tensors on one device");
+                  chunks.device() == master.device(),
+              fn, ": partials needs 2 slots per chunk (", 2 * nchunks, "), all tensors on one device");
+  return nchunks;
+}
+
+// (ratio, map) of `who` (lars / lamb): the trust ratios and, per 64-element block of param, the index of its ratio
+void ratio_map(const char* fn, const char* who, const at::Tensor& ratio, const at::Tensor& map,
+               const at::Tensor& param) {
+  TORCH_CHECK(ratio.scalar_type() == at::kFloat && map.scalar_type() == at::kUInt16 && ratio.is_contiguous() &&
+                  ratio.numel() == 65536 && map.is_contiguous() && map.numel() * 64 >= param.numel() &&
+                  ratio.device() == param.device() && map.device() == param.device(),
+              fn, ": ", who, " needs a contiguous 65536-entry fp32 ratio table and one uint16 map entry per 64 ",
+              "elements on the parameters' device");
+}
+
+// lars_finalize and, without hdr, lamb_finalize (whose third vector is u_norm)
+void trust_finalize(const char* fn, const c10::optional<at::Tensor>& partials, const at::Tensor& segtab,
+                    const at::Tensor* hdr, const at::Tensor& ratio, const at::Tensor& w_norm, const at::Tensor& g_norm,
+                    double grad_scale, double weight_decay, const c10::optional<at::Tensor>& ext,
+                    const c10::optional<at::Tensor>& clip, const c10::optional<at::Tensor>& sums_out) {
+  const int64_t S = int4_table(fn, segtab, "segtab", "S");
+  auto f32 = [&](const at::Tensor& t, int64_t need, const char* name) -> float* {
+    check_dev(t, at::kFloat, name);
+    TORCH_CHECK(t.is_contiguous() && t.numel() >= need && t.device() == segtab.device(), fn, ": ", name,
+                " must hold ", need, " contiguous floats on the table's device");
+    return t.data_ptr<float>();
+  };
+  const float* hp = hdr != nullptr ? f32(*hdr, 2, "hdr") : nullptr;
+  const float* pp = partials.has_value() ? f32(*partials, 0, "partials") : nullptr;
+  const int64_t nchunks = partials.has_value() ? partials->numel() / 2 : 0;
+  float* so = sums_out.has_value() ? f32(*sums_out, 2 * S, "sums_out") : nullptr;
+  float* rp = f32(ratio, so ? 0 : S, "ratio");
+  float* wp = f32(w_norm, so ? 0 : S, "w_norm");
+  float* gp = f32(g_norm, so ? 0 : S, hdr != nullptr ? "g_norm" : "u_norm");
+  const float* ep = ext.has_value() ? f32(*ext, 2 * S, "ext") : nullptr;
+  const float* cp = clip_ptr(clip, segtab);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(segtab.device());
+  check(ldnn::trust_finalize(hdr == nullptr, pp, (int)nchunks, segtab.data_ptr<int32_t>(), (int)S, ep, hp, cp,
+                             (float)grad_scale, (float)weight_decay, rp, wp, gp, so, cur_stream(segtab)),
+        fn);
+}
+
+int64_t seg_sumsq(const at::Tensor& master, const at::Tensor& grad, const at::Tensor& chunks,
+                  const at::Tensor& partials, const Ranges& ranges, const std::vector<int64_t>& seg_offsets) {
+  const int64_t n = f32_bufs("seg_sumsq", {{master, "master"}, {grad, "grad"}}, true, true);
+  const int64_t nchunks = chunk_args("seg_sumsq", chunks, partials, ranges, seg_offsets, master);
   c10::hip::HIPGuardMasqueradingAsCUDA g(master.device());
   check(ldnn::seg_sumsq(master.data_ptr<float>(), grad.data_ptr<float>(), n, chunks.data_ptr<int32_t>(), (int)nchunks,
                         partials.data_ptr<float>(), cur_stream(master)),
@@ -591,75 +680,25 @@ void lars_finalize(const c10::optional<at::Tensor>& partials, const at::Tensor& 
                    const at::Tensor& ratio, const at::Tensor& w_norm, const at::Tensor& g_norm, double grad_scale,
                    double weight_decay, const c10::optional<at::Tensor>& ext, const c10::optional<at::Tensor>& clip,
                    const c10::optional<at::Tensor>& sums_out) {
-  check_dev(segtab, at::kInt, "segtab");
-  check_dev(hdr, at::kFloat, "hdr");
-  TORCH_CHECK(segtab.dim() == 2 && segtab.size(1) == 4 && segtab.is_contiguous() && aligned16(segtab.data_ptr()),
-              "lars_finalize: segtab must be a dense int32 [S][4] table");
-  const int64_t S = segtab.size(0);
-  auto f32 = [&](const at::Tensor& t, int64_t need, const char* name) -> float* {
-    check_dev(t, at::kFloat, name);
-    TORCH_CHECK(t.is_contiguous() && t.numel() >= need && t.device() == segtab.device(), "lars_finalize: ", name,
-                " must hold ", need, " contiguous floats on the table's device");
-    return t.data_ptr<float>();
-  };
-  f32(hdr, 2, "hdr");
-  const float* pp = nullptr;
-  int64_t nchunks = 0;
-  if (partials.has_value()) {
-    pp = f32(*partials, 0, "partials");
-    nchunks = partials->numel() / 2;
-  }
-  float* so = sums_out.has_value() ? f32(*sums_out, 2 * S, "sums_out") : nullptr;
-  float* rp = f32(ratio, so ? 0 : S, "ratio");
-  float* wp = f32(w_norm, so ? 0 : S, "w_norm");
-  float* gp = f32(g_norm, so ? 0 : S, "g_norm");
-  const float* ep = ext.has_value() ? f32(*ext, 2 * S, "ext") : nullptr;
-  c10::hip::HIPGuardMasqueradingAsCUDA g(segtab.device());
-  check(ldnn::lars_finalize(pp, (int)nchunks, segtab.data_ptr<int32_t>(), (int)S, ep, hdr.data_ptr<float>(),
-                            clip_ptr(clip, segtab), (float)grad_scale, (float)weight_decay, rp, wp, gp, so,
-                            cur_stream(segtab)),
-        "lars_finalize");
+  trust_finalize("lars_finalize", partials, segtab, &hdr, ratio, w_norm, g_norm, grad_scale, weight_decay, ext, clip,
+                 sums_out);
 }
 
 // LAMB.  Everything is checked here, before any launch: a refused call leaves every buffer as it was.
 int64_t lamb_moments(const at::Tensor& master, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
                      const at::Tensor& chunks, const at::Tensor& partials, const at::Tensor& hp, double grad_scale,
-                     double beta1, double beta2, double eps, double weight_decay,
-                     const std::vector<std::pair<int64_t, int64_t>>& ranges, const std::vector<int64_t>& seg_offsets,
-                     const c10::optional<at::Tensor>& clip, int64_t policy) {
-  check_dev(master, at::kFloat, "master");
-  check_dev(grad, at::kFloat, "grad");
-  check_dev(m, at::kFloat, "exp_avg");
-  check_dev(v, at::kFloat, "exp_avg_sq");
-  check_dev(chunks, at::kInt, "chunks");
-  check_dev(partials, at::kFloat, "partials");
-  check_dev(hp, at::kFloat, "hp");
-  const int64_t n = master.numel();
-  TORCH_CHECK(master.is_contiguous() && grad.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
-                  grad.numel() == n && m.numel() == n && v.numel() == n && aligned16(master.data_ptr()) &&
-                  aligned16(grad.data_ptr()) && aligned16(m.data_ptr()) && aligned16(v.data_ptr()),
-              "lamb_moments: master / grad / exp_avg / exp_avg_sq must be contiguous, equally long and 16-byte aligned");
-  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4 && chunks.is_contiguous() && aligned16(chunks.data_ptr()),
-              "lamb_moments: chunks must be a dense int32 [nchunks][4] table");
-  for (const auto& r : ranges)
-    TORCH_CHECK(r.first % 64 == 0 && r.second % 64 == 0 && 0 <= r.first && r.first <= r.second && r.second <= n,
-                "lamb_moments: range [", r.first, ", ", r.second, ") must be 64-element aligned and inside [0, ", n,
-                ")");
-  for (const int64_t o : seg_offsets)
-    TORCH_CHECK(o % 64 == 0 && o >= 0 && o <= n, "lamb_moments: segment offset ", o,
-                " must be a multiple of 64 in [0, ", n, "]");
-  const int64_t nchunks = chunks.size(0);
-  TORCH_CHECK(partials.is_contiguous() && partials.numel() >= 2 * nchunks, "lamb_moments: partials needs 2 slots per chunk (",
-              2 * nchunks, ")");
-  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2, "lamb_moments: hp must hold [lr, step]");
+                     double beta1, double beta2, double eps, double weight_decay, const Ranges& ranges,
+                     const std::vector<int64_t>& seg_offsets, const c10::optional<at::Tensor>& clip, int64_t policy) {
+  const int64_t n = f32_bufs("lamb_moments", {{master, "master"}, {grad, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}},
+                             true, true);
+  const int64_t nchunks = chunk_args("lamb_moments", chunks, partials, ranges, seg_offsets, master);
+  const float* hpp = hp_ptr("lamb_moments", hp, master);
   TORCH_CHECK(policy >= 0 && policy <= 2, "lamb_moments: access policy must be 0, 1 or 2");
-  for (const at::Tensor* t : {&grad, &m, &v, &chunks, &partials, &hp})
-    TORCH_CHECK(t->device() == master.device(), "lamb_moments: all tensors must be on one device");
   const float* cp = clip_ptr(clip, master);
   ldnn::LambParams lp{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, ldnn::GradZero{}};
   c10::hip::HIPGuardMasqueradingAsCUDA g(master.device());
   check(ldnn::lamb_moments(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                           n, chunks.data_ptr<int32_t>(), (int)nchunks, hp.data_ptr<float>(), (float)grad_scale, lp,
+                           n, chunks.data_ptr<int32_t>(), (int)nchunks, hpp, (float)grad_scale, lp,
                            partials.data_ptr<float>(), cur_stream(master), cp, (int)policy),
         "lamb_moments");
   return nchunks;
@@ -668,97 +707,40 @@ int64_t lamb_moments(const at::Tensor& master, const at::Tensor& grad, const at:
 void lamb_finalize(const c10::optional<at::Tensor>& partials, const at::Tensor& segtab, const at::Tensor& ratio,
                    const at::Tensor& w_norm, const at::Tensor& u_norm, const c10::optional<at::Tensor>& ext,
                    const c10::optional<at::Tensor>& clip, const c10::optional<at::Tensor>& sums_out) {
-  check_dev(segtab, at::kInt, "segtab");
-  TORCH_CHECK(segtab.dim() == 2 && segtab.size(1) == 4 && segtab.is_contiguous() && aligned16(segtab.data_ptr()),
-              "lamb_finalize: segtab must be a dense int32 [S][4] table");
-  const int64_t S = segtab.size(0);
-  auto f32 = [&](const at::Tensor& t, int64_t need, const char* name) -> float* {
-    check_dev(t, at::kFloat, name);
-    TORCH_CHECK(t.is_contiguous() && t.numel() >= need && t.device() == segtab.device(), "lamb_finalize: ", name,
-                " must hold ", need, " contiguous floats on the table's device");
-    return t.data_ptr<float>();
-  };
-  const float* pp = nullptr;
-  int64_t nchunks = 0;
-  if (partials.has_value()) {
-    pp = f32(*partials, 0, "partials");
-    nchunks = partials->numel() / 2;
-  }
-  float* so = sums_out.has_value() ? f32(*sums_out, 2 * S, "sums_out") : nullptr;
-  float* rp = f32(ratio, so ? 0 : S, "ratio");
-  float* wp = f32(w_norm, so ? 0 : S, "w_norm");
-  float* up = f32(u_norm, so ? 0 : S, "u_norm");
-  const float* ep = ext.has_value() ? f32(*ext, 2 * S, "ext") : nullptr;
-  const float* cp = clip_ptr(clip, segtab);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(segtab.device());
-  check(ldnn::lamb_finalize(pp, (int)nchunks, segtab.data_ptr<int32_t>(), (int)S, ep, cp, rp, wp, up, so,
-                            cur_stream(segtab)),
-        "lamb_finalize");
+  trust_finalize("lamb_finalize", partials, segtab, nullptr, ratio, w_norm, u_norm, 1.0, 0.0, ext, clip, sums_out);
 }
 
 void lamb_apply(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
                 const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double beta1, double beta2, double eps,
-                double weight_decay, const at::Tensor& ratio, const at::Tensor& map,
-                const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, const c10::optional<at::Tensor>& clip) {
-  check_dev(param, at::kFloat, "param");
-  check_dev(grad, at::kFloat, "grad");
-  check_dev(m, at::kFloat, "exp_avg");
-  check_dev(v, at::kFloat, "exp_avg_sq");
-  check_dev(hp, at::kFloat, "hp");
-  check_dev(ratio, at::kFloat, "lamb ratio");
-  check_dev(map, at::kUInt16, "lamb map");
-  const int64_t n = param.numel();
-  TORCH_CHECK(param.is_contiguous() && grad.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
-                  grad.numel() == n && m.numel() == n && v.numel() == n,
-              "lamb_apply: param / grad / exp_avg / exp_avg_sq must be contiguous and equally long");
-  TORCH_CHECK(n % 64 == 0 && aligned16(param.data_ptr()) && aligned16(grad.data_ptr()) && aligned16(m.data_ptr()) &&
-                  aligned16(v.data_ptr()),
-              "lamb_apply: the range must be 64-element aligned (", n, " elements) and 16-byte aligned");
-  TORCH_CHECK(ratio.is_contiguous() && ratio.numel() == 65536 && map.is_contiguous() && map.numel() * 64 >= n,
-              "lamb_apply: needs a contiguous 65536-entry ratio table and one uint16 map entry per 64 elements");
-  TORCH_CHECK(hp.is_contiguous() && hp.numel() >= 2, "lamb_apply: hp must hold [lr, step]");
-  for (const at::Tensor* t : {&grad, &m, &v, &hp, &ratio, &map})
-    TORCH_CHECK(t->device() == param.device(), "lamb_apply: all tensors must be on one device");
-  uint16_t* sh = nullptr;
-  if (shadow.has_value()) {
-    check_dev(*shadow, at::kBFloat16, "shadow");
-    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == n && shadow->device() == param.device() &&
-                    (reinterpret_cast<uintptr_t>(shadow->data_ptr()) & 7) == 0,
-                "lamb_apply: bad shadow");
-    sh = bf16_mut(*shadow);
-  }
+                double weight_decay, const at::Tensor& ratio, const at::Tensor& map, const Ranges& zero_ranges,
+                const c10::optional<at::Tensor>& clip) {
+  const int64_t n = f32_bufs("lamb_apply", {{param, "param"}, {grad, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}},
+                             true, true);
+  TORCH_CHECK(n % 64 == 0, "lamb_apply: the range must be 64-element aligned (", n, " elements)");
+  ratio_map("lamb_apply", "lamb", ratio, map, param);
+  const float* hpp = hp_ptr("lamb_apply", hp, param);
+  uint16_t* sh = shadow_ptr("lamb_apply", shadow, param, true);
   const float* cp = clip_ptr(clip, param);
   ldnn::LambParams lp{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, grad_zero(zero_ranges, n)};
   c10::hip::HIPGuardMasqueradingAsCUDA g(param.device());
   check(ldnn::lamb_apply(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sh,
-                         hp.data_ptr<float>(), lp, n, ratio.data_ptr<float>(), map.data_ptr<uint16_t>(),
-                         cur_stream(param), cp),
+                         hpp, lp, n, ratio.data_ptr<float>(), map.data_ptr<uint16_t>(), cur_stream(param), cp),
         "lamb_apply");
 }
 
 void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& mom,
               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double momentum,
-              double dampening, double weight_decay, bool nesterov, bool first_step,
-              const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, int64_t t_begin,
-              const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip,
+              double dampening, double weight_decay, bool nesterov, bool first_step, const Ranges& zero_ranges,
+              int64_t t_begin, const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip,
               const c10::optional<std::pair<at::Tensor, at::Tensor>>& lars) {
-  check_dev(param, at::kFloat, "param");
-  check_dev(grad, at::kFloat, "grad");
   check_dev(hp, at::kFloat, "hp");
-  const int64_t n = param.numel();
-  TORCH_CHECK(param.is_contiguous() && grad.is_contiguous() && grad.numel() == n, "sgd: bad param/grad");
+  const int64_t n = f32_bufs("sgd", {{param, "param"}, {grad, "grad"}}, false, false);
   float* mp = nullptr;
   if (momentum != 0.0) {
-    check_dev(mom, at::kFloat, "mom");
-    TORCH_CHECK(mom.is_contiguous() && mom.numel() == n, "sgd: bad momentum buffer");
+    f32_bufs("sgd", {{param, "param"}, {mom, "mom"}}, false, false);
     mp = mom.data_ptr<float>();
   }
-  uint16_t* sh = nullptr;
-  if (shadow.has_value()) {
-    check_dev(*shadow, at::kBFloat16, "shadow");
-    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == n, "sgd: bad shadow");
-    sh = bf16_mut(*shadow);
-  }
+  uint16_t* sh = shadow_ptr("sgd", shadow, param, false);
   ldnn::SgdParams sp{(float)momentum, (float)dampening, (float)weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0,
                      grad_zero(zero_ranges, n)};
   ldnn::ShadowT tr{};
@@ -774,47 +756,27 @@ void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor&
     tr.cols = (int)t_out->size(0);
     tr.out = bf16_mut(*t_out);
   }
-  const float* lr_ = nullptr;
-  const uint16_t* lm_ = nullptr;
   if (lars.has_value()) {
-    // (ratio, map): the trust ratios and, per 64-element block of param, the index of its ratio
-    const at::Tensor& ratio = lars->first;
-    const at::Tensor& map = lars->second;
-    check_dev(ratio, at::kFloat, "lars ratio");
-    check_dev(map, at::kUInt16, "lars map");
-    TORCH_CHECK(!t_out.has_value(), "sgd: lars= and t_out= do not go together (the transposed-shadow form has no LARS)");
-    TORCH_CHECK(ratio.is_contiguous() && ratio.numel() == 65536 && map.is_contiguous() &&
-                    map.numel() * 64 >= n && ratio.device() == param.device() && map.device() == param.device(),
-                "sgd: lars needs a contiguous 65536-entry ratio table and one uint16 map entry per 64 elements");
+    TORCH_CHECK(!t_out.has_value(),
+                "sgd: lars= and t_out= do not go together (the transposed-shadow form has no LARS)");
+    ratio_map("sgd", "lars", lars->first, lars->second, param);
     TORCH_CHECK(aligned16(param.data_ptr()) && aligned16(grad.data_ptr()), "sgd: lars needs 16-byte aligned ranges");
-    lr_ = ratio.data_ptr<float>();
-    lm_ = map.data_ptr<uint16_t>();
   }
   check(ldnn::sgd_step(param.data_ptr<float>(), grad.data_ptr<float>(), mp, sh, hp.data_ptr<float>(),
                        (float)grad_scale, sp, n, cur_stream(param), t_out.has_value() ? &tr : nullptr,
-                       clip_ptr(clip, param), lr_, lm_),
+                       clip_ptr(clip, param), lars.has_value() ? lars->first.data_ptr<float>() : nullptr,
+                       lars.has_value() ? lars->second.data_ptr<uint16_t>() : nullptr),
         "sgd_step");
 }
 
 void adam_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double beta1,
-               double beta2, double eps, double weight_decay, bool decoupled,
-               const std::vector<std::pair<int64_t, int64_t>>& zero_ranges, const c10::optional<at::Tensor>& clip) {
-  check_dev(param, at::kFloat, "param");
-  check_dev(grad, at::kFloat, "grad");
-  check_dev(m, at::kFloat, "exp_avg");
-  check_dev(v, at::kFloat, "exp_avg_sq");
+               double beta2, double eps, double weight_decay, bool decoupled, const Ranges& zero_ranges,
+               const c10::optional<at::Tensor>& clip) {
   check_dev(hp, at::kFloat, "hp");
-  const int64_t n = param.numel();
-  TORCH_CHECK(param.is_contiguous() && grad.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
-                  grad.numel() == n && m.numel() == n && v.numel() == n,
-              "adam: bad buffers");
-  uint16_t* sh = nullptr;
-  if (shadow.has_value()) {
-    check_dev(*shadow, at::kBFloat16, "shadow");
-    TORCH_CHECK(shadow->is_contiguous() && shadow->numel() == n, "adam: bad shadow");
-    sh = bf16_mut(*shadow);
-  }
+  const int64_t n =
+      f32_bufs("adam", {{param, "param"}, {grad, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}}, false, false);
+  uint16_t* sh = shadow_ptr("adam", shadow, param, false);
   ldnn::AdamParams ap{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, decoupled ? 1 : 0,
                       grad_zero(zero_ranges, n)};
   check(ldnn::adam_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),

@@ -393,7 +393,7 @@ struct ShadowT {
 // clip (optional, device fp32 [kClipState]): the global-norm clipping state clip_finalize wrote.
 // The update multiplies grad_scale by clip[kClipCoef]; with clip[kClipSkip] set it touches no
 // master / state / shadow element and only clears the requested gradient zero ranges.
-// lars_ratio / lars_map (optional, both or neither): the LARS trust ratios lars_finalize wrote and,
+// lars_ratio / lars_map (optional, both or neither): the LARS trust ratios trust_finalize wrote and,
 // per 64-element block of THIS range, the index of its ratio (alignment gaps point at a slot that
 // holds 1).  The update becomes ratio * (g + weight_decay * p); together with `tr` it is refused.
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
@@ -454,9 +454,11 @@ hipError_t seg_sumsq(const float* master, const float* grad, int64_t n, const in
 //   ratio[i] = 1                                                 otherwise
 // (hdr = [trust_coef, eps], written by the host like the lr; a sum of squares that overflowed fp32
 // gives ratio 0), w_norm[i] = wn, g_norm[i] = gn.  With clip[kClipSkip] set nothing is written.
-hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
-                         const float* hdr, const float* clip, float grad_scale, float weight_decay, float* ratio,
-                         float* w_norm, float* g_norm, float* sums_out, hipStream_t s);
+// lamb: the partials are lamb_moments' (w^2, u^2) and ratio[i] = wn / un under the same conditions (no
+// hdr, grad_scale or weight_decay; g_norm receives |u|); the clip state lends its skip flag only.
+hipError_t trust_finalize(bool lamb, const float* partials, int nchunks, const int32_t* segtab, int S,
+                          const float* ext, const float* hdr, const float* clip, float grad_scale, float weight_decay,
+                          float* ratio, float* w_norm, float* g_norm, float* sums_out, hipStream_t s);
 
 // ---- LAMB (You et al. 2020): per-tensor trust ratios |w| / |u| on the Adam direction ----
 //   m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2          (g = grad * grad_scale * clip coef)
@@ -475,11 +477,6 @@ struct LambParams {
 hipError_t lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const int32_t* chunks,
                         int nchunks, const float* hp, float grad_scale, LambParams lp, float* partials,
                         hipStream_t s, const float* clip = nullptr, int policy = 1);
-// lars_finalize's reduction over (w^2, u^2) partials (+ ext): ratio[i] = wn / un if adapted, wn > 0
-// and un > 0, else 1 (a sum beyond fp32: 0); the clip state lends its skip flag only.
-hipError_t lamb_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
-                         const float* clip, float* ratio, float* w_norm, float* u_norm, float* sums_out,
-                         hipStream_t s);
 // The apply pass over [0, n), n a multiple of 64: u from the stored moments, the ratio through the
 // per-64-element map (as sgd_step's lars_map), master + bf16 shadow written, zero ranges cleared.
 // With clip[kClipSkip] set only the zero ranges are cleared.

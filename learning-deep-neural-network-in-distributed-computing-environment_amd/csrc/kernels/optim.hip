@@ -57,10 +57,13 @@ __device__ __forceinline__ void clear4(const GradZero& z, float* grad, int64_t i
 // CLIP = false instances carry an empty argument and compile to the unclipped code.
 template <bool CLIP>
 struct ClipArg {
+  static constexpr bool on = CLIP;
   const float* st;
 };
 template <>
-struct ClipArg<false> {};
+struct ClipArg<false> {
+  static constexpr bool on = false;
+};
 
 // LARS: the kernel also takes the per-tensor trust ratios (lars_finalize) and the map from each
 // 64-element block of this launch's range to its ratio slot.  The LARS = false instances carry
@@ -323,16 +326,17 @@ __global__ void clip_finalize_kernel(const float* __restrict__ partials, int npa
   if (!finite) state[kClipSkipped] += 1.f;
 }
 
-// Per-segment sums of squares of the master AND the gradient.  chunks[c] = (segment, begin / 64,
-// end / 64, -): a run of whole 64-element blocks inside one segment (a few thousand elements; a
-// range that cuts a segment only changes which chunks exist).  ONE workgroup reduces a whole chunk
-// -- 16-byte loads, four independent accumulators per buffer and thread, wave64 shuffle, LDS -- and
-// stores partials[2c] (master) and partials[2c + 1] (gradient) with plain stores: no atomics, and
-// a chunk's partial does not depend on the grid, so equal inputs give equal bits.  Plain loads:
-// the update re-reads both buffers right after.  A chunk outside [0, n) contributes nothing.
-__global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __restrict__ g,
-                                 const int4* __restrict__ chunks, int nchunks, int64_t n,
-                                 float* __restrict__ partials) {
+// The per-chunk reduction of seg_sumsq and lamb_moments.  chunks[c] = (segment, begin / 64, end / 64,
+// counted): a run of whole 64-element blocks inside one segment (a few thousand elements; a range
+// that cuts a segment only changes which chunks exist).  ONE workgroup reduces a whole chunk (the grid
+// strides over the chunks): body(i, a) returns one float4 of float4 index i and hands the other back
+// in a; four independent accumulator pairs per thread, wave64 shuffle, LDS; partials[2c] = sum a^2,
+// partials[2c + 1] = sum of the returned squares, plain stores: no atomics, and a chunk's partial does
+// not depend on the grid, so equal inputs give equal bits.  COUNTED: a chunk whose fourth field is 0
+// stores 0, 0.  A chunk outside [0, n) runs no body.
+template <bool COUNTED, class Body>
+__device__ __forceinline__ void chunk_sumsq(const int4* chunks, int nchunks, int64_t n,
+                                            float* partials, Body body) {
   static_assert(kBlock == 256, "the cross-wave sum below adds exactly four waves");
   __shared__ float red[2][kBlock / 64];
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
@@ -343,10 +347,9 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __res
     floatx4 w0 = z, w1 = z, w2 = z, w3 = z, g0 = z, g1 = z, g2 = z, g3 = z;
     int64_t i = b + threadIdx.x;
     for (; i + 3 * kBlock < e; i += 4 * kBlock) {
-      const floatx4 a0 = ld4<false>(w, i), a1 = ld4<false>(w, i + kBlock), a2 = ld4<false>(w, i + 2 * kBlock),
-                    a3 = ld4<false>(w, i + 3 * kBlock);
-      const floatx4 b0 = ld4<false>(g, i), b1 = ld4<false>(g, i + kBlock), b2 = ld4<false>(g, i + 2 * kBlock),
-                    b3 = ld4<false>(g, i + 3 * kBlock);
+      floatx4 a0, a1, a2, a3;
+      const floatx4 b0 = body(i, a0), b1 = body(i + kBlock, a1), b2 = body(i + 2 * kBlock, a2),
+                    b3 = body(i + 3 * kBlock, a3);
       w0 += a0 * a0;
       w1 += a1 * a1;
       w2 += a2 * a2;
@@ -357,7 +360,8 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __res
       g3 += b3 * b3;
     }
     for (; i < e; i += kBlock) {
-      const floatx4 a = ld4<false>(w, i), bb = ld4<false>(g, i);
+      floatx4 a;
+      const floatx4 bb = body(i, a);
       w0 += a * a;
       g0 += bb * bb;
     }
@@ -370,18 +374,31 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __res
       red[1][threadIdx.x >> 6] = sg;
     }
     __syncthreads();
-    if (threadIdx.x < 2)
-      partials[2 * (int64_t)c + threadIdx.x] =
-          (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    if (threadIdx.x < 2) {
+      const float s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+      partials[2 * (int64_t)c + threadIdx.x] = (!COUNTED || ch.w != 0) ? s : 0.f;
+    }
     __syncthreads();
   }
+}
+
+// Per-segment sums of squares of the master AND the gradient: partials[2c] (master) and
+// partials[2c + 1] (gradient) of every chunk, whatever its fourth field.  Plain loads: the update
+// re-reads both buffers right after.
+__global__ void seg_sumsq_kernel(const float* __restrict__ w, const float* __restrict__ g,
+                                 const int4* __restrict__ chunks, int nchunks, int64_t n,
+                                 float* __restrict__ partials) {
+  chunk_sumsq<false>(chunks, nchunks, n, partials, [&](int64_t i, floatx4& wq) __attribute__((always_inline)) {
+    wq = ld4<false>(w, i);
+    return ld4<false>(g, i);
+  });
 }
 
 // One wave per segment (waves stride over the segments, so any S works).  segtab[s] = (first
 // chunk, end chunk, adapted, -).  Fixed summation order, in double: lane l adds the segment's
 // partials l, l + 64, ... in index order, the 64 lane sums meet in an xor butterfly (every lane
 // ends with the same bits).  ext: [2S] sums added on top (the sharded path's all-reduced vector).
-// sums_out: write the [2S] sums alone; else the ratios (ldnn_kernels.h lars_finalize).
+// sums_out: write the [2S] sums alone; else the ratios (ldnn_kernels.h trust_finalize).
 // LAMB: the same sums (master, Adam direction u) give ratio = wn / un: no header, and the clip state
 // lends its skip flag only (the coefficient went into the moments before u was formed).
 template <bool LAMB>
@@ -470,66 +487,22 @@ __device__ __forceinline__ floatx4 lamb_mom4(const float* __restrict__ w, const 
   return u;
 }
 
-// chunks[c] = (segment, begin / 64, end / 64, counted) as for seg_sumsq_kernel, ONE workgroup per
-// chunk (the grid strides over the chunks): partials[2c] = sum w^2, partials[2c + 1] = sum u^2 over
-// the chunk, plain stores, no atomics, independent of the grid.  An uncounted chunk (another rank
-// counts these elements) updates its moments and stores 0, 0.  A chunk outside [0, n) does nothing.
+// chunk_sumsq over lamb_mom4: partials[2c] = sum w^2, partials[2c + 1] = sum u^2 over the chunk.  An
+// uncounted chunk (another rank counts these elements) updates its moments and stores 0, 0.
 template <bool CLIP, int POL>
 __global__ void lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mm,
                                     float* __restrict__ vv, const int4* __restrict__ chunks, int nchunks, int64_t n,
                                     const float* __restrict__ hp, float grad_scale, LambParams lp,
                                     float* __restrict__ partials, ClipArg<CLIP> clip) {
-  static_assert(kBlock == 256, "the cross-wave sum below adds exactly four waves");
   if constexpr (CLIP) {
     if (clip.st[kClipSkip] != 0.f) return;  // a skipped step: moments and partials stay
     grad_scale *= clip.st[kClipCoef];
   }
   const float t = hp[1];
   const float rbc1 = 1.f / (1.f - powf(lp.beta1, t)), rbc2 = 1.f / (1.f - powf(lp.beta2, t));
-  __shared__ float red[2][kBlock / 64];
-  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const int4 ch = chunks[c];
-    int64_t b = (int64_t)ch.y * 16, e = (int64_t)ch.z * 16;  // in float4s
-    if (ch.y < 0 || ch.z < ch.y || (int64_t)ch.z * 64 > n) b = e = 0;
-    const floatx4 z = {0.f, 0.f, 0.f, 0.f};
-    floatx4 w0 = z, w1 = z, w2 = z, w3 = z, u0 = z, u1 = z, u2 = z, u3 = z;
-    int64_t i = b + threadIdx.x;
-    for (; i + 3 * kBlock < e; i += 4 * kBlock) {
-      floatx4 a0, a1, a2, a3;
-      const floatx4 b0 = lamb_mom4<POL>(w, g, mm, vv, i, grad_scale, rbc1, rbc2, lp, a0);
-      const floatx4 b1 = lamb_mom4<POL>(w, g, mm, vv, i + kBlock, grad_scale, rbc1, rbc2, lp, a1);
-      const floatx4 b2 = lamb_mom4<POL>(w, g, mm, vv, i + 2 * kBlock, grad_scale, rbc1, rbc2, lp, a2);
-      const floatx4 b3 = lamb_mom4<POL>(w, g, mm, vv, i + 3 * kBlock, grad_scale, rbc1, rbc2, lp, a3);
-      w0 += a0 * a0;
-      w1 += a1 * a1;
-      w2 += a2 * a2;
-      w3 += a3 * a3;
-      u0 += b0 * b0;
-      u1 += b1 * b1;
-      u2 += b2 * b2;
-      u3 += b3 * b3;
-    }
-    for (; i < e; i += kBlock) {
-      floatx4 a;
-      const floatx4 bb = lamb_mom4<POL>(w, g, mm, vv, i, grad_scale, rbc1, rbc2, lp, a);
-      w0 += a * a;
-      u0 += bb * bb;
-    }
-    w0 = (w0 + w1) + (w2 + w3);
-    u0 = (u0 + u1) + (u2 + u3);
-    const float sw = wave_sum((w0[0] + w0[1]) + (w0[2] + w0[3]));
-    const float su = wave_sum((u0[0] + u0[1]) + (u0[2] + u0[3]));
-    if ((threadIdx.x & 63) == 0) {
-      red[0][threadIdx.x >> 6] = sw;
-      red[1][threadIdx.x >> 6] = su;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-      const float s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-      partials[2 * (int64_t)c + threadIdx.x] = ch.w != 0 ? s : 0.f;
-    }
-    __syncthreads();
-  }
+  chunk_sumsq<true>(chunks, nchunks, n, partials, [&](int64_t i, floatx4& wq) __attribute__((always_inline)) {
+    return lamb_mom4<POL>(w, g, mm, vv, i, grad_scale, rbc1, rbc2, lp, wq);
+  });
 }
 
 // w -= lr * ratio * u over [0, n) (n a multiple of 64), u recomputed from the moments this step's
@@ -564,33 +537,40 @@ __global__ void lamb_apply_kernel(float* __restrict__ param, float* __restrict__
   }
 }
 
-
 int g_opt_max_blocks = 2048;  // optimizer grid cap (set_opt_max_blocks: a narrow side-stream update)
 
 inline int grid_for(int64_t n4) {
   int64_t g = (n4 + kBlock - 1) / kBlock;
   return (int)(g < 1 ? 1 : (g > g_opt_max_blocks ? g_opt_max_blocks : g));
 }
+// a chunk-table kernel: one workgroup per chunk up to the cap
+inline int chunk_grid(int nchunks) { return nchunks < g_opt_max_blocks ? nchunks : g_opt_max_blocks; }
+// the finalize kernel: one wave per segment, at most 256 workgroups
+inline int finalize_grid(int S) {
+  const int g = (S + kBlock / 64 - 1) / (kBlock / 64);
+  return g > 256 ? 256 : g;
+}
+
+// launch(ClipArg<..>): the CLIP instance when a clipping state is given, else the unclipped one
+template <class Launch>
+void with_clip(const float* clip, Launch launch) {
+  if (clip != nullptr) launch(ClipArg<true>{clip});
+  else launch(ClipArg<false>{});
+}
+
+template <bool TR, bool LARS>
+void launch_sgd(int grid, float* param, float* grad, float* mom, uint16_t* shadow, const float* hp, float grad_scale,
+                const SgdParams& sp, int64_t n, hipStream_t s, const ShadowT& tr, const float* clip,
+                LarsArg<LARS> la) {
+  with_clip(clip, [&](auto ca) {
+    sgd_kernel<true, TR, ca.on, LARS><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, tr, ca,
+                                                              la);
+  });
+}
 
 }  // namespace
 
 void set_opt_max_blocks(int n) { g_opt_max_blocks = n > 0 ? n : 2048; }
-
-namespace {
-template <bool TR, bool CLIP, bool LARS>
-void launch_sgd(int grid, float* param, float* grad, float* mom, uint16_t* shadow, const float* hp, float grad_scale,
-                const SgdParams& sp, int64_t n, hipStream_t s, const ShadowT& tr, const float* clip,
-                const float* ratio, const uint16_t* map) {
-  ClipArg<CLIP> ca;
-  if constexpr (CLIP) ca.st = clip;
-  LarsArg<LARS> la;
-  if constexpr (LARS) {
-    la.ratio = ratio;
-    la.map = map;
-  }
-  sgd_kernel<true, TR, CLIP, LARS><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, tr, ca, la);
-}
-}  // namespace
 
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
                     float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr, const float* clip,
@@ -606,39 +586,26 @@ hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, con
       return hipErrorInvalidValue;
     const int64_t ntiles = (int64_t)(tr->rows / 64) * (tr->cols / 64);
     const int64_t rest = (n - (int64_t)tr->rows * tr->cols + 3) / 4;
-    const int grid = (int)ntiles + grid_for(rest);
-    if (clip != nullptr)
-      launch_sgd<true, true, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, *tr, clip, nullptr, nullptr);
-    else
-      launch_sgd<true, false, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, *tr, nullptr, nullptr,
-                                     nullptr);
+    launch_sgd<true, false>((int)ntiles + grid_for(rest), param, grad, mom, shadow, hp, grad_scale, sp, n, s, *tr, clip,
+                            {});
     return hipGetLastError();
   }
   const int grid = grid_for((n + 3) / 4);
-  const ShadowT none{};
-  auto go = [&](auto launch) {
-    launch(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, none, clip, lars_ratio, lars_map);
-  };
-  if (clip != nullptr) {
-    if (lars) go(launch_sgd<false, true, true>);
-    else go(launch_sgd<false, true, false>);
-  } else {
-    if (lars) go(launch_sgd<false, false, true>);
-    else go(launch_sgd<false, false, false>);
-  }
+  if (lars)
+    launch_sgd<false, true>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, ShadowT{}, clip,
+                            {lars_ratio, lars_map});
+  else
+    launch_sgd<false, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, ShadowT{}, clip, {});
   return hipGetLastError();
 }
 
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
                      float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip) {
   if (n <= 0) return hipSuccess;
-  const int grid = grid_for((n + 3) / 4);
-  if (clip != nullptr)
-    adam_kernel<true, true><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
-                                                    ClipArg<true>{clip});
-  else
-    adam_kernel<true, false><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
-                                                     ClipArg<false>{});
+  with_clip(clip, [&](auto ca) {
+    adam_kernel<true, ca.on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
+                                                                      ca);
+  });
   return hipGetLastError();
 }
 
@@ -672,62 +639,33 @@ int seg_sumsq_chunk() { return kSegChunk; }
 hipError_t seg_sumsq(const float* master, const float* grad, int64_t n, const int32_t* chunks, int nchunks,
                      float* partials, hipStream_t s) {
   if (nchunks <= 0) return hipSuccess;
-  const int grid = nchunks < g_opt_max_blocks ? nchunks : g_opt_max_blocks;
-  seg_sumsq_kernel<<<grid, kBlock, 0, s>>>(master, grad, reinterpret_cast<const int4*>(chunks), nchunks, n, partials);
+  seg_sumsq_kernel<<<chunk_grid(nchunks), kBlock, 0, s>>>(master, grad, reinterpret_cast<const int4*>(chunks), nchunks,
+                                                          n, partials);
   return hipGetLastError();
 }
 
-hipError_t lars_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
-                         const float* hdr, const float* clip, float grad_scale, float weight_decay, float* ratio,
-                         float* w_norm, float* g_norm, float* sums_out, hipStream_t s) {
+hipError_t trust_finalize(bool lamb, const float* partials, int nchunks, const int32_t* segtab, int S,
+                          const float* ext, const float* hdr, const float* clip, float grad_scale, float weight_decay,
+                          float* ratio, float* w_norm, float* g_norm, float* sums_out, hipStream_t s) {
   if (S <= 0) return hipSuccess;
-  const int waves = kBlock / 64;
-  int grid = (S + waves - 1) / waves;
-  if (grid > 256) grid = 256;
-  lars_finalize_kernel<false><<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext, hdr,
-                                               clip, grad_scale, weight_decay, ratio, w_norm, g_norm, sums_out);
+  const auto kernel = lamb ? lars_finalize_kernel<true> : lars_finalize_kernel<false>;
+  kernel<<<finalize_grid(S), kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext, hdr,
+                                             clip, grad_scale, weight_decay, ratio, w_norm, g_norm, sums_out);
   return hipGetLastError();
 }
-
-namespace {
-template <bool LAMB_CLIP>
-void launch_lamb_moments(int grid, int policy, const float* w, const float* g, float* m, float* v, const int4* chunks,
-                         int nchunks, int64_t n, const float* hp, float gs, const LambParams& lp, float* partials,
-                         ClipArg<LAMB_CLIP> ca, hipStream_t s) {
-  if (policy == 1)
-    lamb_moments_kernel<LAMB_CLIP, 1><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
-  else if (policy == 2)
-    lamb_moments_kernel<LAMB_CLIP, 2><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
-  else
-    lamb_moments_kernel<LAMB_CLIP, 0><<<grid, kBlock, 0, s>>>(w, g, m, v, chunks, nchunks, n, hp, gs, lp, partials, ca);
-}
-}  // namespace
 
 hipError_t lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const int32_t* chunks,
                         int nchunks, const float* hp, float grad_scale, LambParams lp, float* partials,
                         hipStream_t s, const float* clip, int policy) {
   if (nchunks <= 0) return hipSuccess;
   if (policy < 0 || policy > 2) return hipErrorInvalidValue;
-  const int grid = nchunks < g_opt_max_blocks ? nchunks : g_opt_max_blocks;
-  const int4* ct = reinterpret_cast<const int4*>(chunks);
-  if (clip != nullptr)
-    launch_lamb_moments<true>(grid, policy, master, grad, m, v, ct, nchunks, n, hp, grad_scale, lp, partials,
-                              ClipArg<true>{clip}, s);
-  else
-    launch_lamb_moments<false>(grid, policy, master, grad, m, v, ct, nchunks, n, hp, grad_scale, lp, partials,
-                               ClipArg<false>{}, s);
-  return hipGetLastError();
-}
-
-hipError_t lamb_finalize(const float* partials, int nchunks, const int32_t* segtab, int S, const float* ext,
-                         const float* clip, float* ratio, float* w_norm, float* u_norm, float* sums_out,
-                         hipStream_t s) {
-  if (S <= 0) return hipSuccess;
-  const int waves = kBlock / 64;
-  int grid = (S + waves - 1) / waves;
-  if (grid > 256) grid = 256;
-  lars_finalize_kernel<true><<<grid, kBlock, 0, s>>>(partials, nchunks, reinterpret_cast<const int4*>(segtab), S, ext,
-                                                     nullptr, clip, 1.f, 0.f, ratio, w_norm, u_norm, sums_out);
+  with_clip(clip, [&](auto ca) {
+    const auto kernel = policy == 1   ? lamb_moments_kernel<ca.on, 1>
+                        : policy == 2 ? lamb_moments_kernel<ca.on, 2>
+                                      : lamb_moments_kernel<ca.on, 0>;
+    kernel<<<chunk_grid(nchunks), kBlock, 0, s>>>(master, grad, m, v, reinterpret_cast<const int4*>(chunks), nchunks, n,
+                                                  hp, grad_scale, lp, partials, ca);
+  });
   return hipGetLastError();
 }
 
@@ -736,11 +674,9 @@ hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v,
                       const float* clip) {
   if (n <= 0) return hipSuccess;
   if (n % 64 || ratio == nullptr || map == nullptr) return hipErrorInvalidValue;
-  const int grid = grid_for(n / 4);
-  if (clip != nullptr)
-    lamb_apply_kernel<true><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ClipArg<true>{clip});
-  else
-    lamb_apply_kernel<false><<<grid, kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ClipArg<false>{});
+  with_clip(clip, [&](auto ca) {
+    lamb_apply_kernel<ca.on><<<grid_for(n / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ca);
+  });
   return hipGetLastError();
 }
 

@@ -93,41 +93,26 @@ def _cut(sl, *ts):
     return ts if sl is None else tuple(t[sl] if t is not None else None for t in ts)
 
 
-def lars_chunk_table(bounds, ranges, chunk):
-    """The seg_sumsq tables (host lists) for segments ``bounds`` = [(begin, end)] restricted to
-    the flat ``ranges``: ``chunks`` rows (segment, begin / 64, end / 64, 0) of at most ``chunk``
-    elements, never across a segment boundary, a segment's chunks consecutive; ``segs`` rows
-    (first chunk, end chunk) per segment.  Everything must lie on 64-element boundaries."""
-    for lo, hi in list(ranges) + list(bounds):
-        if lo % 64 or hi % 64 or lo < 0 or hi < lo:
-            raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
-    if chunk <= 0 or chunk % 64:
-        raise ValueError(f"LARS: chunk {chunk} must be a positive multiple of 64")
-    rs = sorted((lo, hi) for lo, hi in ranges if hi > lo)
-    chunks, segs = [], []
-    for s, (b, e) in enumerate(bounds):
-        first = len(chunks)
-        for lo, hi in rs:
-            x, y = max(b, lo), min(e, hi)
-            while x < y:
-                z = min(x + chunk, y)
-                chunks.append((s, x // 64, z // 64, 0))
-                x = z
-        segs.append((first, len(chunks)))
-    return chunks, segs
-
-
-def lamb_chunk_table(bounds, ranges, counted, chunk):
-    """``lars_chunk_table`` for lamb_moments: the chunks cover ``ranges``, and a chunk's fourth
-    field says whether it lies inside the flat ranges ``counted`` (its sums enter this rank's
-    norms) -- the chunks are cut at the edges of ``counted`` so each is wholly in or out."""
-    for lo, hi in counted:
-        if lo % 64 or hi % 64 or lo < 0 or hi < lo:
-            raise ValueError(f"LAMB: the counted range [{lo}, {hi}) is not 64-element aligned")
+def _aligned64(who, what, ranges):
     for lo, hi in ranges:
         if lo % 64 or hi % 64 or lo < 0 or hi < lo:
-            raise ValueError(f"LAMB: the flat range [{lo}, {hi}) is not 64-element aligned")
-    cs = sorted((lo, hi) for lo, hi in counted if hi > lo)
+            raise ValueError(f"{who}: the {what} range [{lo}, {hi}) is not 64-element aligned")
+
+
+def chunk_table(bounds, ranges, chunk, counted=None):
+    """The seg_sumsq / lamb_moments tables (host lists) for segments ``bounds`` = [(begin, end)]
+    restricted to the flat ``ranges``: ``chunks`` rows (segment, begin / 64, end / 64, counted) of at
+    most ``chunk`` elements, never across a segment boundary, a segment's chunks consecutive; ``segs``
+    rows (first chunk, end chunk) per segment.  Everything must lie on 64-element boundaries.
+    ``counted`` (LAMB; None: LARS's table, fourth field 0): flat ranges whose sums enter this rank's
+    norms -- the chunks are cut at their edges so each lies wholly in (fourth field 1, a segment's
+    first chunks) or out."""
+    who = "LARS" if counted is None else "LAMB"
+    _aligned64(who, "counted", counted or ())
+    _aligned64(who, "flat", list(ranges) + list(bounds))
+    if chunk <= 0 or chunk % 64:
+        raise ValueError(f"{who}: chunk {chunk} must be a positive multiple of 64")
+    cs = sorted((lo, hi) for lo, hi in counted or () if hi > lo)
     pieces = []          # ``ranges`` cut into (lo, hi, counted) runs
     for lo, hi in sorted((lo, hi) for lo, hi in ranges if hi > lo):
         x = lo
@@ -145,14 +130,31 @@ def lamb_chunk_table(bounds, ranges, counted, chunk):
     for s, (b, e) in enumerate(bounds):
         first = len(chunks)
         for flag in (1, 0):
-            part, _ = lars_chunk_table([(b, e)], [(lo, hi) for lo, hi, c in pieces if c == flag], chunk)
-            chunks += [(s, x, y, flag) for _, x, y, _ in part]
+            for lo, hi in sorted((lo, hi) for lo, hi, c in pieces if c == flag):
+                x, y = max(b, lo), min(e, hi)
+                while x < y:
+                    z = min(x + chunk, y)
+                    chunks.append((s, x // 64, z // 64, flag))
+                    x = z
         segs.append((first, len(chunks)))
     return chunks, segs
 
 
+def lars_chunk_table(bounds, ranges, chunk):
+    """``chunk_table`` for seg_sumsq."""
+    return chunk_table(bounds, ranges, chunk)
+
+
+def lamb_chunk_table(bounds, ranges, counted, chunk):
+    """``chunk_table`` for lamb_moments."""
+    return chunk_table(bounds, ranges, chunk, counted)
+
+
 class _Lars:
-    """Device state of LARS over one flat buffer (or, ``flat`` None, over loose tensors)."""
+    """Device state of the per-tensor trust ratios over one flat buffer (or, ``flat`` None, over
+    loose tensors): segment map, ratio table, norm vectors, chunk tables per set of ranges, and
+    ``local``, the [2S] sums a sharded step all-reduces (LARS: with clipping's scalar behind them)."""
+    who, local_extra = "LARS", 1
 
     def __init__(self, flat, params, exclude_1d, device):
         self.flat, self.device, self.exclude_1d = flat, device, exclude_1d
@@ -161,6 +163,7 @@ class _Lars:
             self.names = [s.name for s in segs]
             self.adapt = [not (exclude_1d and s.param.dim() < 2) for s in segs]
             self.bounds = [(s.offset, s.offset + (s.storage_numel + 63) // 64 * 64) for s in segs]
+            self.offsets = [b for b, _ in self.bounds]
             if len(segs) >= _LARS_GAP:
                 raise ValueError(f"LARS: {len(segs)} parameter tensors exceed the uint16 segment map")
             seg_of = torch.full((flat.numel // 64,), _LARS_GAP, dtype=torch.int64)
@@ -179,44 +182,39 @@ class _Lars:
         self.ratio = torch.ones(max(_LARS_SLOTS, S + 1), dtype=torch.float32, device=device)
         self.w_norm = torch.zeros(S, dtype=torch.float32, device=device)
         self.g_norm = torch.zeros(S, dtype=torch.float32, device=device)
-        self.local = torch.zeros(2 * S + 1, dtype=torch.float32, device=device)   # sharded: [2S] sums + clip's
+        self.local = torch.zeros(2 * S + self.local_extra, dtype=torch.float32, device=device)
         self.tables = {}
 
-    def table(self, ranges, capturing):
-        """Device chunk tables + partial slots of seg_sumsq over ``ranges`` (built once per set)."""
+    def table(self, ranges, capturing, counted=None):
+        """Device chunk tables + partial slots of seg_sumsq (``counted``: of lamb_moments) over
+        ``ranges``, built once per set."""
         def make():
-            chunks, segs = lars_chunk_table(self.bounds, ranges, _ext.C().seg_sumsq_chunk())
+            chunks, segs = chunk_table(self.bounds, ranges, _ext.C().seg_sumsq_chunk(), counted)
             segtab = [(a, b, int(ad), 0) for (a, b), ad in zip(segs, self.adapt)]
             i32 = dict(dtype=torch.int32, device=self.device)
             return dict(ranges=[tuple(r) for r in ranges], chunks=torch.tensor(chunks, **i32).reshape(-1, 4),
                         segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
                         partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
-        key = tuple(ranges)
+        key = tuple(ranges) if counted is None else (tuple(ranges), tuple(counted))
         return self.tables.get(key) or _graph_state(self.tables, key, capturing, make)
 
     def elem_ratio(self, lo, hi):
         """The ratio of every element of the flat range [lo, hi) (torch paths)."""
         return self.ratio[self.seg_of[lo // 64: hi // 64]].repeat_interleave(64)
 
-    def sums_torch(self, f, ranges):
-        """seg_sumsq in torch ops: [2][S] fp64 sums of squares of master / grad over ``ranges``."""
+    def sums_torch(self, bufs, ranges):
+        """seg_sumsq in torch ops: [2][S] fp64 sums of squares of the two flat ``bufs`` over ``ranges``."""
+        _aligned64(self.who, "flat", ranges)
         out = torch.zeros(2, self.S + 1, dtype=torch.float64, device=self.device)
         for lo, hi in ranges:
-            if lo % 64 or hi % 64:
-                raise ValueError(f"LARS: the flat range [{lo}, {hi}) is not 64-element aligned")
             if hi <= lo:
                 continue
             idx = self.seg_of[lo // 64: hi // 64].clamp(max=self.S)
-            for k, buf in enumerate((f.master, f.grad)):
+            for k, buf in enumerate(bufs):
                 out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
         return out[:, :self.S]
 
-    def finalize_torch(self, sums, gscale, wd):
-        """lars_finalize in torch ops; ``gscale`` = grad_scale (* the clip coefficient)."""
-        trust, eps = self.hdr.double()
-        wn = sums[0].double().sqrt()
-        gn = sums[1].double().sqrt() * gscale
-        r = trust * wn / (gn + wd * wn + eps)
+    def _set_ratios(self, sums, wn, gn, r):
         over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
         r = torch.where(over, torch.zeros_like(r), r)
         r = torch.where(self.adapt_t & (wn > 0) & (gn > 0), r, torch.ones_like(r))
@@ -224,50 +222,23 @@ class _Lars:
         self.w_norm.copy_(wn)
         self.g_norm.copy_(gn)
 
+    def finalize_torch(self, sums, gscale, wd):
+        """lars_finalize in torch ops; ``gscale`` = grad_scale (* the clip coefficient)."""
+        trust, eps = self.hdr.double()
+        wn = sums[0].double().sqrt()
+        gn = sums[1].double().sqrt() * gscale
+        self._set_ratios(sums, wn, gn, trust * wn / (gn + wd * wn + eps))
+
 
 class _Lamb(_Lars):
-    """Device state of LAMB: LARS's layout (segment map, ratio table, norm vectors; ``g_norm``
-    holds |u|), chunk tables per (moments ranges, counted ranges), ``local`` = the [2S] sums a
-    sharded step all-reduces.  ``u``: the torch paths' Adam direction between moments and update."""
-    u = None
-
-    def __init__(self, flat, params, exclude_1d, device):
-        super().__init__(flat, params, exclude_1d, device)
-        self.local = torch.zeros(2 * self.S, dtype=torch.float32, device=device)
-
-    def table(self, ranges, counted, capturing):
-        def make():
-            chunks, segs = lamb_chunk_table(self.bounds, ranges, counted, _ext.C().seg_sumsq_chunk())
-            segtab = [(a, b, int(ad), 0) for (a, b), ad in zip(segs, self.adapt)]
-            i32 = dict(dtype=torch.int32, device=self.device)
-            return dict(ranges=[tuple(r) for r in ranges], chunks=torch.tensor(chunks, **i32).reshape(-1, 4),
-                        segtab=torch.tensor(segtab, **i32).reshape(-1, 4),
-                        partials=torch.zeros(2 * len(chunks), dtype=torch.float32, device=self.device))
-        key = (tuple(ranges), tuple(counted))
-        return self.tables.get(key) or _graph_state(self.tables, key, capturing, make)
-
-    def sums_torch(self, f, ranges):
-        """[2][S] fp64 sums of squares of master / u over ``ranges``."""
-        out = torch.zeros(2, self.S + 1, dtype=torch.float64, device=self.device)
-        for lo, hi in ranges:
-            if lo % 64 or hi % 64:
-                raise ValueError(f"LAMB: the flat range [{lo}, {hi}) is not 64-element aligned")
-            if hi <= lo:
-                continue
-            idx = self.seg_of[lo // 64: hi // 64].clamp(max=self.S)
-            for k, buf in enumerate((f.master, self.u)):
-                out[k].index_add_(0, idx, buf[lo:hi].double().square().view(-1, 64).sum(1))
-        return out[:, :self.S]
+    """LAMB's: ``g_norm`` holds |u|, the tables are keyed by (moments ranges, counted ranges), ``local``
+    is the [2S] sums alone.  ``u``: the torch paths' Adam direction between moments and update."""
+    who, local_extra, u = "LAMB", 0, None
 
     def finalize_torch(self, sums):
         """lamb_finalize in torch ops."""
         wn, un = sums[0].double().sqrt(), sums[1].double().sqrt()
-        over = torch.isinf(sums.float()).any(0)      # (a sum of squares beyond fp32: ratio 0)
-        r = torch.where(over, torch.zeros_like(wn), wn / un)
-        r = torch.where(self.adapt_t & (wn > 0) & (un > 0), r, torch.ones_like(r))
-        self.ratio[:self.S] = r.float()
-        self.w_norm.copy_(wn)
-        self.g_norm.copy_(un)
+        self._set_ratios(sums, wn, un, wn / un)
 
 
 def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
@@ -326,7 +297,7 @@ class _FlatStep:
         if clip is not None or thr is not None or lars is not None:
             self._norm_state(clip, thr, lars, dev, sharded)
         if lamb is not None:
-            self.M = opt._lamb_state(lamb, f)
+            self.M = opt._trust_state("lamb", lamb, f)
             self.local2 = self.M.local if sharded else None
         if native:
             hp = st.get("hp")
@@ -343,7 +314,7 @@ class _FlatStep:
         elif thr is not None:
             self.own_clip, self.cl = True, opt._state("clip", dev)
         if lars is not None:
-            self.L = opt._lars_state(lars[2], self.f)
+            self.L = opt._trust_state("lars", lars[2], self.f)
         self.normed = self.own_clip or self.L is not None
         if sharded and self.normed:
             self.local = self.L.local if self.L is not None else opt._state("clip_local", dev)
@@ -351,7 +322,7 @@ class _FlatStep:
     def _seg_sums(self):
         L, f = self.L, self.f
         self.tab = t = L.table(self.ranges, self.opt._ldnn_capturing)
-        _ext.C().seg_sumsq(f.master, f.grad, t["chunks"], t["partials"], t["ranges"], [b for b, _ in L.bounds])
+        _ext.C().seg_sumsq(f.master, f.grad, t["chunks"], t["partials"], t["ranges"], L.offsets)
 
     def norm(self, ranges):
         """The sums of squares over ``ranges`` (of a sharded buffer: this rank's shard ranges, on
@@ -386,7 +357,7 @@ class _FlatStep:
             if local is not None:
                 local[-1:].copy_(self.sumsq.reshape(1))
         if L is not None and local is not None:
-            local[:2 * L.S].copy_(L.sums_torch(f, ranges).t().reshape(-1))
+            local[:2 * L.S].copy_(L.sums_torch((f.master, f.grad), ranges).t().reshape(-1))
 
     def finalize(self, reduced: bool):
         """The clip state, then the LARS ratios (which use the clip coefficient), then the
@@ -426,7 +397,7 @@ class _FlatStep:
             if self.skip:
                 return
             if L is not None:
-                sums = local[:2 * L.S].view(L.S, 2).t() if reduced else L.sums_torch(f, self.ranges)
+                sums = local[:2 * L.S].view(L.S, 2).t() if reduced else L.sums_torch((f.master, f.grad), self.ranges)
                 L.finalize_torch(sums, gs * (cl[_CLIP_COEF].double() if cl is not None else 1.0), wd)
 
     def moments(self, ranges, counted):
@@ -439,10 +410,10 @@ class _FlatStep:
         counted = [(lo, hi) for lo, hi in counted if hi > lo]
         if self.native:
             C = _ext.C()
-            self.mtab = t = M.table(ranges, counted, self.opt._ldnn_capturing)
+            self.mtab = t = M.table(ranges, self.opt._ldnn_capturing, counted)
             g = self.group
             C.lamb_moments(f.master, f.grad, self.ctx[0], self.ctx[1], t["chunks"], t["partials"], self.hp, f.grad_scale,
-                           *g["betas"], g["eps"], g["weight_decay"], t["ranges"], [b for b, _ in M.bounds], clip=self.cl)
+                           *g["betas"], g["eps"], g["weight_decay"], t["ranges"], M.offsets, clip=self.cl)
             if self.local2 is not None:
                 C.lamb_finalize(t["partials"], t["segtab"], M.ratio, M.w_norm, M.g_norm, sums_out=self.local2)
             return
@@ -454,7 +425,7 @@ class _FlatStep:
                                                  self.ctx[0][lo:hi], self.ctx[1][lo:hi])
         self.counted = counted
         if self.local2 is not None:
-            self.local2.copy_(M.sums_torch(f, counted).t().reshape(-1))
+            self.local2.copy_(M.sums_torch((f.master, M.u), counted).t().reshape(-1))
 
     def ratios(self, reduced: bool):
         """LAMB: the trust ratios from the all-reduced ``local2`` or from ``moments``' own sums."""
@@ -468,7 +439,8 @@ class _FlatStep:
             else:
                 _ext.C().lamb_finalize(t["partials"], t["segtab"], M.ratio, M.w_norm, M.g_norm, clip=self.cl)
             return
-        M.finalize_torch(self.local2.view(M.S, 2).t() if reduced else M.sums_torch(self.f, self.counted))
+        M.finalize_torch(self.local2.view(M.S, 2).t() if reduced
+                         else M.sums_torch((self.f.master, M.u), self.counted))
 
     def update(self, lo: int, hi: int, zero=()):
         """Update flat elements [lo, hi): one fused launch (which also zeroes the flat gradient
@@ -548,15 +520,34 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 t[1] = float(st.get("step", 0))
         return t
 
-    def _lars_state(self, excl, flat, params=None, device=None):
-        """The LARS device state over ``flat`` (None: over the loose ``params``)."""
+    def _trust_state(self, key, excl, flat, params=None, device=None):
+        """The LARS / LAMB (``key`` "lars" / "lamb") device state over ``flat`` (None: over the loose ``params``)."""
         st = self._ls()
         device = flat.master.device if flat is not None else device
-        L = st.get("lars")
-        if L is None or L.flat is not flat or L.device != device or L.exclude_1d != excl or \
-                (flat is None and L.S != len(params)):
-            L = _graph_state(st, "lars", self._ldnn_capturing, lambda: _Lars(flat, params, excl, device))
-        return L
+        T = st.get(key)
+        if T is None or T.flat is not flat or T.device != device or T.exclude_1d != excl or \
+                (flat is None and T.S != len(params)):
+            cls = _Lamb if key == "lamb" else _Lars
+            T = _graph_state(st, key, self._ldnn_capturing, lambda: cls(flat, params, excl, device))
+        return T
+
+    def _lars_state(self, *args):
+        return self._trust_state("lars", *args)
+
+    def _lamb_state(self, *args):
+        return self._trust_state("lamb", *args)
+
+    def _trust_stats(self, key, excl, norm2):
+        """``lars_stats`` / ``lamb_stats``: the state ``key`` (built when no step has run yet) as a dict."""
+        T = self._ls().get(key)
+        if T is None:
+            f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
+            ps = [p for g in self.param_groups for p in g["params"]]
+            T = self._trust_state(key, excl, f, ps, ps[0].device if ps else torch.device("cpu"))
+            if key == "lars":
+                self._write_hyperparams()
+        return {"ratio": T.ratio[:T.S], "w_norm": T.w_norm, norm2: T.g_norm, "names": list(T.names),
+                "adapted": list(T.adapt)}
 
     def _write_hyperparams(self, lr=None, conf=None):
         """Write the learning rate, the clipping threshold and LARS's trust coefficient and eps
@@ -667,16 +658,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """In segment (flat-buffer) order: the device tensors ``ratio`` / ``w_norm`` / ``g_norm`` of
         the last LARS step, the parameter ``names`` and which tensors are ``adapted`` (reading a
         tensor syncs); None when LARS is off."""
-        if self._lars_conf() is None:
-            return None
-        L = self._ls().get("lars")
-        if L is None:
-            f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
-            ps = [p for g in self.param_groups for p in g["params"]]
-            L = self._lars_state(self._lars_conf()[2], f, ps, ps[0].device if ps else torch.device("cpu"))
-            self._write_hyperparams()
-        return {"ratio": L.ratio[:L.S], "w_norm": L.w_norm, "g_norm": L.g_norm, "names": list(L.names),
-                "adapted": list(L.adapt)}
+        lars = self._lars_conf()
+        return None if lars is None else self._trust_stats("lars", lars[2], "g_norm")
 
     # ---- LAMB: per-tensor trust ratios (Lamb) -------------------------------------------
     def _lamb_conf(self):
@@ -686,30 +669,12 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return self._same_in_groups(lambda g: bool(g.get("lamb_exclude_1d", True)),
                                     "lamb_exclude_1d must be the same in every param group")
 
-    def _lamb_state(self, excl, flat, params=None, device=None):
-        """The LAMB device state over ``flat`` (None: over the loose ``params``)."""
-        st = self._ls()
-        device = flat.master.device if flat is not None else device
-        M = st.get("lamb")
-        if M is None or M.flat is not flat or M.device != device or M.exclude_1d != excl or \
-                (flat is None and M.S != len(params)):
-            M = _graph_state(st, "lamb", self._ldnn_capturing, lambda: _Lamb(flat, params, excl, device))
-        return M
-
     def lamb_stats(self):
         """In segment (flat-buffer) order: the device tensors ``ratio`` / ``w_norm`` / ``u_norm`` of
         the last LAMB step, the parameter ``names`` and which tensors are ``adapted`` (reading a
         tensor syncs); None on the other optimizers."""
         excl = self._lamb_conf()
-        if excl is None:
-            return None
-        M = self._ls().get("lamb")
-        if M is None:
-            f = self._flat_for_group(self.param_groups[0]) if len(self.param_groups) == 1 else None
-            ps = [p for g in self.param_groups for p in g["params"]]
-            M = self._lamb_state(excl, f, ps, ps[0].device if ps else torch.device("cpu"))
-        return {"ratio": M.ratio[:M.S], "w_norm": M.w_norm, "u_norm": M.g_norm, "names": list(M.names),
-                "adapted": list(M.adapt)}
+        return None if excl is None else self._trust_stats("lamb", excl, "u_norm")
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
@@ -942,6 +907,11 @@ class SGD(_FlatOptimizer):
         p.add_(g, alpha=-lr)
 
 
+def _adam_moments(m, v, g, b1, b2):
+    m.mul_(b1).add_(g, alpha=1 - b1)
+    v.mul_(b2).addcmul_(g, g, value=1 - b2)
+
+
 class Adam(_FlatOptimizer):
     decoupled = False
 
@@ -966,20 +936,25 @@ class Adam(_FlatOptimizer):
         m, v = _cut(sl, s.ctx[0], s.ctx[1])
         self._adam_torch(p, g_, m, v, s.ctx[2], g["lr"], *g["betas"], g["eps"], g["weight_decay"])
 
+    def _loose_state(self, p, cl):
+        """The per-tensor step of a loose ``p`` begins: its gradient clipped, its state (exp_avg,
+        exp_avg_sq, step; created on the first step) with the step counted."""
+        if cl is not None:
+            p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+        ps = self.state.setdefault(p, {})
+        if "exp_avg" not in ps:
+            ps["exp_avg"] = torch.zeros_like(p)
+            ps["exp_avg_sq"] = torch.zeros_like(p)
+            ps["step"] = 0
+        ps["step"] += 1
+        return ps
+
     def _loose_update(self, group, cl, loose):
         lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
         for p in group["params"]:
-            if p.grad is None:
-                continue
-            if cl is not None:
-                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
-            ps = self.state.setdefault(p, {})
-            if "exp_avg" not in ps:
-                ps["exp_avg"] = torch.zeros_like(p)
-                ps["exp_avg_sq"] = torch.zeros_like(p)
-                ps["step"] = 0
-            ps["step"] += 1
-            self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps, wd)
+            if p.grad is not None:
+                ps = self._loose_state(p, cl)
+                self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps, wd)
 
     def _adam_torch(self, p, g, m, v, t, lr, b1, b2, eps, wd):
         if wd != 0:
@@ -987,8 +962,7 @@ class Adam(_FlatOptimizer):
                 p.mul_(1 - lr * wd)
             else:
                 g = g + wd * p
-        m.mul_(b1).add_(g, alpha=1 - b1)
-        v.mul_(b2).addcmul_(g, g, value=1 - b2)
+        _adam_moments(m, v, g, b1, b2)
         bc1 = 1 - b1 ** t
         bc2 = 1 - b2 ** t
         denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
@@ -1025,7 +999,7 @@ class Lamb(_FlatOptimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d))
 
-    _begin_ranges = Adam._begin_ranges
+    _begin_ranges, _loose_state = Adam._begin_ranges, Adam._loose_state
 
     def _update_native(self, s, sl, zero):
         f, g, M = s.f, s.group, s.M
@@ -1041,10 +1015,8 @@ class Lamb(_FlatOptimizer):
     def _moments_torch(self, s, p, g_, m, v):
         """The moment update of one flat range in torch ops; returns u."""
         g = s.group
-        b1, b2 = g["betas"]
-        m.mul_(b1).add_(g_, alpha=1 - b1)
-        v.mul_(b2).addcmul_(g_, g_, value=1 - b2)
-        return self._direction(p, m, v, s.ctx[2], b1, b2, g["eps"], g["weight_decay"])
+        _adam_moments(m, v, g_, *g["betas"])
+        return self._direction(p, m, v, s.ctx[2], *g["betas"], g["eps"], g["weight_decay"])
 
     def _update_torch(self, s, sl, p, g_, ratio):
         p.sub_(s.group["lr"] * ratio * _cut(sl, s.M.u)[0])
@@ -1060,17 +1032,9 @@ class Lamb(_FlatOptimizer):
             loose["k"] += 1
             if p.grad is None:
                 continue
-            if cl is not None:
-                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
-            ps = self.state.setdefault(p, {})
-            if "exp_avg" not in ps:
-                ps["exp_avg"] = torch.zeros_like(p)
-                ps["exp_avg_sq"] = torch.zeros_like(p)
-                ps["step"] = 0
-            ps["step"] += 1
+            ps = self._loose_state(p, cl)
             m, v = ps["exp_avg"], ps["exp_avg_sq"]
-            m.mul_(b1).add_(p.grad, alpha=1 - b1)
-            v.mul_(b2).addcmul_(p.grad, p.grad, value=1 - b2)
+            _adam_moments(m, v, p.grad, b1, b2)
             u = self._direction(p.data, m, v, ps["step"], b1, b2, eps, wd)
             wn, un = float(p.detach().double().norm()), float(u.double().norm())
             ratio = wn / un if (M.adapt[k] and wn > 0 and un > 0) else 1.0

@@ -58,8 +58,8 @@ def main():
     mm, vv = torch.zeros_like(f.master), torch.zeros_like(f.master)
     hp = torch.tensor([0.0, 1.0], device="cuda")      # lr 0: the weights stay put over the iterations
     M = _Lamb(f, None, True, f.master.device)
-    t = M.table([(0, n)], [(0, n)], False)
-    offs = [b for b, _ in M.bounds]
+    t = M.table([(0, n)], False, [(0, n)])
+    offs = M.offsets
     junk = torch.empty(128 << 20, device="cuda") if a.flush else None
     flush = (lambda: junk.add_(1.0)) if a.flush else None
     B1, B2, EPS, WD = 0.9, 0.999, 1e-6, 1e-2

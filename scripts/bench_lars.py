@@ -62,7 +62,7 @@ def main():
     L = _Lars(f, None, True, f.master.device)
     L.hdr.copy_(torch.tensor([1.0, 1e-8]))
     t = L.table([(0, n)], False)
-    offs = [b for b, _ in L.bounds]
+    offs = L.offsets
     junk = torch.empty(128 << 20, device="cuda") if a.flush else None
     flush = (lambda: junk.add_(1.0)) if a.flush else None
 
