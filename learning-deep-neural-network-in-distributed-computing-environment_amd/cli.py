@@ -74,6 +74,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="clip the gradient by its global L2 norm (torch clip_grad_norm_ semantics) inside the fused "
                         "optimizer, and skip a step whose norm is not finite; 0 (default) = off.  metrics.jsonl then "
                         "logs grad_norm_last / grad_clipped_steps / grad_skipped_steps per global epoch")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing of the cross-entropy (torch semantics: targets eps / C + (1 - eps) * onehot, "
+                        "0 <= eps <= 1) inside the fused loss kernel; 0 (default) = off.  The same criterion serves "
+                        "validation and the final test, so the reported val / test losses are the smoothed ones "
+                        "(accuracy is unaffected)")
     p.add_argument("--step_size", type=int, default=25, help="StepLR step (local epochs), BAR/main.py:54")
     p.add_argument("--gamma", type=float, default=0.1)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
@@ -183,6 +188,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "optimizer", None) == "lamb":
         # ... nor for a tensor's whole Adam direction
         why = "--optimizer lamb runs on the autograd path"
+    elif getattr(args, "label_smoothing", 0.0) > 0:
+        # the static engine's head kernels compute the plain loss
+        why = "--label_smoothing runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -190,6 +198,8 @@ def resolve_engine(args, model, dev, world: int) -> bool:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if not 0.0 <= args.label_smoothing <= 1.0:
+        raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
     from . import prepare
     from .data.loader import get_loaders
     from .models import CrossEntropyLoss, build_model, dataset_for, xavier_init
@@ -268,7 +278,7 @@ def main(argv=None):
     train_loader, val_loader, test_loader, trainset, valset, tr_idx, va_idx = loaders[:7]
     fixed_classes = loaders[7] if len(loaders) > 7 else None
 
-    criterion = CrossEntropyLoss()
+    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     if not use_engine:
         optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
                                     max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,

@@ -449,7 +449,10 @@ int* xent_fin_ws(const at::Tensor& like) {
 
 void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::Tensor& dlogits,
                   const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias, int64_t num_classes,
-                  double grad_scale, const c10::optional<at::Tensor>& loss_out, double loss_scale) {
+                  double grad_scale, const c10::optional<at::Tensor>& loss_out, double loss_scale,
+                  double label_smoothing) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent: label_smoothing must be in [0, 1], got ",
+              label_smoothing);
   check_dev(logits, at::kBFloat16, "logits");
   check_dev(dlogits, at::kBFloat16, "dlogits");
   check_dev(labels, at::kLong, "labels");
@@ -488,7 +491,7 @@ void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::
   }
   check(ldnn::softmax_xent(bf16_ptr(logits), labels.data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
                            (int)logits.size(0), (int)num_classes, (int)ld, (float)grad_scale, cur_stream(logits),
-                           loss_out.has_value() ? &fin : nullptr),
+                           loss_out.has_value() ? &fin : nullptr, (float)label_smoothing),
         "softmax_xent");
 }
 
@@ -2182,9 +2185,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("a") = 1.0, py::arg("b") = 0.0, py::arg("c") = 0.0, py::arg("shadow") = py::none());
   m.def("softmax_xent", &softmax_xent, py::arg("logits"), py::arg("labels"), py::arg("dlogits"),
         py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("grad_scale"),
-        py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0,
+        py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,
         "fused softmax-xent + argmax; loss_out: the last block writes [loss_sum * loss_scale, #correct] there "
-        "(and adds both into stats if given)");
+        "(and adds both into stats if given); label_smoothing in [0, 1]: torch's smoothed targets");
   m.def("scale_bf16", [](const at::Tensor& src, const at::Tensor& scale, const at::Tensor& out) {
     check_dev(src, at::kBFloat16, "src");
     check_dev(out, at::kBFloat16, "out");

@@ -351,9 +351,12 @@ struct XentFin {
   unsigned* cnt = nullptr;
   float scale = 1.f;
 };
+// label_smoothing = eps in [0, 1] (hipErrorInvalidValue outside): targets eps/C + (1-eps)*onehot,
+// torch's label_smoothing with mean reduction -- the loss sums and dlogits are the smoothed ones,
+// #correct is unaffected.  0 launches the unsmoothed kernel instances.
 hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
                         float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s,
-                        const XentFin* fin = nullptr);
+                        const XentFin* fin = nullptr, float label_smoothing = 0.f);
 // out[i] = src[i] * (*scale) over n bf16 (the loss backward's grad_output, read on the device)
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s);
 // overlap-probe communication stand-in: `reps` copies of src on `blocks` workgroups

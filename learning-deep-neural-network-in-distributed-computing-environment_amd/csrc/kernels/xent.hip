@@ -8,6 +8,15 @@
 // One wave per row (lanes stride over classes), 4 waves per block, 16 rows per
 // block; per-block partials are combined in LDS and added with one atomic per
 // statistic / bias column.
+//
+// Label smoothing (torch's label_smoothing=eps, mean reduction) is a compile-time
+// SMOOTH instance of both kernels: targets q_c = eps/C + (1-eps)[c == label], so
+//   loss_r = logsumexp(x_r) - (1-eps) x_r[label] - (eps/C) sum_{c<C} x_r[c]
+//   dlogits = (softmax - q) * grad_scale
+// on the same loads, stores and single launch; the row sum is one more wave_sum per
+// row in the wave kernel and a register sum in the rows kernel.  conf = 1-eps and
+// epsc = eps/C are formed on the host.  The SMOOTH = false instances are the code
+// as it was.
 #include <algorithm>
 
 #include "ldnn_common.h"
@@ -56,11 +65,13 @@ __global__ __launch_bounds__(256) void scale_bf16_kernel(const bf16_t* __restric
   }
 }
 
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ logits,
                                                    const int64_t* __restrict__ labels,
                                                    bf16_t* __restrict__ dlogits, float* __restrict__ stats,
                                                    float* __restrict__ dbias, int B, int C, int ld,
-                                                   float grad_scale, int rows_per_block, XentFin fin) {
+                                                   float grad_scale, int rows_per_block, XentFin fin,
+                                                   float conf, float epsc) {
   __shared__ float sdb[4][kMaxColsPerLane * 64];
   __shared__ float sstat[4][2];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -91,17 +102,19 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
     int cand = (mx == wmx) ? amax : 0x7fffffff;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    float se = 0.f, xl = 0.f;
+    float se = 0.f, xl = 0.f, sx = 0.f;
 #pragma unroll
     for (int t = 0; t < kMaxColsPerLane; ++t) {
       const int c = lane + 64 * t;
       if (t < nt && c < C) {
         se += __expf(xv[t] - wmx);
         if (c == lab) xl = xv[t];
+        if constexpr (SMOOTH) sx += xv[t];
       }
     }
     se = wave_sum(se);
     xl = wave_sum(xl);
+    if constexpr (SMOOTH) sx = wave_sum(sx);
     const float lse = wmx + __logf(se);
     const float inv = 1.f / se;
 #pragma unroll
@@ -109,14 +122,19 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
       const int c = lane + 64 * t;
       if (t < nt && c < ld) {
         float g = 0.f;
-        if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+        if constexpr (SMOOTH) {
+          if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
+        } else {
+          if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+        }
         const uint16_t gb = f2bf(g);
         dlogits[(size_t)r * ld + c] = gb;
         dacc[t] += bf2f(gb);
       }
     }
     if (lane == 0) {
-      loss_sum += lse - xl;
+      if constexpr (SMOOTH) loss_sum += lse - conf * xl - epsc * sx;
+      else loss_sum += lse - xl;
       correct += (cand == lab) ? 1.f : 0.f;
     }
   }
@@ -149,12 +167,12 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
 // so a 4096-row batch is one load round trip instead of a chain of wave
 // shuffles per row.  Column sums for the bias gradient: per-column wave
 // reduction, then one atomic per column per wave.
-template <int LD>
+template <int LD, bool SMOOTH>
 __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict__ logits,
                                                         const int64_t* __restrict__ labels,
                                                         bf16_t* __restrict__ dlogits, float* __restrict__ stats,
                                                         float* __restrict__ dbias, int B, int C, int ld,
-                                                        float grad_scale, XentFin fin) {
+                                                        float grad_scale, XentFin fin, float conf, float epsc) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool ok = r < B;
   float x[LD];
@@ -176,25 +194,31 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int c = 0; c < LD; ++c)
       if (c < C && x[c] > mx) { mx = x[c]; am = c; }
-    float se = 0.f, xl = 0.f;
+    float se = 0.f, xl = 0.f, sx = 0.f;
 #pragma unroll
     for (int c = 0; c < LD; ++c)
       if (c == lab) xl = x[c];
 #pragma unroll
     for (int c = 0; c < LD; ++c) {
       if (c < C) {
+        if constexpr (SMOOTH) sx += x[c];
         x[c] = __expf(x[c] - mx);
         se += x[c];
       }
     }
-    loss = mx + __logf(se) - xl;  // = logsumexp - x_label
+    if constexpr (SMOOTH) loss = mx + __logf(se) - conf * xl - epsc * sx;
+    else loss = mx + __logf(se) - xl;  // = logsumexp - x_label
     correct = (am == lab) ? 1.f : 0.f;
     const float inv = 1.f / se;
     u16x8 out[LD / 8];
 #pragma unroll
     for (int c = 0; c < LD; ++c) {
       float v = 0.f;
-      if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+      if constexpr (SMOOTH) {
+        if (c < C) v = (x[c] * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
+      } else {
+        if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+      }
       const uint16_t b = f2bf(v);
       out[c / 8][c % 8] = b;
       g[c] = bf2f(b);
@@ -229,24 +253,19 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
   xent_finish(fin, stats);
 }
 
-}  // namespace
-
-hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
-                        float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin* finp) {
-  if (ld > kMaxColsPerLane * 64 || C > ld) return hipErrorInvalidValue;
-  const XentFin fin = finp ? *finp : XentFin{};
-  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
-  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
-  if (B <= 0) return hipSuccess;
+template <bool SMOOTH>
+hipError_t launch_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats, float* dbias,
+                       int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin& fin, float conf,
+                       float epsc) {
   const bool vec_ok = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
   if (vec_ok && ld <= 64) {
     const int g = (B + 255) / 256;
     switch (ld) {
 #define XENT_ROWS_CASE(L) \
-      case L: xent_rows_kernel<L><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin); break;
+      case L: xent_rows_kernel<L, SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc); break;
       XENT_ROWS_CASE(8) XENT_ROWS_CASE(16) XENT_ROWS_CASE(24) XENT_ROWS_CASE(32) XENT_ROWS_CASE(40) XENT_ROWS_CASE(48) XENT_ROWS_CASE(56)
 #undef XENT_ROWS_CASE
-      default: xent_rows_kernel<64><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin); break;
+      default: xent_rows_kernel<64, SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc); break;
     }
     return hipGetLastError();
   }
@@ -254,8 +273,25 @@ hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t*
   // instead of 4 waves walking 16 rows each), 16 rows per block beyond
   const int rpb = B <= 4 * 256 ? 4 : kRowsPerBlock;
   const int g = (B + rpb - 1) / rpb;
-  xent_kernel<<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin);
+  xent_kernel<SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin, conf, epsc);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
+                        float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin* finp,
+                        float label_smoothing) {
+  if (ld > kMaxColsPerLane * 64 || C > ld) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return hipErrorInvalidValue;  // (NaN too)
+  const XentFin fin = finp ? *finp : XentFin{};
+  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
+  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  if (label_smoothing == 0.f)
+    return launch_xent<false>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f, 0.f);
+  return launch_xent<true>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f - label_smoothing,
+                           label_smoothing / (float)C);
 }
 
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s) {

@@ -48,10 +48,23 @@ class Flatten(nn.Flatten):
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):
     """Mean cross-entropy (the reference's criterion, BAR/main.py:52) on the fused
-    softmax-xent kernel.  Pass ``stats`` to accumulate loss-sum / #correct on device."""
+    softmax-xent kernel.  Pass ``stats`` to accumulate loss-sum / #correct on device.
+    ``label_smoothing`` is torch's; class weights, ``ignore_index`` and the sum / none
+    reductions are not implemented and refused."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
+                 reduction: str = "mean", label_smoothing: float = 0.0):
+        super().__init__(weight, size_average, ignore_index, reduce, reduction, label_smoothing)
+        if weight is not None:
+            raise NotImplementedError("ldnn CrossEntropyLoss: class weights are not implemented")
+        if ignore_index != -100:
+            raise NotImplementedError("ldnn CrossEntropyLoss: ignore_index is not implemented")
+        if self.reduction != "mean":
+            raise NotImplementedError(f"ldnn CrossEntropyLoss: reduction={self.reduction!r} is not implemented "
+                                      "(mean only)")
 
     def forward(self, logits, labels, stats=None):
-        return LF.cross_entropy(logits, labels, stats)
+        return LF.cross_entropy(logits, labels, stats, self.label_smoothing)
 
 
 class Conv2d(nn.Conv2d):

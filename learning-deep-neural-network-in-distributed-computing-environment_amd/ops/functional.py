@@ -206,7 +206,7 @@ def sigmoid(x):
 
 class _SoftmaxXentNative(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, stats):
+    def forward(ctx, logits, labels, stats, label_smoothing=0.0):
         C = _ext.C()
         B, n = logits.shape
         lg = logits if (logits.dtype == torch.bfloat16 and logits.stride(1) == 1) else logits.to(torch.bfloat16).contiguous()
@@ -215,7 +215,8 @@ class _SoftmaxXentNative(torch.autograd.Function):
         # one launch: the kernel's last block writes [mean loss, #correct] into `out`
         # and adds [loss sum, #correct] into `stats` (no fill / divide / add kernels)
         out = torch.empty(2, dtype=torch.float32, device=lg.device)
-        C.softmax_xent(lg, labels, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B)
+        C.softmax_xent(lg, labels, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
+                       label_smoothing=label_smoothing)
         ctx.save_for_backward(dfull)
         ctx.n, ctx.in_dtype = n, logits.dtype
         return out[0]
@@ -226,28 +227,33 @@ class _SoftmaxXentNative(torch.autograd.Function):
         if ctx.in_dtype == torch.bfloat16 and getattr(go, "_ldnn_unit", False):
             # the graphed steps' persistent seed is exactly 1 (train.graphed.unit_seed): the
             # forward's d(mean loss)/d(logits) is the gradient as is, no scaling pass
-            return dfull[:, : ctx.n], None, None
+            return dfull[:, : ctx.n], None, None, None
         if ctx.in_dtype == torch.bfloat16 and go.dtype == torch.float32 and go.is_cuda and dfull.numel() % 8 == 0:
             # d = dlogits * grad_output in one pass over the padded rows (pad stays 0)
             full = torch.empty_like(dfull)
             _ext.C().scale_bf16(dfull, go.reshape(1), full)
-            return full[:, : ctx.n], None, None
+            return full[:, : ctx.n], None, None, None
         d = dfull[:, : ctx.n]
         d = (d.float() * go).to(torch.bfloat16) if ctx.in_dtype == torch.bfloat16 else d.float() * go
         if ctx.in_dtype == torch.bfloat16 and dfull.stride(0) != ctx.n:
             full = torch.zeros_like(dfull)
             full[:, : ctx.n] = d
             d = full[:, : ctx.n]
-        return d, None, None
+        return d, None, None, None
 
 
-def cross_entropy(logits, labels, stats: torch.Tensor | None = None):
+def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoothing: float = 0.0):
     """Mean softmax cross-entropy.  `stats` (device fp32, >= 2) accumulates
-    [sum of per-sample loss, #correct] without a host sync."""
+    [sum of per-sample loss, #correct] without a host sync.  `label_smoothing` in [0, 1]:
+    torch's smoothed targets eps / C + (1 - eps) * onehot (the loss, its gradient and the
+    accumulated loss sum are the smoothed ones; #correct is unaffected)."""
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
     if _ext.use_native(logits):
-        return _SoftmaxXentNative.apply(logits, labels, stats)
+        return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing)
     lf = logits.float()
-    loss = F.cross_entropy(lf, labels)
+    loss = F.cross_entropy(lf, labels, label_smoothing=label_smoothing)
     if stats is not None:
         with torch.no_grad():
             stats[0] += loss.detach() * labels.numel()

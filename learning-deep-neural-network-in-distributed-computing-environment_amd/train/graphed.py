@@ -20,6 +20,8 @@ What makes the ldnn step capturable:
   the graph does NOT capture the host->device lr write, ``GraphedStep``
   refreshes it before a replay whenever ``param_groups[..]['lr']`` changed
   (so StepLR & co. keep working);
+* the criterion's label smoothing is a kernel argument of the loss launch, so it IS
+  captured: a replay raises when the criterion's value differs from the captured one;
 * every native op writes into caller-provided / caching-allocator tensors
   (graph-pool allocations during capture).
 
@@ -65,6 +67,16 @@ def unit_seed(device) -> torch.Tensor:
     one = torch.ones((), dtype=torch.float32, device=device)
     one._ldnn_unit = True
     return one
+
+
+def check_label_smoothing(criterion, captured: float) -> None:
+    """A captured step has the criterion's label smoothing baked into its loss launch (a kernel
+    argument, not a device scalar): a replay under another value would silently train with the
+    captured one.  A host float compare, no device traffic."""
+    now = float(getattr(criterion, "label_smoothing", 0.0))
+    if now != captured:
+        raise RuntimeError(f"the criterion's label_smoothing changed from {captured} to {now} since this step "
+                           "was captured: capture again")
 
 
 def static_input(model, x_example: torch.Tensor):
@@ -131,6 +143,7 @@ class GraphedStep:
         if not x_example.is_cuda:
             raise ValueError("GraphedStep needs GPU tensors")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
         self.x, self._stage_x = static_input(model, x_example)
         self.y = y_example.detach().clone()
         self.stats = stats if stats is not None else torch.zeros(2, dtype=torch.float32, device=self.x.device)
@@ -197,6 +210,7 @@ class GraphedStep:
         """One training step on (x, y); returns the (device) loss tensor of this step."""
         if x.shape != self.x.shape or y.shape != self.y.shape:
             return self._eager_step(x, y)
+        check_label_smoothing(self.criterion, self._label_smoothing)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         self.graph.replay()
@@ -263,6 +277,7 @@ class GraphedDPStep:
         if not x_example.is_cuda:
             raise ValueError("GraphedDPStep needs GPU tensors")
         self.dp, self.model, self.criterion, self.optimizer = dp, dp.module, criterion, optimizer
+        self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
         self.bk, self.flat, self.comm = dp.bucketer, dp.flat, dp.comm
         self._SUM = SUM
         self.comm_fn = comm_fn
@@ -504,6 +519,7 @@ class GraphedDPStep:
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         if x.shape != self.x.shape or y.shape != self.y.shape:
             return self._eager_step(x, y)
+        check_label_smoothing(self.criterion, self._label_smoothing)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         works = {}

@@ -47,6 +47,9 @@ def main():
                          "kernels with unchanged math)")
     ap.add_argument("--lars", type=float, default=0.0,
                     help="lars_trust of the ldnn SGD (LARS trust ratios; 0 = off)")
+    ap.add_argument("--label_smoothing", type=float, default=0.0,
+                    help="label smoothing of the ldnn criterion (the fused loss kernel's SMOOTH instance; 0 = off); "
+                         "the stock baseline gets the same value")
     a = ap.parse_args()
     from ldnn.ops import _ext as _e
 
@@ -67,7 +70,7 @@ def main():
     opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
            else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
            else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
-    crit = CrossEntropyLoss()
+    crit = CrossEntropyLoss(label_smoothing=a.label_smoothing)
     xb = x.bfloat16()
 
     def step_ldnn():
@@ -84,7 +87,7 @@ def main():
             gs(xb, y)
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
@@ -102,7 +105,7 @@ def main():
         _ext._DISABLED = True
         ropt = (torch.optim.Adam(ref.parameters(), lr=1e-3) if a.optimizer in ("adam", "lamb") else
                 torch.optim.SGD(ref.parameters(), lr=0.01, momentum=0.9))
-        ce = nn.CrossEntropyLoss()
+        ce = nn.CrossEntropyLoss(label_smoothing=a.label_smoothing)
         xc = x.contiguous(memory_format=torch.channels_last)
 
         def step_stock():

@@ -1,0 +1,85 @@
+"""Are the unsmoothed softmax-xent kernels still the instruction streams they were?
+
+    hipcc -O3 -std=c++17 -I<pkg>/csrc/include --offload-arch=gfx950 -munsafe-fp-atomics \
+          --cuda-device-only -S <pkg>/csrc/kernels/xent.hip -o new.s      (same on the older tree: old.s)
+    python scripts/xent_isa_diff.py old.s new.s
+
+Pairs every xent kernel of old.s with the instance of new.s that has the same leading template
+arguments and SMOOTH = false, and compares their instruction streams: comments dropped, the
+function number of local labels (.LBB<fn>_<n>) and the kernels' own symbol names normalised.
+Two scalar loads that differ only in their constant offset are counted apart: appended kernel
+arguments move the hidden ones (block / grid size) behind them in the kernel-argument segment.
+Prints one line per kernel; exit status 1 when a pair differs in anything else.
+"""
+import re
+import sys
+
+
+def kernels(path):
+    """{mangled name: [instruction lines]} for every kernel function of an assembly file."""
+    out, name, body = {}, None, None
+    for ln in open(path):
+        m = re.match(r"^(_Z\w+):", ln)
+        if m and name is None:
+            name, body = m.group(1), []
+            continue
+        if name is None:
+            continue
+        if ln.startswith(".Lfunc_end"):
+            out[name] = body
+            name = None
+            continue
+        ln = ln.split(";", 1)[0].strip()
+        if not ln or (ln.startswith(".") and not ln.startswith(".LBB")):
+            continue   # directives
+        ln = re.sub(r"\.LBB\d+_", ".LBB_", ln)
+        ln = re.sub(r"_Z\w+", "SYM", ln)
+        body.append(ln)
+    return out
+
+
+def key(name):
+    """('rows', LD) / ('wave',) / None, and the SMOOTH flag (None: a tree without it)."""
+    m = re.search(r"xent_rows_kernelILi(\d+)(?:ELb([01]))?EE", name)
+    if m:
+        return ("rows", int(m.group(1))), (None if m.group(2) is None else m.group(2) == "1")
+    m = re.search(r"\d+xent_kernel(?:ILb([01])EE)?", name)
+    if m:
+        return ("wave",), (None if m.group(1) is None else m.group(1) == "1")
+    return None, None
+
+
+_SLOAD = re.compile(r"^(s_load_dword\w* s\S+ s\[\d+:\d+\],) 0x[0-9a-f]+$")
+
+
+def offset_only(x, y):
+    a, b = _SLOAD.match(x), _SLOAD.match(y)
+    return bool(a and b and a.group(1) == b.group(1))
+
+
+def main():
+    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    olds = {key(n)[0]: b for n, b in old.items() if key(n)[0] is not None}
+    plain = {key(n)[0]: b for n, b in new.items() if key(n)[0] is not None and not key(n)[1]}
+    smooth = {key(n)[0]: b for n, b in new.items() if key(n)[1]}
+    bad = 0
+    for k in sorted(olds):
+        a, b = olds[k], plain.get(k)
+        tag = "_".join(str(v) for v in k)
+        if b is None:
+            print(f"{tag}: missing from {sys.argv[2]}")
+            bad += 1
+            continue
+        pairs = [(x, y) for x, y in zip(a, b) if x != y]
+        offs = sum(offset_only(x, y) for x, y in pairs)
+        diff = len(pairs) - offs + abs(len(a) - len(b))
+        bad += diff != 0
+        s = smooth.get(k)
+        print(f"{tag}: old {len(a)} instructions, new SMOOTH=false {len(b)}, kernel-argument offsets moved in "
+              f"{offs}, otherwise differing {diff}: {'IDENTICAL' if diff == 0 else 'DIFFERENT'}"
+              + (f"; SMOOTH=true {len(s)} instructions ({len(s) - len(b):+d})" if s is not None else ""))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
