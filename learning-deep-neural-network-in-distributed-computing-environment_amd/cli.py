@@ -79,6 +79,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "0 <= eps <= 1) inside the fused loss kernel; 0 (default) = off.  The same criterion serves "
                         "validation and the final test, so the reported val / test losses are the smoothed ones "
                         "(accuracy is unaffected)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the weights (decay d, 0 <= d < 1; 0 = off) on the "
+                        "device, updated once per non-skipped optimizer step, and run every validation and the final "
+                        "test on the averaged weights (BatchNorm running statistics are not averaged: the live ones "
+                        "serve).  Each replica averages its own master; an end-of-epoch aggregation is one more jump "
+                        "of the weights it follows.  metrics.jsonl then logs ema_updates / ema_a_last per global epoch")
+    p.add_argument("--ema_no_warmup", action="store_true",
+                   help="--ema_decay: use d from the first step on instead of d_t = min(d, (1 + c) / (10 + c)) after "
+                        "c updates")
     p.add_argument("--step_size", type=int, default=25, help="StepLR step (local epochs), BAR/main.py:54")
     p.add_argument("--gamma", type=float, default=0.1)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
@@ -191,6 +200,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "label_smoothing", 0.0) > 0:
         # the static engine's head kernels compute the plain loss
         why = "--label_smoothing runs on the autograd path"
+    elif getattr(args, "ema_decay", 0.0) > 0:
+        # the static engine's wgrad-fused optimizer epilogue has no averaging pass behind it
+        why = "--ema_decay runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -200,13 +212,15 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if not 0.0 <= args.label_smoothing <= 1.0:
         raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
     from . import prepare
     from .data.loader import get_loaders
     from .models import CrossEntropyLoss, build_model, dataset_for, xavier_init
     from .optim import StepLR, build_optimizer
     from .parallel.comm import default_comm
     from .parallel.ddp import DataParallel
-    from .train.trainer import train_global
+    from .train.trainer import ema_eval, train_global
     from .train.validator import evaluate
     from .utils import distributed as D
     from .utils.checkpoint import Checkpointer, load_checkpoint
@@ -282,6 +296,8 @@ def main(argv=None):
     if not use_engine:
         optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
                                     max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,
+                                    ema_decay=args.ema_decay if args.ema_decay > 0 else None,
+                                    ema_warmup=not args.ema_no_warmup,
                                     **(dict(lars_trust=args.lars_trust, lars_eps=args.lars_eps,
                                             lars_exclude_1d=not args.lars_adapt_1d)
                                        if args.optimizer == "lars" else
@@ -351,8 +367,11 @@ def main(argv=None):
         logger.log(kind="final_weights", sha256=weights_digest(model))
     result = {"histories": [list(h) if not isinstance(h, list) else h for h in histories]}
     if rank == 0 and not args.no_eval:
-        loss, acc, _, _ = evaluate(net, test_loader, criterion, dev, rank, num_classes=trainset.num_classes,
-                                   verbose=not args.quiet)
+        # (--ema_decay: the test runs on the averaged weights, like every validation; train_global
+        # left master and average whole)
+        with ema_eval(optimizer):
+            loss, acc, _, _ = evaluate(net, test_loader, criterion, dev, rank, num_classes=trainset.num_classes,
+                                       verbose=not args.quiet)
         rep = {k: v for k, v in evaluate.last_report.items() if k != "confusion_matrix"}
         result.update(test_loss=loss, test_acc=acc, **rep)
         logger.log(kind="test", test_loss=loss, test_acc=acc, **rep)

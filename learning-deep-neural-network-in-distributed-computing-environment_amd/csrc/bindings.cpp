@@ -1031,6 +1031,46 @@ void bump_step(const at::Tensor& hp, const c10::optional<at::Tensor>& clip) {
   check(ldnn::bump_step(hp.data_ptr<float>(), cur_stream(hp), clip_ptr(clip, hp)), "bump_step");
 }
 
+// the weight EMA's header [decay, warm-up, updates, a_t] on the device of `like`
+float* ema_hdr(const char* fn, const at::Tensor& hdr, const at::Tensor* like) {
+  check_dev(hdr, at::kFloat, "hdr");
+  TORCH_CHECK(hdr.is_contiguous() && hdr.numel() >= ldnn::kEmaState &&
+                  (like == nullptr || hdr.device() == like->device()),
+              fn, ": hdr must be a contiguous fp32 header of ", (int)ldnn::kEmaState,
+              " elements on the buffers' device");
+  return hdr.data_ptr<float>();
+}
+
+void ema_begin(const at::Tensor& hdr, const c10::optional<at::Tensor>& clip) {
+  float* h = ema_hdr("ema_begin", hdr, nullptr);
+  check(ldnn::ema_begin(h, cur_stream(hdr), clip_ptr(clip, hdr)), "ema_begin");
+}
+
+// (f32_bufs would name all four refusals in one message; these name the one that failed)
+int64_t ema_bufs(const char* fn, const at::Tensor& master, const at::Tensor& ema) {
+  check_dev(master, at::kFloat, "master");
+  check_dev(ema, at::kFloat, "ema");
+  TORCH_CHECK(master.is_contiguous() && ema.is_contiguous(), fn, ": master / ema must be contiguous");
+  TORCH_CHECK(master.numel() == ema.numel(), fn, ": master (", master.numel(), ") and ema (", ema.numel(),
+              ") must be equally long");
+  TORCH_CHECK(master.device() == ema.device(), fn, ": master / ema must be on one device");
+  TORCH_CHECK(aligned16(master.data_ptr()) && aligned16(ema.data_ptr()), fn,
+              ": master / ema must be 16-byte aligned");
+  return master.numel();
+}
+
+void ema_update(const at::Tensor& master, const at::Tensor& ema, const at::Tensor& hdr) {
+  const int64_t n = ema_bufs("ema_update", master, ema);
+  const float* h = ema_hdr("ema_update", hdr, &master);
+  check(ldnn::ema_update(master.data_ptr<float>(), ema.data_ptr<float>(), h, n, cur_stream(master)), "ema_update");
+}
+
+void ema_swap(const at::Tensor& master, const at::Tensor& ema, const c10::optional<at::Tensor>& shadow) {
+  const int64_t n = ema_bufs("ema_swap", master, ema);
+  uint16_t* sh = shadow_ptr("ema_swap", shadow, master, true);
+  check(ldnn::ema_swap(master.data_ptr<float>(), ema.data_ptr<float>(), sh, n, cur_stream(master)), "ema_swap");
+}
+
 void synth_normal(const at::Tensor& x, int64_t seed, double stddev) {
   check_dev(x, at::kBFloat16, "x");
   TORCH_CHECK(x.is_contiguous(), "synth_normal: x must be contiguous");
@@ -2257,6 +2297,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
   m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
+  m.def("ema_begin", &ema_begin, "weight EMA, once per step: a_t and the update count into hdr (not on a skipped step)",
+        py::arg("hdr"), py::arg("clip") = py::none());
+  m.def("ema_update", &ema_update, "ema += a_t * (master - ema), a_t read from hdr", py::arg("master"),
+        py::arg("ema"), py::arg("hdr"));
+  m.def("ema_swap", &ema_swap, "master <-> ema (exact), shadow = bf16(new master)", py::arg("master"), py::arg("ema"),
+        py::arg("shadow") = py::none());
   m.def("grad_sumsq", &grad_sumsq, "per-workgroup sums of squares of a flat fp32 range into partials[slot0 ...]; "
         "returns the number of slots written", py::arg("grad"), py::arg("partials"), py::arg("slot0") = 0);
   m.def("grad_sumsq_parts", &ldnn::grad_sumsq_parts, py::arg("n"));

@@ -426,6 +426,16 @@ enum ClipSlot : int {
   kClipSkipped = 6,
   kClipState = 8,
 };
+// The weight EMA's device header (fp32; the functions are further down): decay and the warm-up flag
+// are WRITTEN BY THE HOST like the lr (a captured graph follows a changed decay), the count and the
+// step's coefficient by ema_begin.  The count is fp32 (exact to 2^24).
+enum EmaSlot : int {
+  kEmaDecay = 0,    // d (host)
+  kEmaWarmup = 1,   // != 0: warm-up on (host)
+  kEmaUpdates = 2,  // c: EMA updates done so far
+  kEmaAlpha = 3,    // a_t of the running step; 0 on a skipped step
+  kEmaState = 4,
+};
 // workgroups (= partial slots) a grad_sumsq launch over n elements uses under the current grid cap
 int grad_sumsq_parts(int64_t n);
 // partials[slot0 + b] = sum of squares workgroup b saw of grad[0, n) (any element alignment; no
@@ -486,6 +496,17 @@ hipError_t lamb_moments(const float* master, const float* grad, float* m, float*
 hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v, uint16_t* shadow, const float* hp,
                       LambParams lp, int64_t n, const float* ratio, const uint16_t* map, hipStream_t s,
                       const float* clip = nullptr);
+
+// ---- exponential moving average of the weights, e += a_t * (w - e) (header: EmaSlot above) ----
+// Once per step, one thread: a_t = 1 - d, with warm-up max(1 - d, 9 / (10 + c)) (the decay ramps as
+// d_t = min(d, (1 + c) / (10 + c))); then c += 1.  With clip[kClipSkip] set: a_t = 0, c stays.
+hipError_t ema_begin(float* hdr, hipStream_t s, const float* clip = nullptr);
+// ema[i] += a_t * (master[i] - ema[i]) over n elements (both 16-byte aligned), a_t = hdr[kEmaAlpha];
+// a_t == 0 (a skipped step) returns before touching either buffer.
+hipError_t ema_update(const float* master, float* ema, const float* hdr, int64_t n, hipStream_t s);
+// master[i] <-> ema[i] over n elements (both 16-byte aligned), shadow[i] = bf16(new master[i])
+// (shadow optional, 8-byte aligned): an exact exchange, so a second call restores all three.
+hipError_t ema_swap(float* master, float* ema, uint16_t* shadow, int64_t n, hipStream_t s);
 
 // ---- classifier head (<= 64 classes): fused Linear + softmax-xent, and its wgrad
 struct HeadParams {

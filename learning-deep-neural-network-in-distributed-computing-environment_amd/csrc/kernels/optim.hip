@@ -537,6 +537,71 @@ __global__ void lamb_apply_kernel(float* __restrict__ param, float* __restrict__
   }
 }
 
+// ---- EMA of the weights: a pass of its own behind the update kernels (12 B per element) ----
+// One thread, once per step, before any range: this step's coefficient and the update count.
+template <bool CLIP>
+__global__ void ema_begin_kernel(float* hdr, ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) {  // a skipped step averages nothing and is not counted
+      hdr[kEmaAlpha] = 0.f;
+      return;
+    }
+  }
+  const float c = hdr[kEmaUpdates];
+  float a = 1.f - hdr[kEmaDecay];
+  if (hdr[kEmaWarmup] != 0.f) a = fmaxf(a, 9.f / (10.f + c));
+  hdr[kEmaAlpha] = a;
+  hdr[kEmaUpdates] = c + 1.f;
+}
+
+// e += a_t * (w - e).  e is touched once per step: nontemporal both ways.  The master, which the
+// update kernel has just written with nontemporal stores, is loaded nontemporally too -- a measured
+// choice against plain loads (scripts/bench_ema.py's buffers, profiles/r12/ema_master_load_ab.jsonl).
+// The pair "Adam then ema_update", us, plain / nontemporal: warm loops 88.2 / 91.4 (ResNet-18) and
+// 304.9 / 324.6 (EnhancedCNN), but with 512 MiB streamed through the cache before every iteration, as
+// a forward and backward leave it, 103.4 / 96.6 and 377.9 / 348.5; and the graphed training step
+// decides the same way: EnhancedCNN b64 Adam 1.769 / 1.731 ms (1.635 without the EMA), ResNet-18 b64
+// SGD 2.629 / 2.631 against 2.603 (profiles/r12/ema_graphed_steps.jsonl).
+__global__ void ema_update_kernel(const float* __restrict__ master, float* __restrict__ ema,
+                                  const float* __restrict__ hdr, int64_t n) {
+  const float a = hdr[kEmaAlpha];
+  if (a == 0.f) return;
+  const int64_t nv = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = t0; i < nv; i += stride) {
+    const floatx4 w = ld4<true>(master, i);
+    floatx4 e = ld4<true>(ema, i);
+    e += a * (w - e);
+    st4<true>(ema, i, e);
+  }
+  for (int64_t i = nv * 4 + t0; i < n; i += stride) {
+    const float e = ema[i];
+    ema[i] = e + a * (master[i] - e);
+  }
+}
+
+// master <-> ema, shadow = bf16(new master): every element is read and written by one thread, so the
+// exchange is exact.
+__global__ void ema_swap_kernel(float* __restrict__ master, float* __restrict__ ema, bf16_t* __restrict__ shadow,
+                                int64_t n) {
+  const int64_t nv = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = t0; i < nv; i += stride) {
+    const floatx4 w = ld4<true>(master, i), e = ld4<true>(ema, i);
+    st4<true>(master, i, e);
+    st4<true>(ema, i, w);
+    if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = u16x4{f2bf(e[0]), f2bf(e[1]), f2bf(e[2]), f2bf(e[3])};
+  }
+  for (int64_t i = nv * 4 + t0; i < n; i += stride) {
+    const float w = master[i], e = ema[i];
+    master[i] = e;
+    ema[i] = w;
+    if (shadow) shadow[i] = f2bf(e);
+  }
+}
+
 int g_opt_max_blocks = 2048;  // optimizer grid cap (set_opt_max_blocks: a narrow side-stream update)
 
 inline int grid_for(int64_t n4) {
@@ -677,6 +742,23 @@ hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v,
   with_clip(clip, [&](auto ca) {
     lamb_apply_kernel<ca.on><<<grid_for(n / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ca);
   });
+  return hipGetLastError();
+}
+
+hipError_t ema_begin(float* hdr, hipStream_t s, const float* clip) {
+  with_clip(clip, [&](auto ca) { ema_begin_kernel<ca.on><<<1, 1, 0, s>>>(hdr, ca); });
+  return hipGetLastError();
+}
+
+hipError_t ema_update(const float* master, float* ema, const float* hdr, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  ema_update_kernel<<<grid_for((n + 3) / 4), kBlock, 0, s>>>(master, ema, hdr, n);
+  return hipGetLastError();
+}
+
+hipError_t ema_swap(float* master, float* ema, uint16_t* shadow, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  ema_swap_kernel<<<grid_for((n + 3) / 4), kBlock, 0, s>>>(master, ema, shadow, n);
   return hipGetLastError();
 }
 

@@ -44,9 +44,29 @@ second reduce stage (``_FlatStep.moments`` / ``ratios``): ``lamb_moments`` updat
 reduces per tensor, ``lamb_finalize`` leaves the ratios on the device, ``lamb_apply`` writes the
 weights; the sharded step all-reduces the ``2S`` sums in a collective of its own after the
 moments -- they depend on the clip coefficient, which depends on the first reduction.
+
+``ema_decay`` (default None = off; every optimizer, ``build_optimizer(ema_decay=, ema_warmup=)``) keeps an
+exponential moving average of the weights for evaluation: ``_ls()["ema"]``, a flat fp32 buffer shaped
+like the master (loose tensors: ``state[p]["ema"]``), created by the first eager step as a copy of the
+master BEFORE that step's update and, once per non-skipped step after the weight update, moved by
+``e += a_t * (w - e)`` with ``a_t = 1 - d`` or, with ``ema_warmup`` (default), ``max(1 - d, 9 / (10 + c))``
+after ``c`` updates.  ``c``, ``d`` and ``a_t`` live in a small device header (``ema_hdr``; the host
+writes ``d`` and the warm-up flag like the lr, so a captured step follows ``sync_hyperparams()``), and
+the pass rides on ``_FlatStep`` (``ema_begin`` in ``finalize``, ``ema_update`` behind every ``update``),
+so the eager, sharded, range and graphed steps average alike and need no extra collective; a step the
+non-finite guard skips changes neither ``e`` nor ``c``.  The average is saved by ``state_dict()`` (with
+``ema_updates``) and all-gathered by ``gather_master(optimizer)`` with the moments.
+``ema_weights()`` swaps it in for evaluation; ``ema_stats()`` reports the count and the last ``a_t``.
+Buffers (BatchNorm running statistics) are not averaged -- evaluation under the averaged weights uses
+the live ones -- and the end-of-epoch aggregation leaves ``e`` alone: each replica's average follows
+its own master, the jump at an aggregation included.  A graph captured with the EMA off never
+averages until it is captured again; one captured with it on keeps averaging (with the last decay
+written) after ``ema_decay`` is set to None.  Padding and alignment gaps are averaged like everything
+else: zero in the master, they stay zero.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
@@ -70,13 +90,15 @@ def _refuse_partial_sharded(params):
 # slots of the clipping state tensor (csrc/include/ldnn_kernels.h ClipSlot)
 _CLIP_MAX, _CLIP_COEF, _CLIP_SKIP, _CLIP_NORM, _CLIP_STEPS, _CLIP_CLIPPED, _CLIP_SKIPPED, _CLIP_LEN = 0, 1, 2, 3, 4, 5, 6, 8
 # device-only entries of _ls(): rebuilt by an eager step, never saved
-_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb")
+_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb", "ema_hdr")
+# slots of the weight EMA's header (csrc/include/ldnn_kernels.h EmaSlot)
+_EMA_DECAY, _EMA_WARMUP, _EMA_UPDATES, _EMA_ALPHA, _EMA_LEN = 0, 1, 2, 3, 4
 # LARS ratio table: one slot per uint16 map value, so every map entry is in bounds; the slots
 # past the segments are never written and hold 1 (alignment gaps map to the last one)
 _LARS_SLOTS, _LARS_GAP = 65536, 65535
 _CAPTURE_MSG = "run an eager optimizer step before capturing it into a graph"
 # lengths of the fp32 device vectors of _ls() (clip_scratch: as many slots as the ranges need)
-_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1}
+_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1, "ema_hdr": _EMA_LEN}
 
 
 def _graph_state(store: dict, key, capturing: bool, make):
@@ -254,6 +276,22 @@ def _clip_finalize_torch(cl, total_sq, grad_scale=1.0):
     cl[_CLIP_SKIPPED] += (~finite).float()
 
 
+def _ema_begin_torch(hdr, skip=False):
+    """ema_begin's math in torch ops (fp32, no host read): this step's a_t, and the count."""
+    if skip:
+        hdr[_EMA_ALPHA] = 0.0
+        return
+    a = 1.0 - hdr[_EMA_DECAY]
+    a = torch.where(hdr[_EMA_WARMUP] != 0, torch.maximum(a, 9.0 / (10.0 + hdr[_EMA_UPDATES])), a)
+    hdr[_EMA_ALPHA] = a
+    hdr[_EMA_UPDATES] += 1
+
+
+def _ema_update_torch(e, w, hdr):
+    """ema_update in torch ops: e += a_t * (w - e)."""
+    e.add_((w - e).mul_(hdr[_EMA_ALPHA].to(e.device)))
+
+
 class _FlatStep:
     """ONE optimizer step of one flat buffer ``f``, as the stages every driver runs in this order:
 
@@ -279,17 +317,23 @@ class _FlatStep:
 
     ``clip``: ``(state, skip)`` of a norm taken outside (several groups / loose tensors).
 
+    The weight EMA (``ema``: the flat average, ``ema_hdr`` its header) rides on two of the stages, so
+    every driver averages in the stream and graph link of its updates: ``finalize`` issues
+    ``ema_begin`` (this step's a_t and the count; a skipped step gets a_t = 0) and ``update(lo, hi)``
+    issues ``ema_update`` on the same range right behind the optimizer's launch.
+
     The stages hand their results on in the object, so the order is a precondition: when the
     step takes a norm (``normed``: its own clipping, or LARS), ``norm`` comes before ``finalize``;
     ``finalize`` comes before any ``update``.  With neither, ``norm`` may be left out."""
 
     # what a plain step (no clipping, no LARS) never sets
     own_clip = normed = False
-    cl = skip = L = M = hp = local = local2 = tab = mtab = sumsq = ctx = None
+    cl = skip = L = M = hp = local = local2 = tab = mtab = sumsq = ctx = ema = ema_hdr = None
     ranges, counted, nparts = (), (), 0
 
     def __init__(self, opt, f, group, clip=None, sharded=False):
         self.opt, self.f, self.group = opt, f, group
+        opt._refuse_inside_ema("an optimizer step")
         self.st = st = opt._ls()
         self.native = native = _ext.use_native(f.master)
         dev = f.master.device
@@ -299,6 +343,8 @@ class _FlatStep:
         if lamb is not None:
             self.M = opt._trust_state("lamb", lamb, f)
             self.local2 = self.M.local if sharded else None
+        if opt._ema_conf() is not None:
+            self.ema, self.ema_hdr = opt._ema_state(f)
         if native:
             hp = st.get("hp")
             self.hp = hp if hp is not None and hp.device == dev else opt._state("hp", dev)
@@ -367,6 +413,11 @@ class _FlatStep:
             self._finalize_norms(reduced)
         if not self.skip:
             self.ctx = self.opt._begin_ranges(self)
+        if self.ema is not None:
+            if self.native:
+                _ext.C().ema_begin(self.ema_hdr, clip=self.cl)
+            else:
+                _ema_begin_torch(self.ema_hdr, self.skip)
 
     def _finalize_norms(self, reduced):
         f, L, cl, local = self.f, self.L, self.cl, self.local
@@ -454,6 +505,8 @@ class _FlatStep:
                 raise ValueError(f"{'LARS' if L is not None else 'LAMB'}: the update range [{lo}, {hi}) is not "
                                  "64-element aligned")
             self.opt._update_native(self, sl, zero if lo == 0 else [(a - lo, b - lo) for a, b in zero])
+            if self.ema is not None:
+                _ext.C().ema_update(*_cut(sl, f.master, self.ema), self.ema_hdr)
             return
         if not self.skip:
             p, g, shadow = _cut(sl, f.master, f.grad, f.shadow)
@@ -464,6 +517,8 @@ class _FlatStep:
             self.opt._update_torch(self, sl, p, g, L.elem_ratio(lo, hi) if L is not None else None)
             if shadow is not None:
                 shadow.copy_(p)
+            if self.ema is not None:
+                _ema_update_torch(_cut(sl, self.ema)[0], p, self.ema_hdr)
         for a, b in zero:
             f.grad[a:b].zero_()
 
@@ -501,6 +556,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if self._clip_threshold() is not None and "hp" in ls and "exp_avg" in ls:
             # the fused Adam's step count lives on the device: skipped steps did not advance it
             flat["step"] = int(ls["hp"][1].item())
+        if "ema_hdr" in ls:
+            # ... and so does the EMA's update count (load_state_dict hands it to the next header)
+            flat["ema_updates"] = int(ls["ema_hdr"][_EMA_UPDATES].item())
         sd["ldnn_flat_state"] = flat
         return sd
 
@@ -510,7 +568,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _state(self, key, device, n=None):
         """The fp32 device vector ``key`` of ``_ls()``, at least ``n`` long: ``hp`` [lr, Adam's
         step count], ``clip`` [max_norm, coef, skip, last_norm, steps, clipped, skipped, -],
-        ``clip_scratch`` (grad_sumsq's partial slots), ``clip_local`` (the 1-element local sum)."""
+        ``clip_scratch`` (grad_sumsq's partial slots), ``clip_local`` (the 1-element local sum),
+        ``ema_hdr`` [decay, warm-up flag, EMA updates, last a_t]."""
         st = self._ls()
         t = st.get(key)
         n = n or _STATE_LEN[key]
@@ -518,6 +577,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
             t = _graph_state(st, key, self._ldnn_capturing, lambda: torch.zeros(n, dtype=torch.float32, device=device))
             if key == "hp":
                 t[1] = float(st.get("step", 0))
+            elif key == "ema_hdr":
+                t[_EMA_UPDATES] = float(st.get("ema_updates", 0))
         return t
 
     def _trust_state(self, key, excl, flat, params=None, device=None):
@@ -550,13 +611,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 "adapted": list(T.adapt)}
 
     def _write_hyperparams(self, lr=None, conf=None):
-        """Write the learning rate, the clipping threshold and LARS's trust coefficient and eps
-        into whichever of their device tensors exist.  ``conf``: ``(_clip_threshold(),
-        _lars_conf())`` where the caller has them already."""
+        """Write the learning rate, the clipping threshold, LARS's trust coefficient and eps and the
+        EMA's decay and warm-up flag into whichever of their device tensors exist.  ``conf``:
+        ``(_clip_threshold(), _lars_conf())`` where the caller has them already."""
         st = self._ls()
-        hp, cl, L = st.get("hp"), st.get("clip"), st.get("lars")
+        hp, cl, L, eh = st.get("hp"), st.get("clip"), st.get("lars"), st.get("ema_hdr")
         if hp is not None:
             hp[0].fill_(self.param_groups[0]["lr"] if lr is None else lr)
+        if eh is not None:
+            ema = self._ema_conf()
+            if ema is not None:    # (switched off after a capture: the captured kernels keep the last decay)
+                eh[_EMA_DECAY].fill_(ema[0])
+                eh[_EMA_WARMUP].fill_(float(ema[1]))
         if cl is None and L is None:
             return
         mx, lars = conf if conf is not None else (self._clip_threshold(), self._lars_conf())
@@ -571,7 +637,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def sync_hyperparams(self):
         """Write the current learning rate (and clipping threshold, LARS trust coefficient and
-        eps) into the device hyper-parameter tensors."""
+        eps, EMA decay and warm-up flag) into the device hyper-parameter tensors."""
         self._write_hyperparams()
 
     def _buf(self, name, like):
@@ -676,6 +742,122 @@ class _FlatOptimizer(torch.optim.Optimizer):
         excl = self._lamb_conf()
         return None if excl is None else self._trust_stats("lamb", excl, "u_norm")
 
+    # ---- EMA of the weights (evaluation weights) ----------------------------------------
+    _ldnn_in_ema = False    # inside ema_weights(): the master holds the average
+
+    @staticmethod
+    def _check_ema_decay(d):
+        if d is not None and not 0 < d < 1:
+            raise ValueError(f"ema_decay must be None (off) or in (0, 1); got {d}")
+
+    @staticmethod
+    def _group_ema(g):
+        d = g.get("ema_decay")
+        return None if d is None else (float(d), bool(g.get("ema_warmup", True)))
+
+    def _ema_conf(self):
+        """``(decay, warmup)``, or None when the EMA is off.  One setting for the whole optimizer; the
+        keys are read with .get, so state saved before they existed loads."""
+        return self._same_in_groups(self._group_ema, "ema_decay / ema_warmup must be the same in every param group")
+
+    def _ema_state(self, f):
+        """``(ema, header)`` of the flat buffer ``f``; the average starts as a copy of the master (the
+        first eager step calls this before its update)."""
+        st = self._ls()
+        e = st.get("ema")
+        if e is None or e.shape != f.master.shape or e.device != f.master.device:
+            e = _graph_state(st, "ema", self._ldnn_capturing, lambda: f.master.detach().clone())
+        return e, self._state("ema_hdr", f.master.device)
+
+    def _refuse_inside_ema(self, what):
+        if self._ldnn_in_ema:
+            raise RuntimeError(f"{what} inside ema_weights(): the parameters hold the average, not the live weights")
+
+    def _ema_flat(self):
+        """The one flat buffer the EMA covers (None: loose tensors); anything between is refused."""
+        flats = [self._flat_for_group(g) for g in self.param_groups]
+        if all(f is None for f in flats):
+            return None
+        if len(flats) != 1:
+            raise ValueError("ema_decay needs ONE param group holding one flat buffer, or loose tensors only")
+        return flats[0]
+
+    def _loose_ema_begin(self):
+        """Loose tensors, before the step's updates: every parameter's average (created as a copy of
+        it) and the header."""
+        ps = [p for g in self.param_groups for p in g["params"]]
+        for p in ps:
+            if "ema" not in self.state.setdefault(p, {}):
+                self.state[p]["ema"] = p.detach().clone()
+        hdr = self._state("ema_hdr", ps[0].device if ps else torch.device("cpu"))
+        self._write_hyperparams()
+        return ps, hdr
+
+    def ema_stats(self):
+        """The device scalars ``updates`` (EMA updates so far) and ``a_last`` (the last step's a_t; 0
+        after a skipped step) -- reading one syncs -- and ``decay``; None when the EMA is off."""
+        conf = self._ema_conf()
+        if conf is None:
+            return None
+        hdr = self._ls().get("ema_hdr")
+        if hdr is None:
+            ps = self.param_groups[0]["params"]
+            hdr = self._state("ema_hdr", ps[0].device if ps else torch.device("cpu"))
+            self._write_hyperparams()
+        return {"updates": hdr[_EMA_UPDATES], "a_last": hdr[_EMA_ALPHA], "decay": conf[0]}
+
+    @contextlib.contextmanager
+    @torch.no_grad()
+    def ema_weights(self):
+        """Inside the context the parameters (fp32 master and bf16 shadow) hold the EMA and the EMA
+        buffer holds the live weights -- an exact exchange, undone bit for bit on leaving.  Buffers
+        (BatchNorm running statistics) are not averaged: evaluation uses the live ones.  No
+        optimizer step, and no replay of a graph that holds one, may run inside.  Of a sharded
+        buffer the average must be whole first: ``gather_master(optimizer)`` on every rank."""
+        if self._ema_conf() is None:
+            raise RuntimeError("ema_weights(): the EMA is off (ema_decay=None)")
+        if self._ldnn_in_ema:
+            raise RuntimeError("ema_weights() is already active: the context does not nest")
+        f = self._ema_flat()
+        if f is not None:
+            e = self._ls().get("ema")
+            pairs = None
+            if e is not None and (e.shape != f.master.shape or e.device != f.master.device):
+                e = None
+            sh = getattr(f, "shard_sync", None)
+            if e is not None and sh is not None and not sh.master_whole:
+                raise RuntimeError("ema_weights(): this rank holds only its shards of the average; call "
+                                   "gather_master(optimizer) on every rank first")
+        else:
+            pairs = [(p, self.state.get(p, {}).get("ema")) for g in self.param_groups for p in g["params"]]
+            e = None if any(a is None for _, a in pairs) or not pairs else pairs
+        if e is None:
+            raise RuntimeError("ema_weights(): no optimizer step has run yet, there is no average")
+
+        def swap():
+            if pairs is not None:
+                for p, _ in pairs:
+                    st = self.state[p]
+                    p.data, st["ema"] = st["ema"], p.data
+            elif _ext.use_native(f.master):
+                _ext.C().ema_swap(f.master, e, f.shadow)
+                if f.shadow is not None:
+                    torch.autograd.graph.increment_version(f.shadow)   # (as refresh_shadow does)
+            else:
+                tmp = f.master.clone()
+                f.master.copy_(e)
+                e.copy_(tmp)
+                if f.shadow is not None:
+                    f.shadow.copy_(f.master)
+
+        swap()
+        self._ldnn_in_ema = True
+        try:
+            yield
+        finally:
+            self._ldnn_in_ema = False
+            swap()
+
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         flat_state = state_dict.pop("ldnn_flat_state", {})
@@ -709,9 +891,13 @@ class _FlatOptimizer(torch.optim.Optimizer):
         (one pass instead of a later zero_grad fill; on MI355X the zero writes inside
         the bandwidth-bound update cost about what the fill launch does)."""
         loss = closure() if closure is not None else None
+        self._refuse_inside_ema("step()")
         groups = self.param_groups
         flats = [self._flat_for_group(g) for g in groups]
         clip = None
+        loose_ema = None     # the EMA over loose tensors (a flat buffer's rides on its _FlatStep)
+        if self._ema_conf() is not None and self._ema_flat() is None:
+            loose_ema = self._loose_ema_begin()
         if len(flats) != 1 or flats[0] is None:
             # several groups / loose tensors: one norm over all of them in torch ops; and one LARS
             # setting for every group, or a ValueError, before any update
@@ -724,6 +910,13 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 self._flat_step(f, group, clip, clear_grads)
             elif clip is None or not clip[1]:
                 self._loose_update(group, clip[0] if clip is not None else None, loose)
+        if loose_ema is not None:
+            ps, hdr = loose_ema
+            skipped = clip is not None and clip[1]
+            _ema_begin_torch(hdr, skipped)
+            if not skipped:
+                for p in ps:
+                    _ema_update_torch(self.state[p]["ema"], p.data, hdr)
         return loss
 
     def _flat_step(self, f, group, clip, clear_grads):
@@ -835,12 +1028,15 @@ class SGD(_FlatOptimizer):
     fp32 gives that tensor ratio 0.  ``lars_stats()`` reports the last ratios and norms."""
 
     def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_grad_norm=None, lars_trust=None, lars_eps=1e-8, lars_exclude_1d=True):
+                 max_grad_norm=None, lars_trust=None, lars_eps=1e-8, lars_exclude_1d=True, ema_decay=None,
+                 ema_warmup=True):
         if lars_trust is not None and lars_trust <= 0:
             raise ValueError(f"lars_trust must be positive (None: LARS off); got {lars_trust}")
+        self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, max_grad_norm=max_grad_norm, lars_trust=lars_trust,
-                                      lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d))
+                                      lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d, ema_decay=ema_decay,
+                                      ema_warmup=ema_warmup))
 
     def _begin_ranges(self, s):
         # (``first`` is host-driven: the very first step seeds the momentum)
@@ -915,9 +1111,11 @@ def _adam_moments(m, v, g, b1, b2):
 class Adam(_FlatOptimizer):
     decoupled = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True):
+        self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      max_grad_norm=max_grad_norm))
+                                      max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup))
 
     def _begin_ranges(self, s):
         if s.native:
@@ -972,8 +1170,9 @@ class Adam(_FlatOptimizer):
 class AdamW(Adam):
     decoupled = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
-        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup)
 
 
 class Lamb(_FlatOptimizer):
@@ -995,9 +1194,11 @@ class Lamb(_FlatOptimizer):
     Adam's (``exp_avg``, ``exp_avg_sq``, ``step``); ``lamb_stats()`` reports the last ratios."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_grad_norm=None,
-                 lamb_exclude_1d=True):
+                 lamb_exclude_1d=True, ema_decay=None, ema_warmup=True):
+        self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d))
+                                      max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d,
+                                      ema_decay=ema_decay, ema_warmup=ema_warmup))
 
     _begin_ranges, _loose_state = Adam._begin_ranges, Adam._loose_state
 
@@ -1043,8 +1244,10 @@ class Lamb(_FlatOptimizer):
 
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
-                    max_grad_norm: float | None = None, **lars):
-    """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  "lars": SGD with
+                    max_grad_norm: float | None = None, ema_decay: float | None = None, ema_warmup: bool = True,
+                    **lars):
+    """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  ema_decay / ema_warmup: the
+    weight EMA of every optimizer (None: off).  "lars": SGD with
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
     "sgd" takes them too); Adam and AdamW refuse them.  "lamb": Lamb, which takes
     ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords."""
@@ -1056,15 +1259,18 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     bad = set(lars) - allowed
     if bad:
         raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
+    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if name == "lamb":
-        return Lamb(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
+        return Lamb(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema, **lars)
     if name == "lars":
         lars.setdefault("lars_trust", 0.001)
-        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
+        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema,
+                   **lars)
     if name == "sgd":
-        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **lars)
+        return SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema,
+                   **lars)
     if name == "adam":
-        return Adam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        return Adam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     if name == "adamw":
-        return AdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        return AdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     raise ValueError(f"unknown optimizer {name!r}")

@@ -19,7 +19,9 @@ What makes the ldnn step capturable:
 * the fused optimizers read lr (and Adam's step count) from a device tensor;
   the graph does NOT capture the host->device lr write, ``GraphedStep``
   refreshes it before a replay whenever ``param_groups[..]['lr']`` changed
-  (so StepLR & co. keep working);
+  (so StepLR & co. keep working); the weight EMA's decay travels the same way, and its
+  ``ema_begin`` / ``ema_update`` launches are captured with the optimizer's -- a graph
+  captured with ``ema_decay=None`` never averages until it is captured again;
 * the criterion's label smoothing is a kernel argument of the loss launch, so it IS
   captured: a replay raises when the criterion's value differs from the captured one;
 * every native op writes into caller-provided / caching-allocator tensors
@@ -191,10 +193,10 @@ class GraphedStep:
         return loss
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold and LARS's trust coefficient / eps travel like the lr: device
-        # scalars the captured kernels read)
-        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"))
-               for g in self.optimizer.param_groups]
+        # (the clipping threshold, LARS's trust coefficient / eps and the EMA's decay / warm-up flag
+        # travel like the lr: device scalars the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
+                g.get("ema_warmup")) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -492,10 +494,10 @@ class GraphedDPStep:
             self._fire(done)
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold and LARS's trust coefficient / eps travel like the lr: device
-        # scalars the captured kernels read)
-        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"))
-               for g in self.optimizer.param_groups]
+        # (the clipping threshold, LARS's trust coefficient / eps and the EMA's decay / warm-up flag
+        # travel like the lr: device scalars the captured kernels read)
+        lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
+                g.get("ema_warmup")) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()

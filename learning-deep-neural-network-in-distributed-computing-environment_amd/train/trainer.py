@@ -27,6 +27,7 @@ What changes is how it runs on MI355X:
 """
 from __future__ import annotations
 
+import contextlib
 import time
 
 import numpy as np
@@ -265,6 +266,18 @@ def _unpack(buf, E_l, max_len):
     return recs, bls, int(buf[1].item())
 
 
+def ema_eval(optimizer, dp=None):
+    """The context an evaluation runs in: ``optimizer.ema_weights()`` when the optimizer keeps a
+    weight EMA (the averaged weights swapped in; buffers such as BatchNorm running statistics stay
+    the live ones), else nothing.  Under sharded DP the master and the average are made whole first
+    -- collective, so every rank must evaluate at the same points."""
+    if getattr(optimizer, "ema_stats", lambda: None)() is None:
+        return contextlib.nullcontext()
+    if dp is not None and getattr(dp, "sharded", False):
+        dp.gather_master(optimizer)
+    return optimizer.ema_weights()
+
+
 def train_global(model, trainloader, val_loader, trainset, valset, indices_train, indices_val, criterion, optimizer,
                  scheduler, device, rank, world_size, num_local_epochs, num_global_epochs, timelimit, batch_size,
                  prev_fraction, next_fraction, local_weight=0.5, aggregation_type="equal",
@@ -342,7 +355,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                         scheduler.step()
                 break
             samples += train_local_epoch.last_samples
-            with tm.phase("validate"):
+            with tm.phase("validate"), ema_eval(optimizer, dp):
                 val_loss, val_acc = validate(model, val_loader, criterion, dev)
             records.append((loss, acc, val_loss, val_acc))
             batch_losses.append(bl)
@@ -451,6 +464,10 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                 if r.numel():
                     clip_rec.update(lamb_ratio_min=float(r.min()), lamb_ratio_median=float(r.median()),
                                     lamb_ratio_max=float(r.max()))
+            # weight EMA: update count and the last step's a_t, one read each per global epoch
+            ema_stats = getattr(optimizer, "ema_stats", lambda: None)()
+            if ema_stats is not None:
+                clip_rec.update(ema_updates=int(ema_stats["updates"]), ema_a_last=float(ema_stats["a_last"]))
             logger.log(kind="global_epoch", global_epoch=global_epoch + 1, duration_s=duration,
                        train_loss=H["global_train_losses"][-1], train_acc=H["global_train_accuracies"][-1],
                        val_loss=H["global_val_losses"][-1], val_acc=H["global_val_accuracies"][-1],

@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--label_smoothing", type=float, default=0.0,
                     help="label smoothing of the ldnn criterion (the fused loss kernel's SMOOTH instance; 0 = off); "
                          "the stock baseline gets the same value")
+    ap.add_argument("--ema_decay", type=float, default=0.0,
+                    help="ema_decay of the ldnn optimizer (the weight-EMA pass behind every update; 0 = off); the "
+                         "stock baseline keeps no average")
     a = ap.parse_args()
     from ldnn.ops import _ext as _e
 
@@ -67,6 +70,8 @@ def main():
     if a.lars > 0:
         assert a.optimizer == "sgd", "--lars goes with --optimizer sgd"
         kw["lars_trust"] = a.lars
+    if a.ema_decay > 0:
+        kw["ema_decay"] = a.ema_decay
     opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
            else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
            else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
@@ -87,7 +92,7 @@ def main():
             gs(xb, y)
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
