@@ -79,6 +79,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "0 <= eps <= 1) inside the fused loss kernel; 0 (default) = off.  The same criterion serves "
                         "validation and the final test, so the reported val / test losses are the smoothed ones "
                         "(accuracy is unaffected)")
+    p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                   help="Mixup of every training batch with a permutation of itself, lam ~ Beta(ALPHA, ALPHA), one "
+                        "draw per batch, in one native pass (mix.hip) that also writes the class-probability targets "
+                        "of the soft-target loss kernel; 0 (default) = off.  Training accuracy is then agreement with "
+                        "the dominant label; validation and test use hard labels.  metrics.jsonl then logs "
+                        "mix_lam_mean per global epoch")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                   help="CutMix likewise: a box of area ~ 1 - lam comes from the permuted image; 0 (default) = off")
+    p.add_argument("--mix_prob", type=float, default=1.0,
+                   help="--mixup / --cutmix: probability that a batch is mixed at all")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5,
+                   help="--mixup and --cutmix both on: probability that a mixed batch takes CutMix")
     p.add_argument("--ema_decay", type=float, default=0.0,
                    help="keep an exponential moving average of the weights (decay d, 0 <= d < 1; 0 = off) on the "
                         "device, updated once per non-skipped optimizer step, and run every validation and the final "
@@ -203,6 +215,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "ema_decay", 0.0) > 0:
         # the static engine's wgrad-fused optimizer epilogue has no averaging pass behind it
         why = "--ema_decay runs on the autograd path"
+    elif getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0:
+        # the static engine's head kernels take hard labels
+        why = "--mixup / --cutmix runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -214,8 +229,15 @@ def main(argv=None):
         raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
+    for flag, v in (("--mixup", args.mixup), ("--cutmix", args.cutmix)):
+        if not (v >= 0.0 and math.isfinite(v)):
+            raise SystemExit(f"{flag} must be a finite alpha >= 0, got {v}")
+    for flag, v in (("--mix_prob", args.mix_prob), ("--mix_switch_prob", args.mix_switch_prob)):
+        if not 0.0 <= v <= 1.0:
+            raise SystemExit(f"{flag} must be in [0, 1], got {v}")
     from . import prepare
     from .data.loader import get_loaders
+    from .data.mix import BatchMix
     from .models import CrossEntropyLoss, build_model, dataset_for, xavier_init
     from .optim import StepLR, build_optimizer
     from .parallel.comm import default_comm
@@ -285,10 +307,13 @@ def main(argv=None):
         net = dp if dp is not None else model
 
     dtype = torch.bfloat16 if (args.dtype == "bf16" and dev.type == "cuda") else torch.float32
+    # (the train loader fills in its dataset's class count)
+    mix = (BatchMix(args.mixup, args.cutmix, args.mix_prob, args.mix_switch_prob)
+           if args.mixup > 0 or args.cutmix > 0 else None)
     loaders = get_loaders(args.batch_size, world, rank, net, dev, fixed_ratio, dataset=dataset, comm=comm,
                           seed=args.seed, partition_rule=args.partition_rule, n_train=args.n_train,
                           n_test=args.n_test, dtype=dtype, augment=args.augment, data_root=args.data_root,
-                          augment_val=args.augment_val)
+                          augment_val=args.augment_val, mix=mix)
     train_loader, val_loader, test_loader, trainset, valset, tr_idx, va_idx = loaders[:7]
     fixed_classes = loaders[7] if len(loaders) > 7 else None
 
@@ -329,7 +354,7 @@ def main(argv=None):
 
                 tr_idx, va_idx = ex["indices_train"].numpy(), ex["indices_val"].numpy()
                 train_loader = DeviceLoader(trainset, tr_idx, args.batch_size, dev, dtype=dtype, augment=args.augment,
-                                            seed=loader_seed(args.seed, rank, start))
+                                            seed=loader_seed(args.seed, rank, start), mix=mix)
                 val_loader = DeviceLoader(valset, va_idx, args.batch_size, dev, dtype=dtype,
                                           augment=args.augment if args.augment_val else False,
                                           seed=(loader_seed(args.seed, rank, start) * 31 + 7) & 0x7FFFFFFF)

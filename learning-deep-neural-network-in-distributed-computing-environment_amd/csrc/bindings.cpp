@@ -447,15 +447,17 @@ int* xent_fin_ws(const at::Tensor& like) {
   return it->second.data_ptr<int>();
 }
 
-void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::Tensor& dlogits,
-                  const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias, int64_t num_classes,
-                  double grad_scale, const c10::optional<at::Tensor>& loss_out, double loss_scale,
-                  double label_smoothing) {
+// softmax_xent (labels: int64 [B]) and softmax_xent_soft (target: fp32 [B, num_classes]); exactly one is given
+void xent_launch(const at::Tensor& logits, const at::Tensor* labels, const at::Tensor* target,
+                 const at::Tensor& dlogits, const c10::optional<at::Tensor>& stats,
+                 const c10::optional<at::Tensor>& dbias, int64_t num_classes, double grad_scale,
+                 const c10::optional<at::Tensor>& loss_out, double loss_scale, double label_smoothing) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent: label_smoothing must be in [0, 1], got ",
               label_smoothing);
   check_dev(logits, at::kBFloat16, "logits");
   check_dev(dlogits, at::kBFloat16, "dlogits");
-  check_dev(labels, at::kLong, "labels");
+  if (labels) check_dev(*labels, at::kLong, "labels");
+  if (target) check_dev(*target, at::kFloat, "target");
   float* st = nullptr;
   if (stats.has_value()) {
     check_dev(*stats, at::kFloat, "stats");
@@ -466,7 +468,19 @@ void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && dlogits.sizes() == logits.sizes() &&
                   dlogits.strides() == logits.strides(),
               "xent: logits/dlogits layout mismatch");
-  TORCH_CHECK(labels.is_contiguous() && labels.numel() == logits.size(0), "xent: bad labels");
+  if (labels) TORCH_CHECK(labels->is_contiguous() && labels->numel() == logits.size(0), "xent: bad labels");
+  if (target) {
+    TORCH_CHECK(logits.dim() == 2 && target->dim() == 2 && target->size(0) == logits.size(0) &&
+                    target->size(1) == num_classes,
+                "xent: target must be [B, num_classes] = [", logits.size(0), ", ", num_classes, "], got ",
+                target->sizes());
+    TORCH_CHECK(target->device() == logits.device(), "xent: target is on ", target->device(), ", logits on ",
+                logits.device());
+    TORCH_CHECK(target->stride(1) == 1 && (target->size(0) <= 1 || target->stride(0) >= num_classes),
+                "xent: target rows must be dense (inner stride 1, row stride >= num_classes), got strides ",
+                target->strides());
+    TORCH_CHECK(num_classes >= 1, "xent: no classes");
+  }
   // logits may be a [B][C] view of a zero-padded [B][ld] buffer (ld % 8 == 0):
   // the kernel reads C columns and writes all ld columns of dlogits (pad = 0).
   const int64_t ld = logits.stride(0);
@@ -489,10 +503,67 @@ void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::
     fin.cnt = reinterpret_cast<unsigned*>(ws + 2);
     fin.scale = (float)loss_scale;
   }
-  check(ldnn::softmax_xent(bf16_ptr(logits), labels.data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
+  if (target) {
+    const int64_t ldq = target->size(0) > 1 ? target->stride(0) : std::max<int64_t>(num_classes, 1);
+    TORCH_CHECK(ldq <= INT32_MAX, "xent: target row stride too large");
+    check(ldnn::softmax_xent_soft(bf16_ptr(logits), target->data_ptr<float>(), (int)ldq, bf16_mut(dlogits), st, db,
+                                  (int)logits.size(0), (int)num_classes, (int)ld, (float)grad_scale,
+                                  cur_stream(logits), loss_out.has_value() ? &fin : nullptr, (float)label_smoothing),
+          "softmax_xent_soft");
+    return;
+  }
+  check(ldnn::softmax_xent(bf16_ptr(logits), labels->data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
                            (int)logits.size(0), (int)num_classes, (int)ld, (float)grad_scale, cur_stream(logits),
                            loss_out.has_value() ? &fin : nullptr, (float)label_smoothing),
         "softmax_xent");
+}
+
+void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, const at::Tensor& dlogits,
+                  const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias, int64_t num_classes,
+                  double grad_scale, const c10::optional<at::Tensor>& loss_out, double loss_scale,
+                  double label_smoothing) {
+  xent_launch(logits, &labels, nullptr, dlogits, stats, dbias, num_classes, grad_scale, loss_out, loss_scale,
+              label_smoothing);
+}
+
+void softmax_xent_soft(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& dlogits,
+                       const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias,
+                       int64_t num_classes, double grad_scale, const c10::optional<at::Tensor>& loss_out,
+                       double loss_scale, double label_smoothing) {
+  xent_launch(logits, nullptr, &target, dlogits, stats, dbias, num_classes, grad_scale, loss_out, loss_scale,
+              label_smoothing);
+}
+
+// Mixup / CutMix of a batch with its permuted self + the dense soft targets, one launch (mix.hip)
+void batch_mix(const at::Tensor& x, const at::Tensor& perm, const at::Tensor& labels, const at::Tensor& out,
+               const at::Tensor& q, bool cutmix, double lam, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  TORCH_CHECK(x.is_cuda() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16) && x.dim() == 4 &&
+                  x.is_contiguous(),
+              "batch_mix: x must be a contiguous [B, C, H, W] fp32 / bf16 GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == x.scalar_type() && out.sizes() == x.sizes() &&
+                  out.is_contiguous() && out.device() == x.device() && out.data_ptr() != x.data_ptr(),
+              "batch_mix: out must be a second contiguous tensor like x");
+  const int64_t B = x.size(0), H = x.size(2), W = x.size(3);
+  check_dev(perm, at::kLong, "perm");
+  check_dev(labels, at::kLong, "labels");
+  check_dev(q, at::kFloat, "q");
+  TORCH_CHECK(perm.is_contiguous() && perm.numel() == B && labels.is_contiguous() && labels.numel() == B &&
+                  perm.device() == x.device() && labels.device() == x.device() && q.device() == x.device(),
+              "batch_mix: perm and labels must be dense [B] tensors on x's device");
+  TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && q.size(0) == B && q.size(1) % 4 == 0 && q.size(1) >= 4 &&
+                  aligned16(q.data_ptr()),
+              "batch_mix: q must be a dense, 16-byte aligned [B, ldq] tensor with ldq % 4 == 0");
+  TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "batch_mix: lam must be in [0, 1], got ", lam);
+  TORCH_CHECK(0 <= y0 && y0 <= y1 && y1 <= H && 0 <= x0 && x0 <= x1 && x1 <= W, "batch_mix: box [", y0, ", ", y1,
+              ") x [", x0, ", ", x1, ") outside the ", H, " x ", W, " image");
+  TORCH_CHECK(B <= 65534 && H >= 1 && W >= 1 && x.size(1) >= 1 && x.numel() / std::max<int64_t>(B, 1) < (1ll << 31),
+              "batch_mix: batch too large");
+  if (B == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check(ldnn::batch_mix(x.data_ptr(), out.data_ptr(), x.scalar_type() == at::kFloat, perm.data_ptr<int64_t>(),
+                        labels.data_ptr<int64_t>(), q.data_ptr<float>(), (int)q.size(1), (int)B, x.numel() / B, (int)H,
+                        (int)W, cutmix, (float)lam, (int)y0, (int)y1, (int)x0, (int)x1, cur_stream(x)),
+        "batch_mix");
 }
 
 // up to two [begin, end) element ranges of `grad` to clear after the update reads them
@@ -2228,6 +2299,15 @@ PYBIND11_MODULE(_C, m) {
         py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,
         "fused softmax-xent + argmax; loss_out: the last block writes [loss_sum * loss_scale, #correct] there "
         "(and adds both into stats if given); label_smoothing in [0, 1]: torch's smoothed targets");
+  m.def("softmax_xent_soft", &softmax_xent_soft, py::arg("logits"), py::arg("target"), py::arg("dlogits"),
+        py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("grad_scale"),
+        py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,
+        "softmax_xent with class-probability targets: fp32 [B, num_classes], inner stride 1 (torch's "
+        "F.cross_entropy(logits, target, label_smoothing), mean reduction)");
+  m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("perm"), py::arg("labels"), py::arg("out"), py::arg("q"),
+        py::arg("cutmix"), py::arg("lam"), py::arg("y0") = 0, py::arg("y1") = 0, py::arg("x0") = 0,
+        py::arg("x1") = 0,
+        "Mixup / CutMix of a batch with x[perm] + dense soft targets q [B, ldq], one launch (mix.hip)");
   m.def("scale_bf16", [](const at::Tensor& src, const at::Tensor& scale, const at::Tensor& out) {
     check_dev(src, at::kBFloat16, "src");
     check_dev(out, at::kBFloat16, "out");

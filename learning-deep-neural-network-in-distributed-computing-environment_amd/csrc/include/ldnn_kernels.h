@@ -357,8 +357,23 @@ struct XentFin {
 hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
                         float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s,
                         const XentFin* fin = nullptr, float label_smoothing = 0.f);
+// Soft targets: q [B] rows of C fp32 class probabilities (row stride ldq >= C) instead of labels,
+// torch's F.cross_entropy(logits, q, label_smoothing=eps) with mean reduction.  With q' = (1-eps) q + eps/C
+// and s = sum q' (rows need not sum to 1): loss = s logsumexp(x) - sum q' x, dlogits = (softmax s - q') *
+// grad_scale; #correct counts rows whose logits' first-index argmax is q's.  Everything else as softmax_xent.
+hipError_t softmax_xent_soft(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,
+                             float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s,
+                             const XentFin* fin = nullptr, float label_smoothing = 0.f);
 // out[i] = src[i] * (*scale) over n bf16 (the loss backward's grad_output, read on the device)
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s);
+// ---- batch mixing (mix.hip): Mixup / CutMix of a contiguous [B][n] batch (n = C*H*W elements per image,
+// fp32 or bf16) with its permuted self, and the dense soft targets q [B][ldq] (fp32, ldq % 4 == 0, 16-B
+// aligned; q[i][y_i] += lam, q[i][y_perm[i]] += 1 - lam, everything else 0) in one launch.
+// mixup: out[i] = lam x[i] + (1-lam) x[perm[i]]; cutmix: x[perm[i]] inside rows [y0, y1) x columns
+// [x0, x1), x[i] outside (lam then only weighs the targets).  out must not alias x.
+hipError_t batch_mix(const void* x, void* out, bool is_f32, const int64_t* perm, const int64_t* labels, float* q,
+                     int ldq, int B, int64_t n, int H, int W, bool cutmix, float lam, int y0, int y1, int x0, int x1,
+                     hipStream_t s);
 // overlap-probe communication stand-in: `reps` copies of src on `blocks` workgroups
 hipError_t standin_copy(const float* src, float* dst, int64_t n, int blocks, int reps, hipStream_t s);
 

@@ -15,8 +15,22 @@
 //   dlogits = (softmax - q) * grad_scale
 // on the same loads, stores and single launch; the row sum is one more wave_sum per
 // row in the wave kernel and a register sum in the rows kernel.  conf = 1-eps and
-// epsc = eps/C are formed on the host.  The SMOOTH = false instances are the code
+// epsc = eps/C are formed on the host.  The plain (XM_PLAIN) instances are the code
 // as it was.
+//
+// Soft targets (torch's class-probability targets, XM_SOFT): the kernels read a row of
+// fp32 targets q_r (row stride ldq >= C) instead of a label.  With q'_c = conf q_c + epsc
+// and s = sum_c q'_c (NOT assumed 1: torch does not normalise),
+//   loss_r = s logsumexp(x_r) - sum_c q'_c x_r[c]
+//   dlogits = (softmax s - q') * grad_scale
+// and a row counts as correct when the first-index argmax of its logits is the
+// first-index argmax of q_r over c < C.  One instance serves eps = 0 and eps > 0.
+// The rows kernel (a lane owns a row) reads q with 16-B loads where ldq % 4 == 0 and
+// the base is 16-B aligned (the last, partial group of a row and every other layout:
+// 4-B loads); in the wave kernel lanes stride over the classes, so its 4-B loads are
+// already whole 256-B lines per wave instruction.  The LD = 64 rows instance holds
+// x, q' and the rounded gradient per lane without scratch (compiler output in
+// profiles/r13), so the soft mode keeps the plain mode's split between the kernels.
 #include <algorithm>
 
 #include "ldnn_common.h"
@@ -28,6 +42,8 @@ namespace {
 
 constexpr int kRowsPerBlock = 16;  // 4 rows per wave: B = 4096 -> 256 blocks fill the chip
 constexpr int kMaxColsPerLane = 16;  // C <= 1024
+
+enum XentMode { XM_PLAIN = 0, XM_SMOOTH = 1, XM_SOFT = 2 };
 
 // Last-block finalize (fin.out set): every block's statistic atomics are made
 // device-visible before its arrival is counted; the last arrival swaps the sums
@@ -65,13 +81,15 @@ __global__ __launch_bounds__(256) void scale_bf16_kernel(const bf16_t* __restric
   }
 }
 
-template <bool SMOOTH>
+template <int MODE>
 __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ logits,
                                                    const int64_t* __restrict__ labels,
                                                    bf16_t* __restrict__ dlogits, float* __restrict__ stats,
                                                    float* __restrict__ dbias, int B, int C, int ld,
                                                    float grad_scale, int rows_per_block, XentFin fin,
-                                                   float conf, float epsc) {
+                                                   float conf, float epsc, const float* __restrict__ q,
+                                                   int ldq) {
+  constexpr bool SMOOTH = MODE == XM_SMOOTH, SOFT = MODE == XM_SOFT;
   __shared__ float sdb[4][kMaxColsPerLane * 64];
   __shared__ float sstat[4][2];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -84,7 +102,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   const int r_end = min(B, (blockIdx.x + 1) * rows_per_block);
   for (int r = blockIdx.x * rows_per_block + w; r < r_end; r += 4) {
     const bf16_t* row = logits + (size_t)r * ld;
-    const int lab = (int)labels[r];
+    int lab = 0;
+    if constexpr (!SOFT) lab = (int)labels[r];
     float xv[kMaxColsPerLane];
     float mx = -INFINITY;
     int amax = 0x7fffffff;
@@ -97,6 +116,27 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
         if (xv[t] > mx) { mx = xv[t]; amax = c; }
       }
     }
+    float qv[SOFT ? kMaxColsPerLane : 1];  // q' = conf q + epsc (0 beyond C)
+    if constexpr (SOFT) {
+      const float* qrow = q + (size_t)r * ldq;
+      float qm = -INFINITY;
+      int qa = 0x7fffffff;
+#pragma unroll
+      for (int t = 0; t < kMaxColsPerLane; ++t) {
+        const int c = lane + 64 * t;
+        qv[t] = 0.f;
+        if (t < nt && c < C) {
+          const float v = qrow[c];
+          if (v > qm) { qm = v; qa = c; }
+          qv[t] = conf * v + epsc;
+        }
+      }
+      // the targets' first-index argmax stands in for the label
+      const float wqm = wave_max(qm);
+      lab = (qm == wqm) ? qa : 0x7fffffff;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lab = min(lab, __shfl_xor(lab, o, 64));
+    }
     // wave argmax (first index of the max)
     const float wmx = wave_max(mx);
     int cand = (mx == wmx) ? amax : 0x7fffffff;
@@ -108,21 +148,29 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
       const int c = lane + 64 * t;
       if (t < nt && c < C) {
         se += __expf(xv[t] - wmx);
-        if (c == lab) xl = xv[t];
-        if constexpr (SMOOTH) sx += xv[t];
+        if constexpr (SOFT) {
+          xl += qv[t] * xv[t];  // sum q' x
+          sx += qv[t];          // s = sum q'
+        } else {
+          if (c == lab) xl = xv[t];
+          if constexpr (SMOOTH) sx += xv[t];
+        }
       }
     }
     se = wave_sum(se);
     xl = wave_sum(xl);
-    if constexpr (SMOOTH) sx = wave_sum(sx);
+    if constexpr (SMOOTH || SOFT) sx = wave_sum(sx);
     const float lse = wmx + __logf(se);
-    const float inv = 1.f / se;
+    float inv = 1.f / se;
+    if constexpr (SOFT) inv *= sx;
 #pragma unroll
     for (int t = 0; t < kMaxColsPerLane; ++t) {
       const int c = lane + 64 * t;
       if (t < nt && c < ld) {
         float g = 0.f;
-        if constexpr (SMOOTH) {
+        if constexpr (SOFT) {
+          if (c < C) g = (__expf(xv[t] - wmx) * inv - qv[t]) * grad_scale;
+        } else if constexpr (SMOOTH) {
           if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
         } else {
           if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
@@ -133,7 +181,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
       }
     }
     if (lane == 0) {
-      if constexpr (SMOOTH) loss_sum += lse - conf * xl - epsc * sx;
+      if constexpr (SOFT) loss_sum += sx * lse - xl;
+      else if constexpr (SMOOTH) loss_sum += lse - conf * xl - epsc * sx;
       else loss_sum += lse - xl;
       correct += (cand == lab) ? 1.f : 0.f;
     }
@@ -167,12 +216,14 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
 // so a 4096-row batch is one load round trip instead of a chain of wave
 // shuffles per row.  Column sums for the bias gradient: per-column wave
 // reduction, then one atomic per column per wave.
-template <int LD, bool SMOOTH>
+template <int LD, int MODE>
 __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict__ logits,
                                                         const int64_t* __restrict__ labels,
                                                         bf16_t* __restrict__ dlogits, float* __restrict__ stats,
                                                         float* __restrict__ dbias, int B, int C, int ld,
-                                                        float grad_scale, XentFin fin, float conf, float epsc) {
+                                                        float grad_scale, XentFin fin, float conf, float epsc,
+                                                        const float* __restrict__ q, int ldq, bool qvec) {
+  constexpr bool SMOOTH = MODE == XM_SMOOTH, SOFT = MODE == XM_SOFT;
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool ok = r < B;
   float x[LD];
@@ -188,16 +239,45 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[v * 8 + j] = bf2f(q[j]);
     }
-    const int lab = (int)labels[r];
+    int lab = 0;
+    if constexpr (!SOFT) lab = (int)labels[r];
     float mx = -INFINITY;
     int am = 0;
 #pragma unroll
     for (int c = 0; c < LD; ++c)
       if (c < C && x[c] > mx) { mx = x[c]; am = c; }
     float se = 0.f, xl = 0.f, sx = 0.f;
+    float qv[SOFT ? LD : 1];  // q' = conf q + epsc (0 beyond C)
+    if constexpr (SOFT) {
+      const float* qrow = q + (size_t)r * ldq;
 #pragma unroll
-    for (int c = 0; c < LD; ++c)
-      if (c == lab) xl = x[c];
+      for (int v = 0; v < LD / 4; ++v) {
+        floatx4 t = {0.f, 0.f, 0.f, 0.f};
+        if (qvec && 4 * v + 3 < C) {
+          t = reinterpret_cast<const floatx4*>(qrow)[v];
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (4 * v + j < C) t[j] = qrow[4 * v + j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) qv[4 * v + j] = t[j];
+      }
+      float qm = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < LD; ++c) {
+        if (c < C) {
+          if (qv[c] > qm) { qm = qv[c]; lab = c; }  // first-index argmax of the raw targets
+          qv[c] = conf * qv[c] + epsc;
+          sx += qv[c];          // s = sum q'
+          xl += qv[c] * x[c];   // sum q' x
+        }
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < LD; ++c)
+        if (c == lab) xl = x[c];
+    }
 #pragma unroll
     for (int c = 0; c < LD; ++c) {
       if (c < C) {
@@ -206,15 +286,19 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
         se += x[c];
       }
     }
-    if constexpr (SMOOTH) loss = mx + __logf(se) - conf * xl - epsc * sx;
+    if constexpr (SOFT) loss = sx * (mx + __logf(se)) - xl;
+    else if constexpr (SMOOTH) loss = mx + __logf(se) - conf * xl - epsc * sx;
     else loss = mx + __logf(se) - xl;  // = logsumexp - x_label
     correct = (am == lab) ? 1.f : 0.f;
-    const float inv = 1.f / se;
+    float inv = 1.f / se;
+    if constexpr (SOFT) inv *= sx;
     u16x8 out[LD / 8];
 #pragma unroll
     for (int c = 0; c < LD; ++c) {
       float v = 0.f;
-      if constexpr (SMOOTH) {
+      if constexpr (SOFT) {
+        if (c < C) v = (x[c] * inv - qv[c]) * grad_scale;
+      } else if constexpr (SMOOTH) {
         if (c < C) v = (x[c] * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
       } else {
         if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
@@ -253,19 +337,21 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
   xent_finish(fin, stats);
 }
 
-template <bool SMOOTH>
+template <int MODE>
 hipError_t launch_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats, float* dbias,
                        int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin& fin, float conf,
-                       float epsc) {
+                       float epsc, const float* q = nullptr, int ldq = 0) {
+  // 16-B target loads in the rows kernel (XM_SOFT only)
+  const bool qvec = (ldq % 4 == 0) && (reinterpret_cast<uintptr_t>(q) & 15) == 0;
   const bool vec_ok = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
   if (vec_ok && ld <= 64) {
     const int g = (B + 255) / 256;
     switch (ld) {
 #define XENT_ROWS_CASE(L) \
-      case L: xent_rows_kernel<L, SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc); break;
+      case L: xent_rows_kernel<L, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec); break;
       XENT_ROWS_CASE(8) XENT_ROWS_CASE(16) XENT_ROWS_CASE(24) XENT_ROWS_CASE(32) XENT_ROWS_CASE(40) XENT_ROWS_CASE(48) XENT_ROWS_CASE(56)
 #undef XENT_ROWS_CASE
-      default: xent_rows_kernel<64, SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc); break;
+      default: xent_rows_kernel<64, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec); break;
     }
     return hipGetLastError();
   }
@@ -273,7 +359,7 @@ hipError_t launch_xent(const uint16_t* logits, const int64_t* labels, uint16_t* 
   // instead of 4 waves walking 16 rows each), 16 rows per block beyond
   const int rpb = B <= 4 * 256 ? 4 : kRowsPerBlock;
   const int g = (B + rpb - 1) / rpb;
-  xent_kernel<SMOOTH><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin, conf, epsc);
+  xent_kernel<MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin, conf, epsc, q, ldq);
   return hipGetLastError();
 }
 
@@ -289,9 +375,22 @@ hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t*
   if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
   if (B <= 0) return hipSuccess;
   if (label_smoothing == 0.f)
-    return launch_xent<false>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f, 0.f);
-  return launch_xent<true>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f - label_smoothing,
+    return launch_xent<XM_PLAIN>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f, 0.f);
+  return launch_xent<XM_SMOOTH>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin, 1.f - label_smoothing,
                            label_smoothing / (float)C);
+}
+
+hipError_t softmax_xent_soft(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,
+                             float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin* finp,
+                             float label_smoothing) {
+  if (ld > kMaxColsPerLane * 64 || C > ld || C < 1 || ldq < C || q == nullptr) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return hipErrorInvalidValue;  // (NaN too)
+  const XentFin fin = finp ? *finp : XentFin{};
+  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
+  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  return launch_xent<XM_SOFT>(logits, nullptr, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin,
+                              1.f - label_smoothing, label_smoothing / (float)C, q, ldq);
 }
 
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s) {

@@ -60,11 +60,13 @@ class DeviceLoader:
     permutation.  On a GPU with a uint8 dataset each batch is ONE native launch
     (augment.hip): gather + optional AutoAugment / flip+crop + normalise + cast.
     The augmentation draws are counter hashes of (seed, epoch, batch, sample):
-    reproducible, and identical on the CPU path (data/autoaugment.py)."""
+    reproducible, and identical on the CPU path (data/autoaugment.py).  ``mix`` (a
+    data.mix.BatchMix) adds one cross-sample pass per batch, Mixup or CutMix, drawn from
+    the same per-batch seed: batches are then (mixed image, class probabilities)."""
 
     def __init__(self, dataset: ArrayDataset, indices, batch_size: int, device, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, mean=None, std=None, dtype=torch.float32,
-                 augment=False, pad: int = 4):
+                 augment=False, pad: int = 4, mix=None):
         self.dataset = dataset
         self.device = torch.device(device)
         self.batch_size = int(batch_size)
@@ -73,6 +75,13 @@ class DeviceLoader:
         self.augment = augment
         self.mode = augment_mode(augment)
         self.pad = int(pad)
+        # data.mix.BatchMix: every batch is then (x_mixed, q [B, num_classes] fp32), also the
+        # batches its `prob` draw leaves unmixed (one-hot q), so the target's dtype and shape
+        # never change within an epoch
+        if mix is not None and mix.num_classes is None:
+            mix = mix.with_classes(dataset.num_classes)
+        self.mix = mix
+        self.mix_lams: list = []   # lam of every plan drawn so far (host data; the trainer's record)
         self.images = _resident(dataset.images, self.device)
         self.labels = _resident(dataset.labels, self.device)
         idx = np.arange(len(dataset)) if indices is None else np.asarray(indices, dtype=np.int64)
@@ -107,6 +116,14 @@ class DeviceLoader:
         n = len(self.indices_np)
         return (n // self.batch_size) * self.batch_size if self.drop_last else n
 
+    def pop_mix_lam_mean(self):
+        """Mean lam of the plans drawn since the last call (None without ``mix``; 1.0 when no
+        batch was drawn), and forget them: host data, no device sync."""
+        if self.mix is None:
+            return None
+        lams, self.mix_lams = self.mix_lams, []
+        return float(np.mean(lams)) if lams else 1.0
+
     def _batch(self, idx: torch.Tensor, seed: int = 0):
         if self._native:
             _, C, H, W = self.images.shape
@@ -132,7 +149,13 @@ class DeviceLoader:
         n = len(order)
         end = (n // bs) * bs if self.drop_last else n
         for k, s in enumerate(range(0, end, bs)):
-            yield self._batch(order[s: s + bs], AA.batch_seed(self.seed, epoch, k) if self.mode else 0)
+            seed = AA.batch_seed(self.seed, epoch, k) if (self.mode or self.mix is not None) else 0
+            x, y = self._batch(order[s: s + bs], seed if self.mode else 0)
+            if self.mix is not None:
+                plan = self.mix.plan(seed, x.shape[0], x.shape[2], x.shape[3])
+                self.mix_lams.append(plan.lam)
+                x, y = self.mix.apply(x, y, plan)
+            yield x, y
 
 
 AA_MAX_PIXELS = 28 * 1024   # csrc kAugMaxPixels
@@ -209,11 +232,13 @@ def estimate_epoch_duration(trainloader, world_size, model, device, num_batches:
 def get_loaders(batch_size, world_size, rank, model, device, fixed_ratio=None, *, dataset: str = "cifar10",
                 comm=None, seed: int = 0, val_fraction: float = 0.2, partition_rule: str = "reference_duration",
                 probe_batches: int = 10, n_train: int | None = None, n_test: int | None = None,
-                dtype=torch.float32, augment=False, data_root: str = "data", augment_val: bool = False):
+                dtype=torch.float32, augment=False, data_root: str = "data", augment_val: bool = False,
+                mix=None):
     """Build (train, val, test) loaders for this rank (BAR/dataloader.py:9-51).
 
     Returns the reference's 7-tuple (IID) or 8-tuple (+fixed_classes) when
-    ``fixed_ratio`` is given (class-skewed, DAR/dataloader.py:9-52)."""
+    ``fixed_ratio`` is given (class-skewed, DAR/dataloader.py:9-52).  ``mix`` (a BatchMix)
+    goes to the train loader only: validation, test and the throughput probe never mix."""
     full, testset = build_dataset(dataset, n_train, n_test, seed=seed, root=data_root)
     mean, std = channel_stats(full)
     full.mean, full.std = mean, std
@@ -239,7 +264,7 @@ def get_loaders(batch_size, world_size, rank, model, device, fixed_ratio=None, *
                                                   trainset.num_classes, rng)
         val_indices, _ = P.skewed_partition(valset.targets, shares, rank, fixed_ratio, valset.num_classes, rng)
     train_loader = DeviceLoader(trainset, train_indices, batch_size, device, dtype=dtype, augment=augment,
-                                seed=(seed * 1_000_003 + rank * 10_007) & 0x7FFFFFFF)
+                                seed=(seed * 1_000_003 + rank * 10_007) & 0x7FFFFFFF, mix=mix)
     val_loader = DeviceLoader(valset, val_indices, batch_size, device, dtype=dtype,
                               augment=augment if augment_val else False, seed=(seed * 7 + rank * 13 + 5) & 0x7FFFFFFF)
     test_loader = DeviceLoader(testset, None, batch_size, device, dtype=dtype)
@@ -250,8 +275,9 @@ def get_loaders(batch_size, world_size, rank, model, device, fixed_ratio=None, *
 def get_subset_loaders(trainset, valset, train_indices, val_indices, batch_size, prev_fraction, next_fraction,
                        share, device, rng: np.random.Generator, replace: bool = False, fixed_classes=None,
                        fixed_ratio=None, dtype=torch.float32, augment=False, loader_seed: int = 0,
-                       augment_val: bool = False):
-    """Re-partition for the next global epoch (BAR/dataloader.py:107-117)."""
+                       augment_val: bool = False, mix=None):
+    """Re-partition for the next global epoch (BAR/dataloader.py:107-117); ``mix`` goes to
+    the train loader only."""
     kw = {}
     if fixed_classes is not None:
         kw = dict(fixed_classes=fixed_classes, fixed_ratio=fixed_ratio)
@@ -259,6 +285,6 @@ def get_subset_loaders(trainset, valset, train_indices, val_indices, batch_size,
                           labels=trainset.targets if kw else None, **kw)
     va = P.next_partition(len(valset), val_indices, share, prev_fraction, next_fraction, rng, replace,
                           labels=valset.targets if kw else None, **kw)
-    return (DeviceLoader(trainset, tr, batch_size, device, dtype=dtype, augment=augment, seed=loader_seed),
+    return (DeviceLoader(trainset, tr, batch_size, device, dtype=dtype, augment=augment, seed=loader_seed, mix=mix),
             DeviceLoader(valset, va, batch_size, device, dtype=dtype, augment=augment if augment_val else False,
                          seed=(loader_seed * 31 + 7) & 0x7FFFFFFF), tr, va)

@@ -49,8 +49,9 @@ class Flatten(nn.Flatten):
 class CrossEntropyLoss(nn.CrossEntropyLoss):
     """Mean cross-entropy (the reference's criterion, BAR/main.py:52) on the fused
     softmax-xent kernel.  Pass ``stats`` to accumulate loss-sum / #correct on device.
-    ``label_smoothing`` is torch's; class weights, ``ignore_index`` and the sum / none
-    reductions are not implemented and refused."""
+    ``label_smoothing`` is torch's, and so is the dispatch on the target: integer class
+    indices [B] or floating class probabilities [B, C] (Mixup / CutMix, distillation).  Class
+    weights, ``ignore_index`` and the sum / none reductions are not implemented and refused."""
 
     def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
                  reduction: str = "mean", label_smoothing: float = 0.0):

@@ -215,8 +215,15 @@ class _SoftmaxXentNative(torch.autograd.Function):
         # one launch: the kernel's last block writes [mean loss, #correct] into `out`
         # and adds [loss sum, #correct] into `stats` (no fill / divide / add kernels)
         out = torch.empty(2, dtype=torch.float32, device=lg.device)
-        C.softmax_xent(lg, labels, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
-                       label_smoothing=label_smoothing)
+        if labels.dim() == 2:   # class-probability targets (validated by cross_entropy): no gradient for them
+            q = labels if labels.dtype == torch.float32 else labels.float()
+            if q.stride(1) != 1:
+                q = q.contiguous()
+            C.softmax_xent_soft(lg, q, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
+                                label_smoothing=label_smoothing)
+        else:
+            C.softmax_xent(lg, labels, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
+                           label_smoothing=label_smoothing)
         ctx.save_for_backward(dfull)
         ctx.n, ctx.in_dtype = n, logits.dtype
         return out[0]
@@ -242,22 +249,42 @@ class _SoftmaxXentNative(torch.autograd.Function):
         return d, None, None, None
 
 
+def _soft_target(logits, target) -> bool:
+    """torch's dispatch on the target: an integer [B] tensor holds class indices (False), a
+    floating [B, C] tensor class probabilities (True); anything else is refused."""
+    if not target.is_floating_point() and not target.is_complex() and target.dim() == 1:
+        return False
+    if logits.dim() == 2 and target.is_floating_point() and target.shape == logits.shape:
+        if target.requires_grad:
+            raise ValueError("cross_entropy: class-probability targets get no gradient; detach the target")
+        return True
+    raise ValueError(f"cross_entropy: logits {tuple(logits.shape)} ({logits.dtype}) take class indices "
+                     f"[{logits.shape[0]}] (integer) or class probabilities {tuple(logits.shape)} (floating), "
+                     f"got a target {tuple(target.shape)} ({target.dtype})")
+
+
 def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoothing: float = 0.0):
     """Mean softmax cross-entropy.  `stats` (device fp32, >= 2) accumulates
     [sum of per-sample loss, #correct] without a host sync.  `label_smoothing` in [0, 1]:
     torch's smoothed targets eps / C + (1 - eps) * onehot (the loss, its gradient and the
-    accumulated loss sum are the smoothed ones; #correct is unaffected)."""
+    accumulated loss sum are the smoothed ones; #correct is unaffected).
+
+    The target is dispatched as torch does: an integer [B] tensor holds class indices, a
+    floating [B, C] tensor class probabilities (rows are not normalised; smoothing applies to
+    them too).  Under probability targets #correct counts the rows whose logits' argmax is the
+    target row's (first-index) argmax: agreement with the dominant label."""
     label_smoothing = float(label_smoothing)
     if not 0.0 <= label_smoothing <= 1.0:
         raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    soft = _soft_target(logits, labels)
     if _ext.use_native(logits):
         return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing)
     lf = logits.float()
-    loss = F.cross_entropy(lf, labels, label_smoothing=label_smoothing)
+    loss = F.cross_entropy(lf, labels.float() if soft else labels, label_smoothing=label_smoothing)
     if stats is not None:
         with torch.no_grad():
-            stats[0] += loss.detach() * labels.numel()
-            stats[1] += (lf.argmax(1) == labels).sum()
+            stats[0] += loss.detach() * labels.shape[0]
+            stats[1] += (lf.argmax(1) == (labels.argmax(1) if soft else labels)).sum()
     return loss
 
 

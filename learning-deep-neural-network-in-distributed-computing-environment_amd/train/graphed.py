@@ -210,7 +210,9 @@ class GraphedStep:
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """One training step on (x, y); returns the (device) loss tensor of this step."""
-        if x.shape != self.x.shape or y.shape != self.y.shape:
+        # (a target of another shape or dtype -- hard labels given to a step captured with class
+        # probabilities, say -- runs eagerly: staging must never convert it into the static buffer)
+        if x.shape != self.x.shape or y.shape != self.y.shape or y.dtype != self.y.dtype:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
         self._stage_x(x, y, self.y)
@@ -519,7 +521,9 @@ class GraphedDPStep:
         self.stats.zero_()
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        if x.shape != self.x.shape or y.shape != self.y.shape:
+        # (a target of another shape or dtype -- hard labels given to a step captured with class
+        # probabilities, say -- runs eagerly: staging must never convert it into the static buffer)
+        if x.shape != self.x.shape or y.shape != self.y.shape or y.dtype != self.y.dtype:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
         self._stage_x(x, y, self.y)

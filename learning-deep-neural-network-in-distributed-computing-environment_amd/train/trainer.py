@@ -114,14 +114,14 @@ def train_local_epoch(model, trainloader, criterion, optimizer, device, schedule
             last = (x, y)
             scale = 1.0
             if weigh_last and i == nb - 1:
-                scale = weight_of(y.numel())
+                scale = weight_of(y.shape[0])
             if use_graph and scale == 1.0 and (i > 0 or getattr(model, "_ldnn_graphed", None) is not None):
                 # the first batch ran eagerly (momentum / optimizer state exist), so the
                 # capture needs no extra warmup steps and training semantics are unchanged
                 gs = _graphed_step(model, criterion, optimizer, x, y, dp)
                 if x.shape == gs.x.shape:
                     losses[i] = gs(x, y).detach().float()
-                    total += y.numel()
+                    total += y.shape[0]
                     done += 1
                     if cutoff is not None:
                         cutoff.step(i)
@@ -148,7 +148,7 @@ def train_local_epoch(model, trainloader, criterion, optimizer, device, schedule
             with tm.phase("optimizer"):
                 optimizer.step()
             losses[i] = loss.detach().float()
-            total += y.numel()
+            total += y.shape[0]
             done += 1
             if cutoff is not None:
                 cutoff.step(i)
@@ -157,7 +157,7 @@ def train_local_epoch(model, trainloader, criterion, optimizer, device, schedule
         if dp_tail and last is not None:
             nxt = pending if pending is not None else next(it, None)
             x, y = nxt if nxt is not None else last
-            n = y.numel() if nxt is not None else 0
+            n = y.shape[0] if nxt is not None else 0
             scale = weight_of(n)
             if n:
                 optimizer.zero_grad()
@@ -333,6 +333,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
         cutoff.reset()
         max_steps = None
         dp_tail = False
+        epoch_loader = trainloader   # (re-partitioning replaces it before the epoch's record is written)
         if sync_every == "step" and N > 1 or getattr(model, "engine", None) is not None and model.engine.distributed:
             # per-step collectives need the same number of steps on every rank
             nsteps = model.full_batches(trainloader) if hasattr(model, "full_batches") else len(trainloader)
@@ -442,7 +443,10 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                 trainset, valset, indices_train, indices_val, batch_size, prev_fraction, next_fraction, share, dev,
                 rng, replace, fixed_classes, fixed_ratio, dtype=dtype,
                 augment=getattr(trainloader, "augment", False), augment_val=bool(getattr(val_loader, "mode", 0)),
-                loader_seed=loader_seed(seed, rank, global_epoch + 1))
+                loader_seed=loader_seed(seed, rank, global_epoch + 1), mix=getattr(trainloader, "mix", None))
+        # batch mixing: the mean lam of this epoch's plans on this rank (host data, no sync)
+        lam_mean = getattr(epoch_loader, "pop_mix_lam_mean", lambda: None)()
+        mix_rec = {} if lam_mean is None else {"mix_lam_mean": lam_mean}
         if logger is not None:
             # gradient clipping counters: device scalars, read once per global epoch
             clip_stats = getattr(optimizer, "grad_clip_stats", lambda: None)()
@@ -476,7 +480,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                        samples_per_s=total_samples / max(duration, 1e-12),
                        train_samples_per_s_per_rank=[s_ / max(duration, 1e-12) for s_ in samples_per_rank],
                        **({"scaling_efficiency": total_samples / max(duration, 1e-12) / (N * ref_samples_per_s)}
-                          if ref_samples_per_s else {}), **clip_rec)
+                          if ref_samples_per_s else {}), **clip_rec, **mix_rec)
         if checkpointer is not None:
             checkpointer.save(global_epoch + 1, model, optimizer, scheduler, H,
                               extra=dict(indices_train=np.asarray(indices_train),

@@ -53,6 +53,11 @@ def main():
     ap.add_argument("--ema_decay", type=float, default=0.0,
                     help="ema_decay of the ldnn optimizer (the weight-EMA pass behind every update; 0 = off); the "
                          "stock baseline keeps no average")
+    ap.add_argument("--targets", choices=["hard", "soft", "mix"], default="hard",
+                    help="ldnn step: hard = class indices; soft = a pre-mixed batch's class-probability targets "
+                         "[B, C] (the loss kernel's soft-target instance); mix = soft plus the batch-mix pass "
+                         "(mix.hip, alternating Mixup / CutMix plans) in front of every step.  The stock baseline "
+                         "keeps hard labels")
     a = ap.parse_args()
     from ldnn.ops import _ext as _e
 
@@ -83,16 +88,39 @@ def main():
         crit(m(xb), y).backward()
         opt.step()
 
+    feed = lambda: (xb, y)   # noqa: E731
+    if a.targets != "hard":
+        from ldnn.data.mix import BatchMix
+
+        mix = BatchMix(0.2, 1.0, num_classes=nc)
+        plans = [mix.plan(s, a.batch, shape[1], shape[2]) for s in range(16)]
+        perms = [torch.as_tensor(p.perm, device="cuda") for p in plans]
+        pre = mix.apply(xb, y, plans[0])
+        k = [0]
+
+        def feed():  # noqa: F811
+            if a.targets == "soft":
+                return pre
+            k[0] = (k[0] + 1) % len(plans)
+            from ldnn.data.mix import mix_native
+            return mix_native(xb, y, perms[k[0]], plans[k[0]], nc)
+
+        def step_ldnn():  # noqa: F811
+            xm, q = feed()
+            opt.zero_grad()
+            crit(m(xm), q).backward()
+            opt.step()
+
     if a.graph:
         from ldnn.train.graphed import GraphedStep
 
-        gs = GraphedStep(m, crit, opt, xb, y)
+        gs = GraphedStep(m, crit, opt, *feed())
 
         def step_ldnn():  # noqa: F811
-            gs(xb, y)
+            gs(*feed())
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]

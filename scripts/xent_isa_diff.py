@@ -4,8 +4,10 @@
           --cuda-device-only -S <pkg>/csrc/kernels/xent.hip -o new.s      (same on the older tree: old.s)
     python scripts/xent_isa_diff.py old.s new.s
 
-Pairs every xent kernel of old.s with the instance of new.s that has the same leading template
-arguments and SMOOTH = false, and compares their instruction streams: comments dropped, the
+Pairs every plain xent kernel of old.s with the plain instance of new.s that has the same leading
+template arguments (the mode is a trailing `bool SMOOTH` in older trees, an `int MODE` -- 0 plain,
+1 smoothed, 2 soft targets -- since the soft-target instances; with a smoothed old.s the smoothed
+instances are paired too), and compares their instruction streams: comments dropped, the
 function number of local labels (.LBB<fn>_<n>) and the kernels' own symbol names normalised.
 Two scalar loads that differ only in their constant offset are counted apart: appended kernel
 arguments move the hidden ones (block / grid size) behind them in the kernel-argument segment.
@@ -39,13 +41,15 @@ def kernels(path):
 
 
 def key(name):
-    """('rows', LD) / ('wave',) / None, and the SMOOTH flag (None: a tree without it)."""
-    m = re.search(r"xent_rows_kernelILi(\d+)(?:ELb([01]))?EE", name)
+    """('rows', LD) / ('wave',) / None, and the mode: 0 plain, 1 smoothed, 2 soft targets (None: a
+    tree with plain kernels only)."""
+    m = re.search(r"xent_rows_kernelILi(\d+)(?:ELb([01])|ELi(\d+))?EE", name)
     if m:
-        return ("rows", int(m.group(1))), (None if m.group(2) is None else m.group(2) == "1")
-    m = re.search(r"\d+xent_kernel(?:ILb([01])EE)?", name)
+        return ("rows", int(m.group(1))), (None if m.group(2) is None and m.group(3) is None
+                                           else int(m.group(2) or m.group(3)))
+    m = re.search(r"\d+xent_kernel(?:ILb([01])EE|ILi(\d+)EE)?", name)
     if m:
-        return ("wave",), (None if m.group(1) is None else m.group(1) == "1")
+        return ("wave",), (None if m.group(1) is None and m.group(2) is None else int(m.group(1) or m.group(2)))
     return None, None
 
 
@@ -59,13 +63,22 @@ def offset_only(x, y):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    olds = {key(n)[0]: b for n, b in old.items() if key(n)[0] is not None}
-    plain = {key(n)[0]: b for n, b in new.items() if key(n)[0] is not None and not key(n)[1]}
-    smooth = {key(n)[0]: b for n, b in new.items() if key(n)[1]}
+    def by_mode(ks, modes):
+        return {key(n)[0]: b for n, b in ks.items() if key(n)[0] is not None and key(n)[1] in modes}
+
+    plain, smooth, soft = by_mode(new, (None, 0)), by_mode(new, (1,)), by_mode(new, (2,))
+    bad = 0
+    bad += compare(by_mode(old, (None, 0)), plain, smooth, soft, "SMOOTH=false")
+    if by_mode(old, (1,)):
+        bad += compare(by_mode(old, (1,)), smooth, {}, {}, "SMOOTH=true")
+    return 1 if bad else 0
+
+
+def compare(olds, plain, smooth, soft, what):
     bad = 0
     for k in sorted(olds):
         a, b = olds[k], plain.get(k)
-        tag = "_".join(str(v) for v in k)
+        tag = "_".join(str(v) for v in k) + ("" if what == "SMOOTH=false" else "_smooth")
         if b is None:
             print(f"{tag}: missing from {sys.argv[2]}")
             bad += 1
@@ -75,10 +88,12 @@ def main():
         diff = len(pairs) - offs + abs(len(a) - len(b))
         bad += diff != 0
         s = smooth.get(k)
-        print(f"{tag}: old {len(a)} instructions, new SMOOTH=false {len(b)}, kernel-argument offsets moved in "
+        t = soft.get(k)
+        print(f"{tag}: old {len(a)} instructions, new {what} {len(b)}, kernel-argument offsets moved in "
               f"{offs}, otherwise differing {diff}: {'IDENTICAL' if diff == 0 else 'DIFFERENT'}"
-              + (f"; SMOOTH=true {len(s)} instructions ({len(s) - len(b):+d})" if s is not None else ""))
-    return 1 if bad else 0
+              + (f"; SMOOTH=true {len(s)} instructions ({len(s) - len(b):+d})" if s is not None else "")
+              + (f"; soft targets {len(t)} instructions ({len(t) - len(b):+d})" if t is not None else ""))
+    return bad
 
 
 if __name__ == "__main__":
