@@ -100,6 +100,25 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ema_no_warmup", action="store_true",
                    help="--ema_decay: use d from the first step on instead of d_t = min(d, (1 + c) / (10 + c)) after "
                         "c updates")
+    p.add_argument("--lr_schedule", type=str, default="none", choices=["none", "constant", "linear", "poly", "cosine"],
+                   help="per-step learning-rate schedule inside the fused optimizer: a linear warm-up over "
+                        "--warmup_steps, then constant, polynomial (linear: power 1) or cosine decay to "
+                        "--lr_min_ratio at --lr_total_steps.  It multiplies the rate StepLR leaves (--step_size / "
+                        "--gamma keep running per local epoch), counts only steps that updated the weights, and "
+                        "replays from the hipGraphs without a host write.  metrics.jsonl then logs lr_last / "
+                        "lr_sched_steps per global epoch; none (default) = off")
+    p.add_argument("--warmup_steps", type=int, default=0, help="--lr_schedule: linear warm-up steps")
+    p.add_argument("--warmup_start", type=float, default=0.0,
+                   help="--lr_schedule: the warm-up runs from this fraction of the rate (step u of W uses "
+                        "start + (1 - start) * u / W)")
+    p.add_argument("--lr_total_steps", type=int, default=None,
+                   help="--lr_schedule: the horizon in optimizer steps (default: global epochs x local epochs x the "
+                        "initial train loader's length, printed at start; with --sync_every step on several ranks the "
+                        "ranks agree on the steps a local epoch runs -- the shortest loader's, plus the tail step "
+                        "when a rank holds more -- so that every rank schedules alike)")
+    p.add_argument("--lr_min_ratio", type=float, default=0.0,
+                   help="--lr_schedule: the floor of the decay, as a fraction of the rate")
+    p.add_argument("--lr_power", type=float, default=2.0, help="--lr_schedule poly: the power")
     p.add_argument("--step_size", type=int, default=25, help="StepLR step (local epochs), BAR/main.py:54")
     p.add_argument("--gamma", type=float, default=0.1)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
@@ -218,13 +237,57 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0:
         # the static engine's head kernels take hard labels
         why = "--mixup / --cutmix runs on the autograd path"
+    elif getattr(args, "lr_schedule", "none") != "none":
+        # the static engine's optimizer epilogue takes its rate from the host
+        why = "--lr_schedule runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
 
 
+def schedule_from_args(args, default_total: int):
+    """The optimizers' ``lr_schedule`` dict of the --lr_schedule flags (None: off), checked as the
+    optimizers check it: a refusal exits naming the flags.  ``default_total`` stands in for an
+    --lr_total_steps that was not given."""
+    if args.lr_schedule == "none":
+        return None
+    from .optim import check_lr_schedule
+
+    given = args.lr_total_steps is not None
+    sched = dict(kind=args.lr_schedule, total_steps=int(args.lr_total_steps if given else default_total),
+                 warmup_steps=args.warmup_steps, warmup_start=args.warmup_start, min_ratio=args.lr_min_ratio,
+                 power=args.lr_power)
+    try:
+        return check_lr_schedule(sched)
+    except ValueError as e:
+        msg = str(e).replace("lr_schedule:", "--lr_schedule:").replace("total_steps", "--lr_total_steps") \
+            .replace("warmup_steps", "--warmup_steps")
+        if not given:
+            msg += f" (--lr_total_steps was not given: the default horizon of this run is {default_total} steps)"
+        raise SystemExit(msg)
+
+
+def default_total_steps(args, n_batches: int, comm, world: int, dev) -> int:
+    """The horizon --lr_total_steps defaults to: global epochs x local epochs x the steps one local
+    epoch over the initial train loader runs.  Under per-step synchronisation on several ranks the
+    shards, and so the loaders' lengths, differ between ranks, while every rank must run each
+    lock-step update at the same rate: the ranks agree on the count the trainer will run (the
+    shortest loader's, plus the one weighted tail step when a rank holds more), with the one
+    all-reduce the trainer itself uses.  Under the global-epoch schedule each rank keeps its own."""
+    if args.sync_every == "step" and world > 1:
+        from .parallel.comm import MIN
+
+        t = torch.tensor([float(n_batches), -float(n_batches)], device=dev)
+        comm.all_reduce(t, MIN)
+        lo, hi = int(t[0].item()), -int(t[1].item())
+        n_batches = lo + (1 if hi > lo else 0)
+    return args.epochs_global * args.epochs_local * n_batches
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    # (the flags' own limits, before any process group or data exists; the default horizon comes later)
+    schedule_from_args(args, max(args.warmup_steps, 0) + 1)
     if not 0.0 <= args.label_smoothing <= 1.0:
         raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
     if not 0.0 <= args.ema_decay < 1.0:
@@ -319,10 +382,15 @@ def main(argv=None):
 
     criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     if not use_engine:
+        lr_schedule = None
+        if args.lr_schedule != "none":    # (every rank enters: the default horizon may take a collective)
+            lr_schedule = schedule_from_args(args, default_total_steps(args, len(train_loader), comm, world, dev))
+        if lr_schedule is not None and not args.quiet:
+            print(f"[rank {rank}] lr schedule {lr_schedule}")
         optimizer = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
                                     max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,
                                     ema_decay=args.ema_decay if args.ema_decay > 0 else None,
-                                    ema_warmup=not args.ema_no_warmup,
+                                    ema_warmup=not args.ema_no_warmup, lr_schedule=lr_schedule,
                                     **(dict(lars_trust=args.lars_trust, lars_eps=args.lars_eps,
                                             lars_exclude_1d=not args.lars_adapt_1d)
                                        if args.optimizer == "lars" else

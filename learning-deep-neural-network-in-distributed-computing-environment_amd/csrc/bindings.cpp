@@ -1117,6 +1117,16 @@ void ema_begin(const at::Tensor& hdr, const c10::optional<at::Tensor>& clip) {
   check(ldnn::ema_begin(h, cur_stream(hdr), clip_ptr(clip, hdr)), "ema_begin");
 }
 
+// this step's learning rate into hp[0] from the schedule's header (ldnn_kernels.h SchedSlot)
+void lr_sched(const at::Tensor& hdr, const at::Tensor& hp, const c10::optional<at::Tensor>& clip) {
+  check_dev(hdr, at::kFloat, "hdr");
+  TORCH_CHECK(hdr.is_contiguous() && hdr.numel() >= ldnn::kSchedState,
+              "lr_sched: hdr must be a contiguous fp32 header of ", (int)ldnn::kSchedState, " elements");
+  hp_ptr("lr_sched", hp, hdr);
+  check(ldnn::lr_sched(hdr.data_ptr<float>(), hp.data_ptr<float>(), cur_stream(hdr), clip_ptr(clip, hdr)),
+        "lr_sched");
+}
+
 // (f32_bufs would name all four refusals in one message; these name the one that failed)
 int64_t ema_bufs(const char* fn, const at::Tensor& master, const at::Tensor& ema) {
   check_dev(master, at::kFloat, "master");
@@ -2377,6 +2387,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
   m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
+  m.def("lr_sched", &lr_sched, "learning-rate schedule, once per step: hp[0] = base * s(t + 1), the factor and the "
+        "step count into hdr (nothing on a skipped step)", py::arg("hdr"), py::arg("hp"), py::arg("clip") = py::none());
   m.def("ema_begin", &ema_begin, "weight EMA, once per step: a_t and the update count into hdr (not on a skipped step)",
         py::arg("hdr"), py::arg("clip") = py::none());
   m.def("ema_update", &ema_update, "ema += a_t * (master - ema), a_t read from hdr", py::arg("master"),

@@ -451,6 +451,22 @@ enum EmaSlot : int {
   kEmaAlpha = 3,    // a_t of the running step; 0 on a skipped step
   kEmaState = 4,
 };
+// The per-step learning-rate schedule's device header (fp32; the function is further down): kind and
+// the constants are WRITTEN BY THE HOST like the lr (a captured graph follows a change), base is
+// param_groups[0]["lr"] (StepLR's product), the count and the factor are lr_sched's.  The count is
+// fp32 (exact to 2^24).
+enum SchedSlot : int {
+  kSchedKind = 0,    // 0 constant, 1 poly (linear: power 1), 2 cosine (host)
+  kSchedWarmup = 1,  // W: warm-up steps (host)
+  kSchedStart = 2,   // ws: warm-up start factor (host)
+  kSchedTotal = 3,   // T: horizon, > W (host)
+  kSchedMin = 4,     // m: floor (host)
+  kSchedPower = 5,   // q: poly's power (host)
+  kSchedBase = 6,    // base rate (host)
+  kSchedSteps = 7,   // t: non-skipped steps done so far
+  kSchedFactor = 8,  // s(t + 1) of the last non-skipped step
+  kSchedState = 9,
+};
 // workgroups (= partial slots) a grad_sumsq launch over n elements uses under the current grid cap
 int grad_sumsq_parts(int64_t n);
 // partials[slot0 + b] = sum of squares workgroup b saw of grad[0, n) (any element alignment; no
@@ -511,6 +527,15 @@ hipError_t lamb_moments(const float* master, const float* grad, float* m, float*
 hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v, uint16_t* shadow, const float* hp,
                       LambParams lp, int64_t n, const float* ratio, const uint16_t* map, hipStream_t s,
                       const float* clip = nullptr);
+
+// ---- per-step learning-rate schedule (header: SchedSlot above) ----
+// Once per step, one thread, before any update reads hp[0].  With u = t + 1:
+//   u <= W:  s = ws + (1 - ws) * (u / W)                       (the last warm-up step: exactly 1)
+//   else     p = min(1, (u - W) / (T - W)) and
+//            constant: s = 1;  poly: s = m + (1 - m) * (1 - p)^q;  cosine: s = m + (1 - m) * (1 + cos(pi p)) / 2
+// then hp[0] = base * s, hdr[kSchedFactor] = s and t += 1.  With clip[kClipSkip] set nothing is written:
+// every update instance returns on that flag, and the step is not counted.
+hipError_t lr_sched(float* hdr, float* hp, hipStream_t s, const float* clip = nullptr);
 
 // ---- exponential moving average of the weights, e += a_t * (w - e) (header: EmaSlot above) ----
 // Once per step, one thread: a_t = 1 - d, with warm-up max(1 - d, 9 / (10 + c)) (the decay ramps as

@@ -602,6 +602,31 @@ __global__ void ema_swap_kernel(float* __restrict__ master, float* __restrict__ 
   }
 }
 
+// ---- per-step learning-rate schedule: this step's rate into hp[0], where every update reads it ----
+// One thread, once per step, behind the norms' finalize (the skip flag is known) and before any
+// update.  A skipped step writes nothing: the updates return on the flag, and t counts the steps
+// that changed the weights.
+template <bool CLIP>
+__global__ void lr_sched_kernel(float* hdr, float* hp, ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) return;
+  }
+  const float t = hdr[kSchedSteps], u = t + 1.f;
+  const float W = hdr[kSchedWarmup], m = hdr[kSchedMin];
+  const int kind = (int)hdr[kSchedKind];
+  float s = 1.f;
+  if (u <= W) {
+    const float ws = hdr[kSchedStart];
+    s = ws + (1.f - ws) * (u / W);
+  } else if (kind != 0) {
+    const float p = fminf(1.f, (u - W) / (hdr[kSchedTotal] - W));
+    s = m + (1.f - m) * (kind == 1 ? powf(1.f - p, hdr[kSchedPower]) : 0.5f * (1.f + cospif(p)));
+  }
+  hp[0] = hdr[kSchedBase] * s;
+  hdr[kSchedFactor] = s;
+  hdr[kSchedSteps] = u;
+}
+
 int g_opt_max_blocks = 2048;  // optimizer grid cap (set_opt_max_blocks: a narrow side-stream update)
 
 inline int grid_for(int64_t n4) {
@@ -742,6 +767,11 @@ hipError_t lamb_apply(float* param, float* grad, const float* m, const float* v,
   with_clip(clip, [&](auto ca) {
     lamb_apply_kernel<ca.on><<<grid_for(n / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, lp, n, ratio, map, ca);
   });
+  return hipGetLastError();
+}
+
+hipError_t lr_sched(float* hdr, float* hp, hipStream_t s, const float* clip) {
+  with_clip(clip, [&](auto ca) { lr_sched_kernel<ca.on><<<1, 1, 0, s>>>(hdr, hp, ca); });
   return hipGetLastError();
 }
 

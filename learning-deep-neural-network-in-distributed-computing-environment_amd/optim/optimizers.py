@@ -63,11 +63,35 @@ its own master, the jump at an aggregation included.  A graph captured with the 
 averages until it is captured again; one captured with it on keeps averaging (with the last decay
 written) after ``ema_decay`` is set to None.  Padding and alignment gaps are averaged like everything
 else: zero in the master, they stay zero.
+
+``lr_schedule`` (default None = off; every optimizer, ``build_optimizer(lr_schedule=)``) is a per-step
+schedule: a plain dict ``{"kind": "constant" | "linear" | "poly" | "cosine", "total_steps": T,
+"warmup_steps": W = 0, "warmup_start": ws = 0, "min_ratio": m = 0, "power": q = 2}``, checked at
+construction and the same in every param group.  With ``t`` non-skipped steps done and ``u = t + 1``
+the step about to run uses ``param_groups[0]["lr"] * s(u)`` -- ``StepLR`` or the user still move the
+base, and the two multiply: ``s = ws + (1 - ws) * u / W`` while ``u <= W`` (the last warm-up step runs
+at exactly the base); after it, with ``p = min(1, (u - W) / (T - W))``, ``constant``: 1, ``poly``:
+``m + (1 - m) * (1 - p)^q`` (``linear``: q = 1), ``cosine``: ``m + (1 - m) * (1 + cos(pi p)) / 2``; beyond
+the horizon ``m``.  On the flat GPU path the constants, the base, ``t`` and the last factor live in a
+small device header (``sched_hdr``; the host writes constants and base only when one changed) and
+``lr_sched``, a one-thread launch in ``_FlatStep.finalize`` behind the norms and before any update,
+writes this step's rate into ``hp[0]``: the eager, range, sharded and graphed steps schedule in the
+stream and graph link of their updates, a replay needs no host write, and a step the non-finite guard
+skips is not counted -- the next one runs at the rate the skipped one would have had.  Sharded
+per-step data parallelism needs no collective: every rank sees the same skip flag and computes the same
+``t`` (the ranks must be given the same dict: the CLI agrees its default horizon across them); under the weighted mix or gossip each rank counts its own non-skipped steps.  On the CPU, for
+loose tensors and with several param groups (each group's own rate times the one factor) the same
+math runs on the host in Python floats.  ``state_dict()`` saves ``sched_steps`` (a checkpoint without
+it starts at 0), ``lr_schedule_stats()`` reports count, factor and rate.  The count is an fp32 device
+scalar (exact to 2**24; longer horizons are refused).  A graph captured with the schedule off never
+schedules until it is captured again; one captured with it on keeps its ``lr_sched`` (with the last
+constants written, still following the base) after ``lr_schedule`` is set to None.
 """
 from __future__ import annotations
 
 import contextlib
 import math
+import numbers
 
 import torch
 
@@ -90,15 +114,21 @@ def _refuse_partial_sharded(params):
 # slots of the clipping state tensor (csrc/include/ldnn_kernels.h ClipSlot)
 _CLIP_MAX, _CLIP_COEF, _CLIP_SKIP, _CLIP_NORM, _CLIP_STEPS, _CLIP_CLIPPED, _CLIP_SKIPPED, _CLIP_LEN = 0, 1, 2, 3, 4, 5, 6, 8
 # device-only entries of _ls(): rebuilt by an eager step, never saved
-_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb", "ema_hdr")
+_TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb", "ema_hdr", "sched_hdr", "sched_written",
+              "sched_last")
 # slots of the weight EMA's header (csrc/include/ldnn_kernels.h EmaSlot)
 _EMA_DECAY, _EMA_WARMUP, _EMA_UPDATES, _EMA_ALPHA, _EMA_LEN = 0, 1, 2, 3, 4
+# slots of the learning-rate schedule's header (csrc/include/ldnn_kernels.h SchedSlot): the first six
+# are ``_sched_consts``' tuple
+_SCHED_BASE, _SCHED_STEPS, _SCHED_FACTOR, _SCHED_LEN = 6, 7, 8, 9
+_SCHED_KINDS = {"constant": 0, "poly": 1, "linear": 1, "cosine": 2}
+_SCHED_KEYS = ("kind", "total_steps", "warmup_steps", "warmup_start", "min_ratio", "power")
 # LARS ratio table: one slot per uint16 map value, so every map entry is in bounds; the slots
 # past the segments are never written and hold 1 (alignment gaps map to the last one)
 _LARS_SLOTS, _LARS_GAP = 65536, 65535
 _CAPTURE_MSG = "run an eager optimizer step before capturing it into a graph"
 # lengths of the fp32 device vectors of _ls() (clip_scratch: as many slots as the ranges need)
-_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1, "ema_hdr": _EMA_LEN}
+_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1, "ema_hdr": _EMA_LEN, "sched_hdr": _SCHED_LEN}
 
 
 def _graph_state(store: dict, key, capturing: bool, make):
@@ -292,6 +322,77 @@ def _ema_update_torch(e, w, hdr):
     e.add_((w - e).mul_(hdr[_EMA_ALPHA].to(e.device)))
 
 
+def _whole(what, v):
+    """``v`` as an int when it is a whole, finite number (no bool, no string); else a ValueError."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or v in (float("inf"), -float("inf")) \
+            or v != int(v):
+        raise ValueError(f"lr_schedule: {what} must be a whole number; got {v!r}")
+    return int(v)
+
+
+def _real(what, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        raise ValueError(f"lr_schedule: {what} must be a number; got {v!r}")
+    return float(v)
+
+
+def _sched_consts(sched):
+    """Validate an ``lr_schedule`` dict (every refusal is a ValueError); returns the header constants
+    ``(kind code, W, ws, T, m, q)`` (``linear``: poly with q = 1; ``constant`` needs no horizon)."""
+    if not isinstance(sched, dict):
+        raise ValueError(f"lr_schedule must be None (off) or a dict with the keys {_SCHED_KEYS}; got {sched!r}")
+    bad = set(sched) - set(_SCHED_KEYS)
+    if bad:
+        raise ValueError(f"lr_schedule: unknown keys {sorted(bad, key=str)} (known: {_SCHED_KEYS})")
+    kind = sched.get("kind")
+    if not isinstance(kind, str) or kind not in _SCHED_KINDS:
+        raise ValueError(f"lr_schedule: kind must be one of {sorted(_SCHED_KINDS)}; got {kind!r}")
+
+    def get(key, default):
+        return default if sched.get(key) is None else sched[key]
+
+    W = _whole("warmup_steps", get("warmup_steps", 0))
+    ws, m = _real("warmup_start", get("warmup_start", 0.0)), _real("min_ratio", get("min_ratio", 0.0))
+    q = 1.0 if kind == "linear" else _real("power", get("power", 2.0))
+    if W < 0:
+        raise ValueError(f"lr_schedule: warmup_steps must be a whole number >= 0; got {W}")
+    T = get("total_steps", W + 1 if kind == "constant" else None)
+    if T is None:
+        raise ValueError(f"lr_schedule: {kind!r} needs total_steps (> warmup_steps = {W})")
+    T = _whole("total_steps", T)
+    if T <= W:
+        raise ValueError(f"lr_schedule: total_steps must be a whole number > warmup_steps ({W}); got {T}")
+    if not 0.0 <= ws <= 1.0 or not 0.0 <= m <= 1.0:
+        raise ValueError(f"lr_schedule: warmup_start and min_ratio must lie in [0, 1]; got {ws}, {m}")
+    if not q > 0 or q == float("inf"):
+        raise ValueError(f"lr_schedule: power must be positive and finite; got {q}")
+    if T >= 2 ** 24:
+        raise ValueError(f"lr_schedule: total_steps {T} exceeds the fp32 step count (2**24)")
+    return float(_SCHED_KINDS[kind]), float(W), ws, float(T), m, q
+
+
+def check_lr_schedule(sched):
+    """Validate an ``lr_schedule`` value the way the optimizers' constructors do (ValueError on any
+    refusal); returns None for None, else a plain copy of the dict."""
+    if sched is None:
+        return None
+    _sched_consts(sched)
+    return dict(sched)
+
+
+def lr_schedule_factor(sched, u):
+    """The schedule's factor ``s(u)`` of step ``u`` = 1, 2, ... in Python floats (what the CPU and
+    loose-tensor paths use; ``lr_sched`` is the same expression in fp32).  ``sched``: an
+    ``lr_schedule`` dict, or ``_sched_consts``' tuple."""
+    kind, W, ws, T, m, q = sched if isinstance(sched, tuple) else _sched_consts(sched)
+    if u <= W:
+        return ws + (1.0 - ws) * (u / W)
+    if kind == 0:
+        return 1.0
+    p = min(1.0, (u - W) / (T - W))
+    return m + (1.0 - m) * ((1.0 - p) ** q if kind == 1 else 0.5 * (1.0 + math.cos(math.pi * p)))
+
+
 class _FlatStep:
     """ONE optimizer step of one flat buffer ``f``, as the stages every driver runs in this order:
 
@@ -322,6 +423,12 @@ class _FlatStep:
     ``ema_begin`` (this step's a_t and the count; a skipped step gets a_t = 0) and ``update(lo, hi)``
     issues ``ema_update`` on the same range right behind the optimizer's launch.
 
+    The learning-rate schedule rides on ``finalize`` too, behind the norms (the skip flag is known)
+    and before the optimizer's prologue and any ``update``: natively ``lr_sched`` turns the header
+    ``sched_hdr`` into this step's ``hp[0]``; on the torch paths ``lr`` (what ``_update_torch`` uses)
+    becomes ``group["lr"] * s`` in Python floats.  ``sched``: the factor of a schedule stepped
+    outside (several groups / loose tensors), already in ``lr``.
+
     The stages hand their results on in the object, so the order is a precondition: when the
     step takes a norm (``normed``: its own clipping, or LARS), ``norm`` comes before ``finalize``;
     ``finalize`` comes before any ``update``.  With neither, ``norm`` may be left out."""
@@ -329,10 +436,12 @@ class _FlatStep:
     # what a plain step (no clipping, no LARS) never sets
     own_clip = normed = False
     cl = skip = L = M = hp = local = local2 = tab = mtab = sumsq = ctx = ema = ema_hdr = None
+    sched_hdr = sched_host = None
     ranges, counted, nparts = (), (), 0
 
-    def __init__(self, opt, f, group, clip=None, sharded=False):
+    def __init__(self, opt, f, group, clip=None, sharded=False, sched=None):
         self.opt, self.f, self.group = opt, f, group
+        self.lr = group["lr"] if sched is None else group["lr"] * sched
         opt._refuse_inside_ema("an optimizer step")
         self.st = st = opt._ls()
         self.native = native = _ext.use_native(f.master)
@@ -348,10 +457,16 @@ class _FlatStep:
         if native:
             hp = st.get("hp")
             self.hp = hp if hp is not None and hp.device == dev else opt._state("hp", dev)
+        if sched is None:
+            conf = opt._sched_conf()
+            if conf is not None and native:
+                self.sched_hdr = opt._state("sched_hdr", dev)
+            else:
+                self.sched_host = conf
         if not opt._ldnn_capturing:
             # inside a hipGraph capture the writes are NOT recorded: the graph reads the tensors,
             # and GraphedStep refreshes them (sync_hyperparams) whenever a value changes
-            opt._write_hyperparams(group["lr"], (thr, lars))
+            opt._write_hyperparams(self.lr, (thr, lars))
 
     def _norm_state(self, clip, thr, lars, dev, sharded):
         opt = self.opt
@@ -411,6 +526,10 @@ class _FlatStep:
         else straight from ``norm``'s partials (LARS's are taken here: nothing waited for them)."""
         if self.normed:
             self._finalize_norms(reduced)
+        if self.sched_hdr is not None:
+            _ext.C().lr_sched(self.sched_hdr, self.hp, clip=self.cl)
+        elif self.sched_host is not None:
+            self.lr = self.group["lr"] * self.opt._host_sched(self.sched_host, self.group["lr"], bool(self.skip))
         if not self.skip:
             self.ctx = self.opt._begin_ranges(self)
         if self.ema is not None:
@@ -544,6 +663,10 @@ class _RangeStep(_FlatStep):
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._sched_conf()    # (a schedule given per param group: checked, and the same in all)
+
     def _ls(self) -> dict:
         """Fused (flat-buffer) optimizer state: momentum / moments / step / hp (+ the
         clipping state and scratch)."""
@@ -559,6 +682,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if "ema_hdr" in ls:
             # ... and so does the EMA's update count (load_state_dict hands it to the next header)
             flat["ema_updates"] = int(ls["ema_hdr"][_EMA_UPDATES].item())
+        if "sched_hdr" in ls:
+            # ... and the schedule's count of non-skipped steps (the host paths keep it in ``ls``)
+            flat["sched_steps"] = int(ls["sched_hdr"][_SCHED_STEPS].item())
         sd["ldnn_flat_state"] = flat
         return sd
 
@@ -569,7 +695,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """The fp32 device vector ``key`` of ``_ls()``, at least ``n`` long: ``hp`` [lr, Adam's
         step count], ``clip`` [max_norm, coef, skip, last_norm, steps, clipped, skipped, -],
         ``clip_scratch`` (grad_sumsq's partial slots), ``clip_local`` (the 1-element local sum),
-        ``ema_hdr`` [decay, warm-up flag, EMA updates, last a_t]."""
+        ``ema_hdr`` [decay, warm-up flag, EMA updates, last a_t], ``sched_hdr`` [kind, W, ws, T, m,
+        q, base, steps, last factor]."""
         st = self._ls()
         t = st.get(key)
         n = n or _STATE_LEN[key]
@@ -579,6 +706,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 t[1] = float(st.get("step", 0))
             elif key == "ema_hdr":
                 t[_EMA_UPDATES] = float(st.get("ema_updates", 0))
+            elif key == "sched_hdr":
+                t[_SCHED_STEPS] = float(st.get("sched_steps", 0))
         return t
 
     def _trust_state(self, key, excl, flat, params=None, device=None):
@@ -612,12 +741,27 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _write_hyperparams(self, lr=None, conf=None):
         """Write the learning rate, the clipping threshold, LARS's trust coefficient and eps and the
-        EMA's decay and warm-up flag into whichever of their device tensors exist.  ``conf``:
+        EMA's decay and warm-up flag into whichever of their device tensors exist; with a schedule's
+        header the rate goes there as the base (``lr_sched`` writes ``hp[0]``).  ``conf``:
         ``(_clip_threshold(), _lars_conf())`` where the caller has them already."""
         st = self._ls()
         hp, cl, L, eh = st.get("hp"), st.get("clip"), st.get("lars"), st.get("ema_hdr")
-        if hp is not None:
-            hp[0].fill_(self.param_groups[0]["lr"] if lr is None else lr)
+        lr = self.param_groups[0]["lr"] if lr is None else lr
+        sh = st.get("sched_hdr")
+        sched = self._sched_conf() if sh is not None else None
+        if sh is not None:
+            # the schedule's constants and base rate: only the slots whose value changed (all of a new
+            # header), so a scheduled step whose base stands issues no host write at all.  (Switched
+            # off after a capture: the captured lr_sched keeps the last constants and follows the base.)
+            last = st.get("sched_written")
+            old = last[1] if last is not None and last[0] is sh else (None,) * (_SCHED_BASE + 1)
+            vals = (sched if sched is not None else old[:_SCHED_BASE]) + (float(lr),)
+            for i, (v, o) in enumerate(zip(vals, old)):
+                if v != o and v is not None:
+                    sh[i].fill_(v)
+            st["sched_written"] = (sh, vals)
+        if hp is not None and sched is None:
+            hp[0].fill_(lr)
         if eh is not None:
             ema = self._ema_conf()
             if ema is not None:    # (switched off after a capture: the captured kernels keep the last decay)
@@ -637,7 +781,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def sync_hyperparams(self):
         """Write the current learning rate (and clipping threshold, LARS trust coefficient and
-        eps, EMA decay and warm-up flag) into the device hyper-parameter tensors."""
+        eps, EMA decay and warm-up flag, the schedule's constants and base rate) into the device
+        hyper-parameter tensors."""
         self._write_hyperparams()
 
     def _buf(self, name, like):
@@ -858,6 +1003,51 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._ldnn_in_ema = False
             swap()
 
+    # ---- per-step learning-rate schedule -------------------------------------------------
+    _check_schedule = staticmethod(check_lr_schedule)
+
+    def _sched_conf(self):
+        """``_sched_consts`` of the schedule, or None when it is off.  One schedule for the whole
+        optimizer; the key is read with .get, so state saved before it existed loads."""
+        sched = self._same_in_groups(lambda g: g.get("lr_schedule"),
+                                     "lr_schedule must be the same in every param group")
+        if sched is None:
+            return None
+        # (validated once per value: a step, a sync and a stats call only compare the dict)
+        seen = self.__dict__.get("_ldnn_sched_seen")
+        if seen is None or seen[0] != sched:
+            self._ldnn_sched_seen = seen = (dict(sched), _sched_consts(sched))
+        return seen[1]
+
+    def _host_sched(self, conf, base, skip):
+        """One step of the schedule on the host (CPU, loose tensors, several groups): the factor of
+        the step about to run; the count ``sched_steps`` advances unless the step is skipped."""
+        st = self._ls()
+        hdr = st.pop("sched_hdr", None)
+        if hdr is not None:     # (the buffer moved off the native path: its device count comes along)
+            st["sched_steps"] = int(hdr[_SCHED_STEPS].item())
+            st.pop("sched_written", None)
+        if skip:
+            return st.get("sched_last", (0.0, 0.0))[0]
+        t = st.get("sched_steps", 0)
+        s = lr_schedule_factor(conf, t + 1)
+        st["sched_steps"], st["sched_last"] = t + 1, (s, base * s)
+        return s
+
+    def lr_schedule_stats(self):
+        """The scalars ``steps`` (non-skipped steps the schedule has counted), ``factor`` and ``lr``
+        (the last non-skipped step's ``s`` and rate; 0 before the first) -- on the fused path device
+        scalars, reading one syncs -- or None when the schedule is off."""
+        if self._sched_conf() is None:
+            return None
+        st = self._ls()
+        hdr, hp = st.get("sched_hdr"), st.get("hp")
+        if hdr is not None and hp is not None:
+            return {"steps": hdr[_SCHED_STEPS], "factor": hdr[_SCHED_FACTOR], "lr": hp[0]}
+        s, lr = st.get("sched_last", (0.0, 0.0))
+        return {"steps": torch.tensor(float(st.get("sched_steps", 0))), "factor": torch.tensor(s, dtype=torch.float64),
+                "lr": torch.tensor(lr, dtype=torch.float64)}
+
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         flat_state = state_dict.pop("ldnn_flat_state", {})
@@ -894,7 +1084,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._refuse_inside_ema("step()")
         groups = self.param_groups
         flats = [self._flat_for_group(g) for g in groups]
-        clip = None
+        clip = sched = None
         loose_ema = None     # the EMA over loose tensors (a flat buffer's rides on its _FlatStep)
         if self._ema_conf() is not None and self._ema_flat() is None:
             loose_ema = self._loose_ema_begin()
@@ -904,11 +1094,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
             if self._clip_threshold() is not None:
                 clip = self._loose_clip(flats)
             self._lars_conf()
+            # ... and one schedule step on the host for all of them (a single flat buffer's rides
+            # on its _FlatStep), each group's own rate times the factor
+            conf = self._sched_conf()
+            if conf is not None and groups:
+                sched = self._host_sched(conf, groups[0]["lr"], clip is not None and clip[1])
         loose = {}           # what the per-tensor updates of this step share
         for group, f in zip(groups, flats):
             if f is not None:
-                self._flat_step(f, group, clip, clear_grads)
+                self._flat_step(f, group, clip, clear_grads, sched)
             elif clip is None or not clip[1]:
+                if sched is not None:
+                    group = dict(group, lr=group["lr"] * sched)
                 self._loose_update(group, clip[0] if clip is not None else None, loose)
         if loose_ema is not None:
             ps, hdr = loose_ema
@@ -919,7 +1116,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
                     _ema_update_torch(self.state[p]["ema"], p.data, hdr)
         return loss
 
-    def _flat_step(self, f, group, clip, clear_grads):
+    def _flat_step(self, f, group, clip, clear_grads, sched=None):
         """One ``_FlatStep`` over the whole flat buffer; when DataParallel(shard_optimizer=True)
         owns ``f`` (``f.shard_sync``, a GradBucketer), over this rank's flat ranges (its shard of
         every reduce-scattered bucket + the replicated tail) with ONE all-reduce of ``local``
@@ -932,7 +1129,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             raise RuntimeError("DataParallel(shard_optimizer=True) needs ONE param group holding the whole "
                                f"flat buffer; this optimizer has {len(self.param_groups)}")
         f.finalize_grads()
-        s = _FlatStep(self, f, group, clip, sh is not None)
+        s = _FlatStep(self, f, group, clip, sh is not None, sched)
         if sh is None:
             n = f.numel
             if s.normed:
@@ -1029,14 +1226,14 @@ class SGD(_FlatOptimizer):
 
     def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
                  max_grad_norm=None, lars_trust=None, lars_eps=1e-8, lars_exclude_1d=True, ema_decay=None,
-                 ema_warmup=True):
+                 ema_warmup=True, lr_schedule=None):
         if lars_trust is not None and lars_trust <= 0:
             raise ValueError(f"lars_trust must be positive (None: LARS off); got {lars_trust}")
         self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, max_grad_norm=max_grad_norm, lars_trust=lars_trust,
                                       lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d, ema_decay=ema_decay,
-                                      ema_warmup=ema_warmup))
+                                      ema_warmup=ema_warmup, lr_schedule=self._check_schedule(lr_schedule)))
 
     def _begin_ranges(self, s):
         # (``first`` is host-driven: the very first step seeds the momentum)
@@ -1055,7 +1252,7 @@ class SGD(_FlatOptimizer):
     def _update_torch(self, s, sl, p, g_, ratio):
         g, mu = s.group, s.group["momentum"]
         first, mom = s.ctx
-        self._sgd_torch(p, g_, _cut(sl, mom)[0] if mu != 0 else None, g["lr"], mu, g["dampening"],
+        self._sgd_torch(p, g_, _cut(sl, mom)[0] if mu != 0 else None, s.lr, mu, g["dampening"],
                         g["weight_decay"], g["nesterov"], first, ratio=ratio)
 
     def _loose_update(self, group, cl, loose):
@@ -1112,10 +1309,11 @@ class Adam(_FlatOptimizer):
     decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 ema_decay=None, ema_warmup=True):
+                 ema_decay=None, ema_warmup=True, lr_schedule=None):
         self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup))
+                                      max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                      lr_schedule=self._check_schedule(lr_schedule)))
 
     def _begin_ranges(self, s):
         if s.native:
@@ -1132,7 +1330,7 @@ class Adam(_FlatOptimizer):
     def _update_torch(self, s, sl, p, g_, ratio):
         g = s.group
         m, v = _cut(sl, s.ctx[0], s.ctx[1])
-        self._adam_torch(p, g_, m, v, s.ctx[2], g["lr"], *g["betas"], g["eps"], g["weight_decay"])
+        self._adam_torch(p, g_, m, v, s.ctx[2], s.lr, *g["betas"], g["eps"], g["weight_decay"])
 
     def _loose_state(self, p, cl):
         """The per-tensor step of a loose ``p`` begins: its gradient clipped, its state (exp_avg,
@@ -1171,8 +1369,8 @@ class AdamW(Adam):
     decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 ema_decay=None, ema_warmup=True):
-        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup)
+                 ema_decay=None, ema_warmup=True, lr_schedule=None):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup, lr_schedule)
 
 
 class Lamb(_FlatOptimizer):
@@ -1194,11 +1392,12 @@ class Lamb(_FlatOptimizer):
     Adam's (``exp_avg``, ``exp_avg_sq``, ``step``); ``lamb_stats()`` reports the last ratios."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_grad_norm=None,
-                 lamb_exclude_1d=True, ema_decay=None, ema_warmup=True):
+                 lamb_exclude_1d=True, ema_decay=None, ema_warmup=True, lr_schedule=None):
         self._check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d,
-                                      ema_decay=ema_decay, ema_warmup=ema_warmup))
+                                      ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                      lr_schedule=self._check_schedule(lr_schedule)))
 
     _begin_ranges, _loose_state = Adam._begin_ranges, Adam._loose_state
 
@@ -1220,7 +1419,7 @@ class Lamb(_FlatOptimizer):
         return self._direction(p, m, v, s.ctx[2], *g["betas"], g["eps"], g["weight_decay"])
 
     def _update_torch(self, s, sl, p, g_, ratio):
-        p.sub_(s.group["lr"] * ratio * _cut(sl, s.M.u)[0])
+        p.sub_(s.lr * ratio * _cut(sl, s.M.u)[0])
 
     def _loose_update(self, group, cl, loose):
         lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
@@ -1245,9 +1444,10 @@ class Lamb(_FlatOptimizer):
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     max_grad_norm: float | None = None, ema_decay: float | None = None, ema_warmup: bool = True,
-                    **lars):
+                    lr_schedule: dict | None = None, **lars):
     """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  ema_decay / ema_warmup: the
-    weight EMA of every optimizer (None: off).  "lars": SGD with
+    weight EMA of every optimizer (None: off).  lr_schedule: the per-step schedule of every optimizer
+    (a dict, see the module docstring; None: off).  "lars": SGD with
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
     "sgd" takes them too); Adam and AdamW refuse them.  "lamb": Lamb, which takes
     ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords."""
@@ -1259,7 +1459,7 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     bad = set(lars) - allowed
     if bad:
         raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
-    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
+    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup, lr_schedule=lr_schedule)
     if name == "lamb":
         return Lamb(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema, **lars)
     if name == "lars":

@@ -22,6 +22,11 @@ What makes the ldnn step capturable:
   (so StepLR & co. keep working); the weight EMA's decay travels the same way, and its
   ``ema_begin`` / ``ema_update`` launches are captured with the optimizer's -- a graph
   captured with ``ema_decay=None`` never averages until it is captured again;
+* a per-step ``lr_schedule`` needs no refresh at all: its ``lr_sched`` launch is captured in
+  front of the updates and turns the device header (base rate, constants, step count) into
+  ``hp[0]`` on every replay; the host writes the header only when the base rate (StepLR) or
+  the schedule dict changed -- a graph captured with ``lr_schedule=None`` never schedules
+  until it is captured again;
 * the criterion's label smoothing is a kernel argument of the loss launch, so it IS
   captured: a replay raises when the criterion's value differs from the captured one;
 * every native op writes into caller-provided / caching-allocator tensors
@@ -193,10 +198,10 @@ class GraphedStep:
         return loss
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold, LARS's trust coefficient / eps and the EMA's decay / warm-up flag
-        # travel like the lr: device scalars the captured kernels read)
+        # (the clipping threshold, LARS's trust coefficient / eps, the EMA's decay / warm-up flag and
+        # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
-                g.get("ema_warmup")) for g in self.optimizer.param_groups]
+                g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -496,10 +501,10 @@ class GraphedDPStep:
             self._fire(done)
 
     def _sync_lr(self, force: bool = False):
-        # (the clipping threshold, LARS's trust coefficient / eps and the EMA's decay / warm-up flag
-        # travel like the lr: device scalars the captured kernels read)
+        # (the clipping threshold, LARS's trust coefficient / eps, the EMA's decay / warm-up flag and
+        # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
-                g.get("ema_warmup")) for g in self.optimizer.param_groups]
+                g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()

@@ -472,6 +472,10 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
             ema_stats = getattr(optimizer, "ema_stats", lambda: None)()
             if ema_stats is not None:
                 clip_rec.update(ema_updates=int(ema_stats["updates"]), ema_a_last=float(ema_stats["a_last"]))
+            # learning-rate schedule: the last step's rate and the steps it has counted, likewise
+            sched_stats = getattr(optimizer, "lr_schedule_stats", lambda: None)()
+            if sched_stats is not None:
+                clip_rec.update(lr_last=float(sched_stats["lr"]), lr_sched_steps=int(sched_stats["steps"]))
             logger.log(kind="global_epoch", global_epoch=global_epoch + 1, duration_s=duration,
                        train_loss=H["global_train_losses"][-1], train_acc=H["global_train_accuracies"][-1],
                        val_loss=H["global_val_losses"][-1], val_acc=H["global_val_accuracies"][-1],

@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--ema_decay", type=float, default=0.0,
                     help="ema_decay of the ldnn optimizer (the weight-EMA pass behind every update; 0 = off); the "
                          "stock baseline keeps no average")
+    ap.add_argument("--lr_schedule", choices=["none", "constant", "linear", "poly", "cosine"], default="none",
+                    help="lr_schedule of the ldnn optimizer (the one-thread lr_sched launch in front of the update; "
+                         "10 warm-up steps, horizon 10000); the stock baseline keeps a constant rate")
     ap.add_argument("--targets", choices=["hard", "soft", "mix"], default="hard",
                     help="ldnn step: hard = class indices; soft = a pre-mixed batch's class-probability targets "
                          "[B, C] (the loss kernel's soft-target instance); mix = soft plus the batch-mix pass "
@@ -77,6 +80,8 @@ def main():
         kw["lars_trust"] = a.lars
     if a.ema_decay > 0:
         kw["ema_decay"] = a.ema_decay
+    if a.lr_schedule != "none":
+        kw["lr_schedule"] = dict(kind=a.lr_schedule, total_steps=10000, warmup_steps=10)
     opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
            else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
            else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
@@ -120,7 +125,7 @@ def main():
             gs(*feed())
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "lr_schedule": a.lr_schedule, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
