@@ -25,3 +25,11 @@ def prepare(model, device=None):
     if device is not None:
         model.to(torch.device(device))
     return ensure_flat(model, device)
+
+
+def reseed_dropout(model, seed: int) -> int:
+    """Seed and number the model's Dropout modules and zero their call counts
+    (models.layers.reseed_dropout); returns how many there are."""
+    from .models.layers import reseed_dropout as _reseed
+
+    return _reseed(model, seed)

@@ -79,6 +79,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "0 <= eps <= 1) inside the fused loss kernel; 0 (default) = off.  The same criterion serves "
                         "validation and the final test, so the reported val / test losses are the smoothed ones "
                         "(accuracy is unaffected)")
+    p.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                   help="dropout at rate P (0 <= P < 1; 0 (default) = off, no module is built) after every hidden "
+                        "layer of the MLPs, after LeNet-5's fc1 and fc2, in front of the classifier of the ResNets and "
+                        "EnhancedCNNs, in one native pass each way (dropout.hip) whose mask is a counter hash of "
+                        "(--seed, rank, global epoch, module, step): nothing is stored for the backward, a resumed run "
+                        "replays the masks, and validation and the final test run without it")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
                    help="Mixup of every training batch with a permutation of itself, lam ~ Beta(ALPHA, ALPHA), one "
                         "draw per batch, in one native pass (mix.hip) that also writes the class-probability targets "
@@ -240,6 +246,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "lr_schedule", "none") != "none":
         # the static engine's optimizer epilogue takes its rate from the host
         why = "--lr_schedule runs on the autograd path"
+    elif getattr(args, "dropout", 0.0) > 0:
+        # the static engine's layer chain has no pass between a layer's epilogue and the next GEMM
+        why = "--dropout runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -292,6 +301,8 @@ def main(argv=None):
         raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
+    if not 0.0 <= args.dropout < 1.0:
+        raise SystemExit(f"--dropout must be in [0, 1), got {args.dropout}")
     for flag, v in (("--mixup", args.mixup), ("--cutmix", args.cutmix)):
         if not (v >= 0.0 and math.isfinite(v)):
             raise SystemExit(f"{flag} must be a finite alpha >= 0, got {v}")
@@ -319,7 +330,7 @@ def main(argv=None):
     comm = default_comm(args.oneshot_bytes)
 
     dataset = args.dataset or dataset_for(args.model)
-    model = build_model(args.model)
+    model = build_model(args.model, dropout=args.dropout)
     xavier_init(model)
     use_engine = resolve_engine(args, model, dev, world)
     if use_engine:

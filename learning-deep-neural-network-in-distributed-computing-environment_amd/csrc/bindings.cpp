@@ -336,6 +336,52 @@ void act_bwd(const at::Tensor& dy, const at::Tensor& y, const at::Tensor& dx, in
   check(ldnn::act_bwd(bf16_ptr(dy), bf16_ptr(y), bf16_mut(dx), y.numel(), (int)act, cur_stream(y)), "act_bwd");
 }
 
+// Row stride of a dropout operand: a [R][N] bf16 tensor, inner stride 1, whose storage holds R whole
+// rows of that stride from its first element on (a dense matrix, or the [R][N] view of a padded
+// [R][ld] buffer: the kernels write, and their 16-B loads may read, a row's pad columns).
+int64_t dropout_ld(const at::Tensor& t, const char* name) {
+  check_dev(t, at::kBFloat16, name);
+  const int64_t R = t.size(0), N = t.size(1);
+  int64_t ld = ld_of(t, name);
+  if (R == 1 && ld < N) ld = N;   // (a single row's stride is arbitrary)
+  TORCH_CHECK(N >= 1 && ld >= N, name, ": row stride ", ld, " < ", N, " columns");
+  const int64_t have = (int64_t)(t.storage().nbytes() / 2) - t.storage_offset();
+  TORCH_CHECK(R * ld <= have || (ld == N && t.is_contiguous()), name, ": the storage does not hold ", R,
+              " rows of stride ", ld);
+  return ld;
+}
+
+void dropout_words(const at::Tensor& t, const char* name) {
+  check_dev(t, at::kInt, name);
+  TORCH_CHECK(t.is_contiguous() && t.numel() >= 8, name, " must be 8 contiguous int32 words");
+}
+
+void dropout_fwd(const at::Tensor& x, const at::Tensor& y, const at::Tensor& state, const at::Tensor& ticket) {
+  const int64_t ld_in = dropout_ld(x, "x"), ld_out = dropout_ld(y, "y");
+  dropout_words(state, "state");
+  dropout_words(ticket, "ticket");
+  TORCH_CHECK(x.sizes() == y.sizes() && x.device() == y.device() && state.device() == x.device() &&
+                  ticket.device() == x.device(), "dropout_fwd: shape / device mismatch");
+  TORCH_CHECK(x.data_ptr() != y.data_ptr(), "dropout_fwd: in-place is not supported");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check(ldnn::dropout_fwd(bf16_ptr(x), bf16_mut(y), reinterpret_cast<uint32_t*>(state.data_ptr<int>()),
+                          reinterpret_cast<uint32_t*>(ticket.data_ptr<int>()), x.size(0), x.size(1), ld_in, ld_out,
+                          cur_stream(x)),
+        "dropout_fwd");
+}
+
+void dropout_bwd(const at::Tensor& g, const at::Tensor& dx, const at::Tensor& ticket) {
+  const int64_t ld_in = dropout_ld(g, "g"), ld_out = dropout_ld(dx, "dx");
+  dropout_words(ticket, "ticket");
+  TORCH_CHECK(g.sizes() == dx.sizes() && g.device() == dx.device() && ticket.device() == g.device(),
+              "dropout_bwd: shape / device mismatch");
+  TORCH_CHECK(g.data_ptr() != dx.data_ptr(), "dropout_bwd: in-place is not supported");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(g.device());
+  check(ldnn::dropout_bwd(bf16_ptr(g), bf16_mut(dx), reinterpret_cast<const uint32_t*>(ticket.data_ptr<int>()),
+                          g.size(0), g.size(1), ld_in, ld_out, cur_stream(g)),
+        "dropout_bwd");
+}
+
 // the optional ticketed scratch of colsum / act_bwd_colsum: >= cols + 1 zeroed fp32 (kept zero by the kernel)
 float* colsum_ws(const c10::optional<at::Tensor>& ws, int64_t cols) {
   if (!ws.has_value()) return nullptr;
@@ -2297,6 +2343,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("cnt") = py::none());
   m.def("act_fwd", &act_fwd);
   m.def("act_bwd", &act_bwd);
+  m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("y"), py::arg("state"), py::arg("ticket"),
+        "y = dropout(x) over [R, N] bf16 rows (padded row strides allowed; y's pad columns come back 0); the mask "
+        "is a counter hash of the 8-word int32 device state, the call's key goes into the 8-word ticket and the "
+        "launch advances the state's counter");
+  m.def("dropout_bwd", &dropout_bwd, py::arg("g"), py::arg("dx"), py::arg("ticket"),
+        "dx = the forward's mask and scale applied to g, regenerated from the forward's ticket");
   m.def("colsum", &colsum, py::arg("x"), py::arg("out"), py::arg("accumulate") = false, py::arg("ws") = py::none());
   m.def("act_bwd_colsum", &act_bwd_colsum, py::arg("dy"), py::arg("y"), py::arg("dx"), py::arg("out"),
         py::arg("act"), py::arg("accumulate") = true, py::arg("ws") = py::none());

@@ -303,6 +303,17 @@ hipError_t global_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int HW, i
 enum Act : int { ACT_RELU = 0, ACT_SIGMOID = 1 };
 hipError_t act_fwd(const uint16_t* x, uint16_t* y, int64_t n, int act, hipStream_t s);
 hipError_t act_bwd(const uint16_t* dy, const uint16_t* y, uint16_t* dx, int64_t n, int act, hipStream_t s);
+// Dropout over a logical [R][N] bf16 matrix (row strides ld_in / ld_out >= N), the mask a counter hash
+// of (seed, module, call count, r, c) that the backward regenerates (dropout.hip states the definition,
+// the 8-word device state and the 8-word ticket).  Columns N <= c < ld_out of the output are written
+// as zeros.  16-B accesses where both strides are multiples of 8 and both bases 16-B aligned.  The
+// forward writes the ticket and its last workgroup advances the state's counter; the backward reads the
+// ticket only.  thr == 0 (nothing to drop) is the caller's shortcut in eager calls; a captured launch whose
+// module's rate was set to 0 since still runs, with thr 0 and scale 1 in the state: a copy.
+hipError_t dropout_fwd(const uint16_t* x, uint16_t* y, uint32_t* state, uint32_t* ticket, int64_t R, int64_t N,
+                       int64_t ld_in, int64_t ld_out, hipStream_t s);
+hipError_t dropout_bwd(const uint16_t* g, uint16_t* dx, const uint32_t* ticket, int64_t R, int64_t N, int64_t ld_in,
+                       int64_t ld_out, hipStream_t s);
 // dbias[c] (+)= sum_r x[r][c] over a [rows][cols] bf16 matrix (ld = cols).  ws (optional): a zeroed
 // scratch of cols floats + one int the caller keeps; an overwriting sum over several row groups then
 // runs as ONE launch (ticketed: the last group moves the sums into out and re-zeroes ws)

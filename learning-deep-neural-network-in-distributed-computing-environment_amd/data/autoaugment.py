@@ -112,6 +112,16 @@ def smix(z: int) -> int:
     return z ^ (z >> 31)
 
 
+def smix_np(z: np.ndarray) -> np.ndarray:
+    """``smix`` over a uint64 array (wrapping arithmetic, element for element the same values)."""
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        z = z.astype(np.uint64) + u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+    return z ^ (z >> u(31))
+
+
 def draws(seed: int, b: int) -> dict:
     """Per-sample random choices of sample b of a batch with batch seed `seed`."""
     h0 = smix((seed ^ ((b * 0xD1B54A32D192ED03) & _M64)) & _M64)

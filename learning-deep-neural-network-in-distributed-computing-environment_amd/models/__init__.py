@@ -5,26 +5,29 @@ from __future__ import annotations
 import torch.nn as nn
 
 from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock  # noqa: F401
-from .layers import CrossEntropyLoss, Linear  # noqa: F401
+from .layers import CrossEntropyLoss, Dropout, Linear, reseed_dropout  # noqa: F401
 from .mlp import MLP, mlp2, mlp3  # noqa: F401
 from .resnet import ResNet, resnet18  # noqa: F401
 
 # name -> (constructor, input kind for the synthetic dataset)
 REGISTRY = {
-    "enhanced_cnn": (lambda nc=10: EnhancedCNNModel(nc), "cifar10"),
-    "enhanced_cnn_small": (lambda nc=10: EnhancedCNNSmall(nc), "cifar10"),
-    "lenet5": (lambda nc=10: LeNet5(nc), "mnist"),
-    "mlp2": (lambda nc=10: mlp2(784, 1024, nc), "mnist"),
-    "mlp3": (lambda nc=10: mlp3(784, 4096, nc), "mnist"),
-    "mlp3_small": (lambda nc=10: mlp3(784, 1024, nc), "mnist"),
-    "resnet18": (lambda nc=1000: resnet18(nc), "imagenet"),
-    "resnet18_cifar": (lambda nc=10: resnet18(nc), "cifar10"),
+    "enhanced_cnn": (lambda nc=10, dropout=0.0: EnhancedCNNModel(nc, dropout=dropout), "cifar10"),
+    "enhanced_cnn_small": (lambda nc=10, dropout=0.0: EnhancedCNNSmall(nc, dropout=dropout), "cifar10"),
+    "lenet5": (lambda nc=10, dropout=0.0: LeNet5(nc, dropout=dropout), "mnist"),
+    "mlp2": (lambda nc=10, dropout=0.0: mlp2(784, 1024, nc, dropout=dropout), "mnist"),
+    "mlp3": (lambda nc=10, dropout=0.0: mlp3(784, 4096, nc, dropout=dropout), "mnist"),
+    "mlp3_small": (lambda nc=10, dropout=0.0: mlp3(784, 1024, nc, dropout=dropout), "mnist"),
+    "resnet18": (lambda nc=1000, dropout=0.0: resnet18(nc, dropout=dropout), "imagenet"),
+    "resnet18_cifar": (lambda nc=10, dropout=0.0: resnet18(nc, dropout=dropout), "cifar10"),
 }
 
 
-def build_model(name: str, num_classes: int | None = None) -> nn.Module:
+def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0) -> nn.Module:
+    """``dropout``: the rate of the model's Dropout modules (MLPs: after every hidden layer; LeNet-5:
+    after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist."""
     ctor, _ = REGISTRY[name]
-    return ctor() if num_classes is None else ctor(num_classes)
+    kw = {"dropout": dropout} if dropout else {}
+    return ctor(**kw) if num_classes is None else ctor(num_classes, **kw)
 
 
 def dataset_for(name: str) -> str:

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..ops import functional as LF
-from .layers import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Linear, MaxPool2d, ReLU, pair_conv_bn
+from .layers import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, pair_conv_bn
 
 
 class ConvBNReLU(nn.Sequential):
@@ -65,8 +65,17 @@ class ResBlock(nn.Module):
         return self.bn2.act(self.conv2(out), residual=LF.shortcut_input(x), relu=True)
 
 
+def _head(x, pool, fc, drop=None):
+    """fc(drop(flatten(pool(x)))).  Without an active dropout (none constructed, eval mode or
+    rate 0) that is the fused gap_linear launch; with one, pool -> flatten -> dropout -> fc."""
+    if drop is None or not drop.training or drop.p == 0:
+        return LF.gap_linear(x, pool, fc)   # pool -> view -> fc (one fused launch each way on the GPU)
+    y = pool(x)
+    return fc(drop(y.reshape(y.size(0), -1)))
+
+
 class EnhancedCNNModel(nn.Module):
-    def __init__(self, num_classes: int = 10, in_channels: int = 3):
+    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0):
         super().__init__()
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
@@ -79,6 +88,8 @@ class EnhancedCNNModel(nn.Module):
         self.layer4 = nn.Sequential(ResBlock(512, 1024, stride=2), ResBlock(1024, 1024, stride=1))
         self.pool = AdaptiveAvgPool2d(1)
         self.fc = Linear(1024, num_classes)
+        if dropout:   # (none constructed at rate 0: named_modules() stay the reference's)
+            self.drop = Dropout(dropout)
 
     def forward(self, x):
         x = self.prep(x)
@@ -86,13 +97,13 @@ class EnhancedCNNModel(nn.Module):
         x = self.layer2(x)
         x = self.layer3(x)
         x = self.layer4(x)
-        return LF.gap_linear(x, self.pool, self.fc)   # pool -> view -> fc (one fused launch each way on the GPU)
+        return _head(x, self.pool, self.fc, getattr(self, "drop", None))
 
 
 class EnhancedCNNSmall(nn.Module):
     """The reference's commented-out smaller model (BAR/model.py:4-50)."""
 
-    def __init__(self, num_classes: int = 10, in_channels: int = 3):
+    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0):
         super().__init__()
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
@@ -104,18 +115,20 @@ class EnhancedCNNSmall(nn.Module):
         self.layer3 = ResBlock(256, 512, stride=2)
         self.pool = AdaptiveAvgPool2d(1)
         self.fc = Linear(512, num_classes)
+        if dropout:
+            self.drop = Dropout(dropout)
 
     def forward(self, x):
         x = self.prep(x)
         x = self.layer3(self.layer2(self.layer1(x)))
-        return LF.gap_linear(x, self.pool, self.fc)
+        return _head(x, self.pool, self.fc, getattr(self, "drop", None))
 
 
 class LeNet5(nn.Module):
     """LeNet-5 for 28x28 (MNIST-shaped) input: conv5x5(pad 2)-ReLU-pool, conv5x5-ReLU-pool,
     fc 400-120-84-10 (ReLU activations fused into the Linear epilogues)."""
 
-    def __init__(self, num_classes: int = 10, in_channels: int = 1, pool: str = "max"):
+    def __init__(self, num_classes: int = 10, in_channels: int = 1, pool: str = "max", dropout: float = 0.0):
         super().__init__()
         P = MaxPool2d if pool == "max" else AvgPool2d
         self.features = nn.Sequential(
@@ -129,8 +142,13 @@ class LeNet5(nn.Module):
         self.fc1 = Linear(16 * 5 * 5, 120, activation="relu")
         self.fc2 = Linear(120, 84, activation="relu")
         self.fc3 = Linear(84, num_classes)
+        if dropout:   # after fc1 and after fc2
+            self.drop1 = Dropout(dropout)
+            self.drop2 = Dropout(dropout)
 
     def forward(self, x):
         x = self.features(x)
         x = x.flatten(1)
+        if hasattr(self, "drop1"):
+            return self.fc3(self.drop2(self.fc2(self.drop1(self.fc1(x)))))
         return self.fc3(self.fc2(self.fc1(x)))

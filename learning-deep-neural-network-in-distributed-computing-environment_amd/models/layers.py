@@ -46,6 +46,64 @@ class Flatten(nn.Flatten):
     pass
 
 
+class Dropout(nn.Dropout):
+    """nn.Dropout whose mask is a counter hash of (seed, module_index, call count, element)
+    (``LF.dropout_mask``): one native pass each way on the GPU with no mask stored, the exact twin
+    on the CPU.  The state (``LF.DropoutState``) is created lazily on the input's device and kept
+    in ``__dict__``: it is neither a parameter nor a buffer, so ``state_dict()``, ``buffers()``,
+    broadcasts and averaging never see it.  ``reseed_dropout`` gives it its seed and index; the
+    rate is compared on the host before each call and rewritten into the state when ``p`` changed
+    (``sync_rate`` does the same for a captured step).  Eval mode and ``p == 0`` are the identity."""
+
+    def __init__(self, p: float = 0.5, inplace: bool = False):
+        if inplace:
+            raise ValueError("ldnn Dropout: inplace=True is not supported")
+        super().__init__(p, False)
+        self.__dict__["_ldnn_drop"] = None
+        self.__dict__["_ldnn_drop_seed"] = (0, 0)   # (seed, module_index) of the last reseed
+
+    def _state(self, device):
+        st = self.__dict__["_ldnn_drop"]
+        if st is None or st.words.device != device:
+            st = self.__dict__["_ldnn_drop"] = LF.DropoutState(device, *self.__dict__["_ldnn_drop_seed"])
+        return st
+
+    def reseed(self, seed: int, module_index: int) -> None:
+        self.__dict__["_ldnn_drop_seed"] = (int(seed), int(module_index))
+        if self.__dict__["_ldnn_drop"] is not None:
+            self.__dict__["_ldnn_drop"].reseed(seed, module_index)
+
+    def sync_rate(self) -> None:
+        """Write ``self.p`` into an existing state when it changed (a host compare, no device
+        traffic otherwise): the graphed steps call it before a replay."""
+        st = self.__dict__["_ldnn_drop"]
+        if st is not None:
+            st.set_rate(self.p)   # (p == 0: thr 0 and scale 1, the captured launch becomes a copy)
+
+    def forward(self, x):
+        if self.inplace:
+            raise ValueError("ldnn Dropout: inplace=True is not supported")
+        if not self.training or self.p == 0:
+            return x
+        return LF.dropout(x, self.p, True, self._state(x.device))
+
+
+def dropout_modules(model) -> list:
+    """The model's Dropout modules in ``modules()`` order (through a DataParallel wrapper too)."""
+    return [m for m in model.modules() if isinstance(m, Dropout)]
+
+
+def reseed_dropout(model, seed: int) -> int:
+    """Give the k-th Dropout of ``model.modules()`` the index k and ``seed``, and zero its call
+    count: the masks that follow are a pure function of (seed, k, calls since, element).  Host
+    writes into the modules' persistent states, outside any graph: a captured step follows.
+    Returns the number of Dropout modules."""
+    mods = dropout_modules(model)
+    for k, m in enumerate(mods):
+        m.reseed(seed, k)
+    return len(mods)
+
+
 class CrossEntropyLoss(nn.CrossEntropyLoss):
     """Mean cross-entropy (the reference's criterion, BAR/main.py:52) on the fused
     softmax-xent kernel.  Pass ``stats`` to accumulate loss-sum / #correct on device.

@@ -12,12 +12,12 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from .layers import Linear
+from .layers import Dropout, Linear
 
 
 class MLP(nn.Module):
     def __init__(self, in_features: int = 784, hidden=(4096, 4096), num_classes: int = 10,
-                 activation: str = "relu"):
+                 activation: str = "relu", dropout: float = 0.0):
         super().__init__()
         dims = [in_features, *hidden, num_classes]
         self.in_features = in_features
@@ -27,17 +27,24 @@ class MLP(nn.Module):
             Linear(dims[i], dims[i + 1], activation=activation if i < len(dims) - 2 else "none")
             for i in range(len(dims) - 1)
         )
+        # dropout after every hidden layer's fused activation; none is constructed at rate 0, so
+        # named_modules() and every launch are then those of the model without the keyword
+        if dropout:
+            self.drops = nn.ModuleList(Dropout(dropout) for _ in hidden)
 
     def forward(self, x):
         x = x.flatten(1)
-        for layer in self.layers:
+        drops = getattr(self, "drops", ())
+        for i, layer in enumerate(self.layers):
             x = layer(x)
+            if i < len(drops):
+                x = drops[i](x)
         return x
 
 
-def mlp2(in_features=784, hidden=1024, num_classes=10, activation="relu"):
-    return MLP(in_features, (hidden,), num_classes, activation)
+def mlp2(in_features=784, hidden=1024, num_classes=10, activation="relu", dropout=0.0):
+    return MLP(in_features, (hidden,), num_classes, activation, dropout)
 
 
-def mlp3(in_features=784, hidden=4096, num_classes=10, activation="relu"):
-    return MLP(in_features, (hidden, hidden), num_classes, activation)
+def mlp3(in_features=784, hidden=4096, num_classes=10, activation="relu", dropout=0.0):
+    return MLP(in_features, (hidden, hidden), num_classes, activation, dropout)

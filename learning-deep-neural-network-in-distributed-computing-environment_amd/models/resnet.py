@@ -7,7 +7,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..ops import functional as LF
-from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Linear, MaxPool2d, ReLU, pair_conv_bn
+from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, pair_conv_bn
 
 
 class BasicBlock(nn.Module):
@@ -39,7 +39,7 @@ class BasicBlock(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=1000, in_channels=3, width=64):
+    def __init__(self, layers=(2, 2, 2, 2), num_classes=1000, in_channels=3, width=64, dropout: float = 0.0):
         super().__init__()
         self.inplanes = width
         self.conv1 = Conv2d(in_channels, width, 7, 2, 3, bias=False)
@@ -53,6 +53,8 @@ class ResNet(nn.Module):
         self.layer4 = self._make(width * 8, layers[3], 2)
         self.avgpool = AdaptiveAvgPool2d(1)
         self.fc = Linear(width * 8, num_classes)
+        if dropout:   # timm's drop_rate: in front of the classifier (none constructed at rate 0)
+            self.drop = Dropout(dropout)
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -73,8 +75,10 @@ class ResNet(nn.Module):
         x = LF.bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)   # maxpool(relu(bn1(conv1 x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
+        if hasattr(self, "drop"):
+            x = self.drop(x)
         return self.fc(x)
 
 
-def resnet18(num_classes=1000, in_channels=3):
-    return ResNet((2, 2, 2, 2), num_classes, in_channels)
+def resnet18(num_classes=1000, in_channels=3, dropout=0.0):
+    return ResNet((2, 2, 2, 2), num_classes, in_channels, dropout=dropout)

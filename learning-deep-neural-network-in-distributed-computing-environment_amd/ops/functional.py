@@ -1140,3 +1140,172 @@ def gap_linear(x, pool, fc):
             return _GapLinearNative.apply(x, fc.weight, fc.bias, flat)
     y = pool(x)
     return fc(y.reshape(y.size(0), -1))
+
+
+# -------------------------------------------------------------------- dropout
+_M32, _M64 = (1 << 32) - 1, (1 << 64) - 1
+_DROP_GROUP_MUL = 0xD1B54A32D192ED03
+# words of a DropoutState (int32, the device kernel's layout: csrc/kernels/dropout.hip)
+DROP_SEED_LO, DROP_SEED_HI, DROP_MODULE, DROP_COUNTER, DROP_THR, DROP_SCALE, DROP_ARRIVE = range(7)
+
+
+def _i32(v: int) -> int:
+    """A 32-bit pattern as the signed value an int32 tensor stores."""
+    v &= _M32
+    return v - (1 << 32) if v >> 31 else v
+
+
+def dropout_thr(p: float) -> int:
+    """thr = round(p * 65536) of a drop rate 0 <= p <= 1: the realised rate is thr / 65536."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    return int(round(p * 65536.0))
+
+
+def dropout_scale(thr: int):
+    """The fp32 scale 65536 / (65536 - thr) of the kept elements (0 when everything is dropped)."""
+    import numpy as np
+
+    return np.float32(0.0) if thr >= 65536 else np.float32(65536.0) / np.float32(65536 - thr)
+
+
+def dropout_mask(seed: int, module_index: int, counter: int, thr: int, R: int, N: int):
+    """The exact NumPy twin of the dropout kernels' mask (csrc/kernels/dropout.hip): a bool [R, N]
+    array, True where the element is DROPPED.
+
+    A tensor is seen as [R, N]: N the last logical dimension, R the product of the rest.  Four
+    neighbouring columns of a row share one hash; with G = ceil(N / 4):
+
+        key   = smix(smix(seed64) ^ (module_index << 32 | counter))      all 64-bit, wrapping
+        h     = smix(key ^ ((r * G + (c >> 2)) * 0xD1B54A32D192ED03))
+        bits  = (h >> (16 * (c & 3))) & 0xFFFF
+        drop  = bits < thr        with thr = round(p * 65536), 0 <= thr <= 65536
+        scale = 65536.0f / (65536 - thr)   (fp32; thr == 65536: everything is dropped, output 0)
+        y     = drop ? 0 : bf16_rne(float(x) * scale)        dx = drop ? 0 : bf16_rne(float(g) * scale)
+
+    smix is data/autoaugment.smix (splitmix64's finaliser).  The mask depends on the logical (r, c)
+    only, not on strides, padding or the launch."""
+    import numpy as np
+
+    from ..data.autoaugment import smix, smix_np
+
+    key = smix(smix(int(seed) & _M64) ^ (((int(module_index) & _M32) << 32) | (int(counter) & _M32)))
+    G = (N + 3) // 4
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        grp = np.arange(R * G, dtype=np.uint64) * u(_DROP_GROUP_MUL)
+    h = smix_np(grp ^ u(key)).reshape(R, G)
+    bits = (h[:, :, None] >> (np.arange(4, dtype=np.uint64) * u(16))) & u(0xFFFF)
+    return (bits.reshape(R, 4 * G)[:, :N] < u(thr))
+
+
+class DropoutState:
+    """The persistent state one Dropout module's calls read: 8 int32 words on the module's device
+    (seed low / high, module_index, counter, thr, the scale's fp32 bits, the kernel's arrival
+    count).  The host writes it the way the optimizers write the lr: fills into persistent
+    addresses, outside any captured graph.  The counter is advanced by the forward itself (on the
+    GPU by the launch's last workgroup), so every call, and every replay of a captured call, draws
+    a new mask."""
+
+    def __init__(self, device, seed: int = 0, module_index: int = 0):
+        self.words = torch.zeros(8, dtype=torch.int32, device=device)
+        self.thr = 0   # (with scale 1: a launch before any set_rate copies its input)
+        self.words[DROP_SCALE].fill_(_i32(int(dropout_scale(0).view("uint32"))))
+        self.reseed(seed, module_index)
+
+    def reseed(self, seed: int, module_index: int) -> None:
+        s = int(seed) & _M64
+        w = self.words
+        w[DROP_SEED_LO].fill_(_i32(s))
+        w[DROP_SEED_HI].fill_(_i32(s >> 32))
+        w[DROP_MODULE].fill_(_i32(int(module_index)))
+        w[DROP_COUNTER].fill_(0)
+
+    def set_rate(self, p: float) -> int:
+        """thr of ``p``; rewrites the state's thr and scale only when it differs from the last one."""
+        thr = dropout_thr(p)
+        if thr != self.thr:
+            self.words[DROP_THR].fill_(thr)
+            self.words[DROP_SCALE].fill_(_i32(int(dropout_scale(thr).view("uint32"))))
+            self.thr = thr
+        return thr
+
+    def read(self) -> dict:
+        """The state's words as Python ints (a device read: tests and debugging)."""
+        w = [v & _M32 for v in self.words.tolist()]
+        return dict(seed=w[DROP_SEED_LO] | (w[DROP_SEED_HI] << 32), module_index=w[DROP_MODULE],
+                    counter=w[DROP_COUNTER], thr=w[DROP_THR])
+
+
+def _drop_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as a [R, N] operand of the dropout kernels: itself when it is a 2-D tensor with dense rows
+    whose storage holds every row whole (a dense matrix, or the [B, N] view of a padded [B, npad]
+    buffer an ldnn op handed on), else a dense [numel / N, N] copy."""
+    N = t.shape[-1]
+    if (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= N
+            and t.storage_offset() + t.shape[0] * t.stride(0) <= t.untyped_storage().nbytes() // t.element_size()):
+        return t
+    return t.contiguous().view(-1, N)
+
+
+def _drop_out_like(x2: torch.Tensor) -> torch.Tensor:
+    """The output operand for ``x2``: the [R, N] view of a fresh buffer with x2's row stride."""
+    R, N = x2.shape
+    buf = torch.empty(R, max(x2.stride(0), N), dtype=torch.bfloat16, device=x2.device)
+    return buf if buf.shape[1] == N else buf[:, :N]
+
+
+class _DropoutNative(torch.autograd.Function):
+    """dropout.hip: the forward saves only its 8-word ticket, the backward regenerates the mask."""
+
+    @staticmethod
+    def forward(ctx, x, state):
+        C = _ext.C()
+        x2 = _drop_rows(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
+        y = _drop_out_like(x2)
+        ticket = torch.empty(8, dtype=torch.int32, device=x.device)
+        C.dropout_fwd(x2, y, state.words, ticket)
+        ctx.save_for_backward(ticket)
+        ctx.shape, ctx.in_dtype = x.shape, x.dtype
+        if y.stride(0) != y.shape[1] and x.dim() == 2:
+            y._ldnn_zpad = True   # the kernel wrote the pad columns' zeros
+            return y
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (ticket,) = ctx.saved_tensors
+        g2 = _drop_rows(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16))
+        dx = _drop_out_like(g2)
+        _ext.C().dropout_bwd(g2, dx, ticket)
+        dx = dx if dx.shape == ctx.shape else dx.view(ctx.shape)
+        return (dx if ctx.in_dtype == torch.bfloat16 else dx.to(ctx.in_dtype)), None
+
+
+def dropout(x, p: float = 0.5, training: bool = True, state: DropoutState | None = None):
+    """Inverted dropout whose mask is a pure function of (seed, module_index, call count, element):
+    see ``dropout_mask``.  ``state`` carries seed, module_index and the call count, and is advanced
+    by the call.  On the GPU one native pass each way (no mask is stored: the backward regenerates
+    it); on the CPU the exact twin, so a CPU and a GPU run with equal states drop the same elements.
+    ``p == 0`` or ``training == False`` returns ``x`` itself.
+
+    Dtypes: the native path computes in and returns bf16 whatever the input's dtype, like every
+    native activation op (``relu``, ``linear_act``), and hands the input's dtype back only in the
+    gradient; the CPU path keeps the input's dtype.  On bf16 inputs the two agree bit for bit."""
+    thr = dropout_thr(p)
+    if not training or thr == 0 or x.numel() == 0:
+        return x
+    if state is None:
+        raise ValueError("dropout: a DropoutState is needed in training mode (models.layers.Dropout keeps one)")
+    if state.words.device != x.device:
+        raise ValueError(f"dropout: the state lives on {state.words.device}, the input on {x.device}")
+    state.set_rate(p)
+    if _ext.use_native(x):
+        return _DropoutNative.apply(x, state)
+    s = state.read()
+    N = x.shape[-1]
+    drop = torch.from_numpy(dropout_mask(s["seed"], s["module_index"], s["counter"], thr, x.numel() // N, N))
+    state.words[DROP_COUNTER] = _i32(s["counter"] + 1)
+    drop = drop.view(x.shape).to(x.device)
+    return (x.float() * float(dropout_scale(thr))).to(x.dtype).masked_fill(drop, 0.0)

@@ -29,6 +29,12 @@ What makes the ldnn step capturable:
   until it is captured again;
 * the criterion's label smoothing is a kernel argument of the loss launch, so it IS
   captured: a replay raises when the criterion's value differs from the captured one;
+* dropout (models.layers.Dropout) needs no check: seed, module index, call count and rate live
+  in each module's device state.  The captured ``dropout_fwd`` launch advances the count itself
+  (its last workgroup), so every replay draws the next mask, and the captured ``dropout_bwd``
+  reads the ticket its forward wrote in the same replay; ``reseed_dropout`` writes seed and
+  count from the host between replays, and a changed ``module.p`` is written before a replay
+  like a changed lr (a host compare per module) -- no capture bakes a rate or a seed in;
 * every native op writes into caller-provided / caching-allocator tensors
   (graph-pool allocations during capture).
 
@@ -42,6 +48,7 @@ import os
 
 import torch
 
+from ..models.layers import dropout_modules
 from ..optim.optimizers import _FlatOptimizer
 from .static_mlp import no_gc
 
@@ -155,6 +162,7 @@ class GraphedStep:
         self.y = y_example.detach().clone()
         self.stats = stats if stats is not None else torch.zeros(2, dtype=torch.float32, device=self.x.device)
         self._lrs = None
+        self._dropouts = dropout_modules(self.model)
         # persistent d(loss)/d(loss) = 1: the captured backward needs no seed fill launch, and
         # the loss backward knows it scales by exactly 1 (no scaling pass: _SoftmaxXentNative)
         self._one = unit_seed(self.x.device)
@@ -202,6 +210,8 @@ class GraphedStep:
         # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
                 g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
+        for m in self._dropouts:   # (a changed module.p: written like a changed lr)
+            m.sync_rate()
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()
@@ -295,6 +305,7 @@ class GraphedDPStep:
         self._one = unit_seed(self.x.device)
         self.stats = stats if stats is not None else torch.zeros(2, dtype=torch.float32, device=self.x.device)
         self._lrs = None
+        self._dropouts = dropout_modules(self.model)
         self.device_collectives = bool(getattr(self.comm, "device_collectives", False))
         if mode is None:
             mode = "segmented" if (self.device_collectives or comm_fn is not None) else "after"
@@ -505,6 +516,8 @@ class GraphedDPStep:
         # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
                 g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
+        for m in self._dropouts:   # (a changed module.p: written like a changed lr)
+            m.sync_rate()
         if force or lrs != self._lrs:
             if isinstance(self.optimizer, _FlatOptimizer):
                 self.optimizer.sync_hyperparams()

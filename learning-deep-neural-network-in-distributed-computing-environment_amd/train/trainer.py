@@ -35,6 +35,7 @@ import torch
 
 from ..data.loader import get_subset_loaders
 from ..models.layers import CrossEntropyLoss as LdnnCE
+from ..models.layers import reseed_dropout
 from ..parallel.aggregation import Aggregator
 from ..utils.tracing import PhaseTimer, null_timer, trace_range
 from ..parallel.comm import MAX, MIN, SUM, Comm, default_comm
@@ -331,6 +332,11 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                                   "Global Epochs"):
         t_start = time.perf_counter()
         cutoff.reset()
+        # dropout masks are a pure function of (seed, rank, global epoch, module, step within the epoch):
+        # a resumed run replays them, every rank draws its own, and training-mode passes before the
+        # first epoch (the throughput probe) do not matter.  Host writes, outside the step graphs
+        if isinstance(model, torch.nn.Module):
+            reseed_dropout(model, loader_seed(seed, rank, global_epoch))
         max_steps = None
         dp_tail = False
         epoch_loader = trainloader   # (re-partitioning replaces it before the epoch's record is written)

@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--lr_schedule", choices=["none", "constant", "linear", "poly", "cosine"], default="none",
                     help="lr_schedule of the ldnn optimizer (the one-thread lr_sched launch in front of the update; "
                          "10 warm-up steps, horizon 10000); the stock baseline keeps a constant rate")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="dropout rate of the ldnn model (build_model's keyword: the dropout.hip pass each way at the "
+                         "model's dropout sites; 0 = off, no module is built); the stock baseline has none")
     ap.add_argument("--targets", choices=["hard", "soft", "mix"], default="hard",
                     help="ldnn step: hard = class indices; soft = a pre-mixed batch's class-probability targets "
                          "[B, C] (the loss kernel's soft-target instance); mix = soft plus the batch-mix pass "
@@ -71,9 +74,10 @@ def main():
     y = torch.randint(0, nc, (a.batch,), device="cuda")
 
     torch.manual_seed(0)
-    m = build_model(a.model)
+    m = build_model(a.model, dropout=a.dropout)
     xavier_init(m)
     ldnn.prepare(m, "cuda")
+    ldnn.reseed_dropout(m, 0)
     kw = dict(max_grad_norm=a.clip) if a.clip > 0 else {}
     if a.lars > 0:
         assert a.optimizer == "sgd", "--lars goes with --optimizer sgd"
@@ -125,7 +129,7 @@ def main():
             gs(*feed())
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "lr_schedule": a.lr_schedule, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "lr_schedule": a.lr_schedule, "dropout": a.dropout, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
