@@ -56,10 +56,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n_train", type=int, default=None)
     p.add_argument("--n_test", type=int, default=None)
     p.add_argument("--data_root", type=str, default="data")
-    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars", "lamb"],
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars", "lamb", "lion"],
                    help="lars: SGD-momentum with layer-wise adaptive rate scaling (per-tensor trust ratios); "
                         "lamb: Adam's direction with per-tensor trust ratios |w| / |u| (metrics.jsonl then logs "
-                        "lamb_ratio_min / _median / _max per global epoch)")
+                        "lamb_ratio_min / _median / _max per global epoch); lion: the sign of an interpolated "
+                        "momentum with one moment buffer, betas (0.9, 0.99) and decoupled --weight_decay (use a "
+                        "3-10x smaller --lr and a 3-10x larger --weight_decay than for adamw)")
     p.add_argument("--lamb_adapt_1d", action="store_true",
                    help="--optimizer lamb: also adapt tensors with dim() < 2 (biases, BatchNorm affine)")
     p.add_argument("--lars_trust", type=float, default=0.001,
@@ -234,6 +236,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "optimizer", None) == "lamb":
         # ... nor for a tensor's whole Adam direction
         why = "--optimizer lamb runs on the autograd path"
+    elif getattr(args, "optimizer", None) == "lion":
+        # the static engine's wgrad-fused optimizer epilogue has SGD and Adam forms only
+        why = "--optimizer lion runs on the autograd path"
     elif getattr(args, "label_smoothing", 0.0) > 0:
         # the static engine's head kernels compute the plain loss
         why = "--label_smoothing runs on the autograd path"

@@ -904,6 +904,21 @@ void adam_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor
         "adam_step");
 }
 
+// (every check comes before the launch: a refused call leaves the buffers untouched)
+void lion_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m,
+               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double beta1,
+               double beta2, double weight_decay, const Ranges& zero_ranges, const c10::optional<at::Tensor>& clip) {
+  const int64_t n = f32_bufs("lion", {{param, "param"}, {grad, "grad"}, {m, "exp_avg"}}, true, true);
+  const float* hpp = hp_ptr("lion", hp, param);
+  uint16_t* sh = shadow_ptr("lion", shadow, param, true);
+  const float* cp = clip_ptr(clip, param);
+  ldnn::LionParams lp{(float)beta1, (float)beta2, (float)weight_decay, grad_zero(zero_ranges, n)};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(param.device());
+  check(ldnn::lion_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), sh, hpp,
+                        (float)grad_scale, lp, n, cur_stream(param), cp),
+        "lion_step");
+}
+
 void head_fwd_xent(const at::Tensor& h, const at::Tensor& W, const at::Tensor& bias, const at::Tensor& labels,
                    const c10::optional<at::Tensor>& logits, const at::Tensor& dlogits, const at::Tensor& stats,
                    int64_t num_classes, double grad_scale, const c10::optional<at::Tensor>& dh,
@@ -2437,6 +2452,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("adam_step", &adam_step, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),
+        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
+  m.def("lion_step", &lion_step, "Lion: w = w (1 - lr wd) - lr sign(beta1 m + (1 - beta1) g), m = beta2 m + "
+        "(1 - beta2) g (+ bf16 shadow, gradient zero ranges); lr = hp[0]", py::arg("param"), py::arg("grad"),
+        py::arg("exp_avg"), py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("weight_decay"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
   m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
   m.def("lr_sched", &lr_sched, "learning-rate schedule, once per step: hp[0] = base * s(t + 1), the factor and the "

@@ -436,6 +436,14 @@ struct AdamParams {
 };
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
                      float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip = nullptr);
+// Lion: c = beta1 m + (1 - beta1) g, w = w (1 - lr weight_decay) - lr sign(c), m = beta2 m + (1 - beta2) g.
+// hp[0] = lr; hp[1] is not read (no bias correction, no bump_step).  clip / zero as in adam_step.
+struct LionParams {
+  float beta1, beta2, weight_decay;
+  GradZero zero;
+};
+hipError_t lion_step(float* param, float* grad, float* m, uint16_t* shadow, const float* hp, float grad_scale,
+                     LionParams lp, int64_t n, hipStream_t s, const float* clip = nullptr);
 // hp[1] += 1 (graph-capturable step counter); with clip: not on a skipped step
 hipError_t bump_step(float* hp, hipStream_t s, const float* clip = nullptr);
 

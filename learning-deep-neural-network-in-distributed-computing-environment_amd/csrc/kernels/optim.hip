@@ -246,6 +246,57 @@ __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
   }
 }
 
+// ---- Lion (Chen et al. 2023): the sign of an interpolated momentum, ONE moment buffer ----
+// c = beta1 m + (1 - beta1) g;  w = w (1 - lr wd) - lr sign(c);  m = beta2 m + (1 - beta2) g (from the
+// old m).  sign: +-1, 0 at +-0, NaN at NaN (a NaN gradient reaches the weight, as in the other updates).
+// No step count and no per-tensor norm: 22 B per element (w, g, m read; w, m, shadow written).
+__device__ __forceinline__ float lion_elem(float p, float g, float& m, float lr, const LionParams& lp) {
+  const float c = lp.beta1 * m + (1.f - lp.beta1) * g;
+  const float s = c > 0.f ? 1.f : (c < 0.f ? -1.f : (c == c ? 0.f : c));
+  if (lp.weight_decay != 0.f) p *= (1.f - lr * lp.weight_decay);
+  m = lp.beta2 * m + (1.f - lp.beta2) * g;
+  return p - lr * s;
+}
+
+template <bool NT, bool CLIP>
+__global__ void lion_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mm,
+                            bf16_t* __restrict__ shadow, const float* __restrict__ hp, float grad_scale,
+                            LionParams lp, int64_t n, ClipArg<CLIP> clip) {
+  if constexpr (CLIP) {
+    if (clip.st[kClipSkip] != 0.f) {
+      clear_only(lp.zero, grad, n);
+      return;
+    }
+    grad_scale *= clip.st[kClipCoef];
+  }
+  const float lr = hp[0];
+  const int64_t nv = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += stride) {
+    floatx4 p = ld4<NT>(param, i);
+    const floatx4 g = ld4<NT>(grad, i) * grad_scale;
+    clear4(lp.zero, grad, i);
+    floatx4 m = ld4<NT>(mm, i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float mj = m[j];
+      p[j] = lion_elem(p[j], g[j], mj, lr, lp);
+      m[j] = mj;
+    }
+    st4<NT>(param, i, p);
+    st4<NT>(mm, i, m);
+    if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = u16x4{f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
+  }
+  for (int64_t i = nv * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
+    float m = mm[i];
+    const float p = lion_elem(param[i], grad[i] * grad_scale, m, lr, lp);
+    if (in_zero(lp.zero, i)) grad[i] = 0.f;
+    param[i] = p;
+    mm[i] = m;
+    if (shadow) shadow[i] = f2bf(p);
+  }
+}
+
 __global__ void bump_kernel(float* hp) { hp[1] += 1.f; }
 // (a skipped step does not advance Adam's step count)
 __global__ void bump_clip_kernel(float* hp, const float* __restrict__ clip) {
@@ -695,6 +746,15 @@ hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* sh
   with_clip(clip, [&](auto ca) {
     adam_kernel<true, ca.on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
                                                                       ca);
+  });
+  return hipGetLastError();
+}
+
+hipError_t lion_step(float* param, float* grad, float* m, uint16_t* shadow, const float* hp, float grad_scale,
+                     LionParams lp, int64_t n, hipStream_t s, const float* clip) {
+  if (n <= 0) return hipSuccess;
+  with_clip(clip, [&](auto ca) {
+    lion_kernel<true, ca.on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, shadow, hp, grad_scale, lp, n, ca);
   });
   return hipGetLastError();
 }

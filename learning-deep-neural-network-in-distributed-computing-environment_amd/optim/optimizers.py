@@ -45,6 +45,10 @@ reduces per tensor, ``lamb_finalize`` leaves the ratios on the device, ``lamb_ap
 weights; the sharded step all-reduces the ``2S`` sums in a collective of its own after the
 moments -- they depend on the clip coefficient, which depends on the first reduction.
 
+``Lion`` (``build_optimizer("lion")``) sits at the other end: one moment, the sign of an interpolated
+momentum, no step count and no norm -- one ``lion_step`` launch per range and no stage of its own in
+``_FlatStep``; see the class (its NaN behaviour is documented there, beside LAMB's).
+
 ``ema_decay`` (default None = off; every optimizer, ``build_optimizer(ema_decay=, ema_warmup=)``) keeps an
 exponential moving average of the weights for evaluation: ``_ls()["ema"]``, a flat fp32 buffer shaped
 like the master (loose tensors: ``state[p]["ema"]``), created by the first eager step as a copy of the
@@ -676,8 +680,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         sd = super().state_dict()
         ls = self._ls()
         flat = {k: v for k, v in ls.items() if k not in _TRANSIENT}
-        if self._clip_threshold() is not None and "hp" in ls and "exp_avg" in ls:
+        if self._bumps_step and self._clip_threshold() is not None and "hp" in ls and "exp_avg" in ls:
             # the fused Adam's step count lives on the device: skipped steps did not advance it
+            # (Adam / AdamW / Lamb; Lion never bumps hp[1], its count is the host's)
             flat["step"] = int(ls["hp"][1].item())
         if "ema_hdr" in ls:
             # ... and so does the EMA's update count (load_state_dict hands it to the next header)
@@ -690,6 +695,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     # ---- device state an eager step allocates and a captured graph reads ---------------
     _ldnn_capturing = False    # set on the instance by GraphedStep / GraphedDPStep around their capture
+    _bumps_step = False        # the optimizer's prologue issues bump_step: hp[1] counts the non-skipped steps
 
     def _state(self, key, device, n=None):
         """The fp32 device vector ``key`` of ``_ls()``, at least ``n`` long: ``hp`` [lr, Adam's
@@ -1307,6 +1313,7 @@ def _adam_moments(m, v, g, b1, b2):
 
 class Adam(_FlatOptimizer):
     decoupled = False
+    _bumps_step = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
                  ema_decay=None, ema_warmup=True, lr_schedule=None):
@@ -1399,7 +1406,7 @@ class Lamb(_FlatOptimizer):
                                       ema_decay=ema_decay, ema_warmup=ema_warmup,
                                       lr_schedule=self._check_schedule(lr_schedule)))
 
-    _begin_ranges, _loose_state = Adam._begin_ranges, Adam._loose_state
+    _begin_ranges, _loose_state, _bumps_step = Adam._begin_ranges, Adam._loose_state, True
 
     def _update_native(self, s, sl, zero):
         f, g, M = s.f, s.group, s.M
@@ -1442,6 +1449,69 @@ class Lamb(_FlatOptimizer):
             p.data.add_(u, alpha=-lr * ratio)
 
 
+class Lion(_FlatOptimizer):
+    """Lion (Chen et al. 2023, "evolved sign momentum"): one moment, the update is a sign,
+
+        c = b1 m + (1 - b1) g
+        w = w (1 - lr weight_decay) - lr sign(c)      (decoupled decay; no factor when weight_decay == 0)
+        m = b2 m + (1 - b2) g                         (from the OLD m, after c)
+
+    ``g`` is the reduced, scaled and -- with ``max_grad_norm`` -- clipped gradient; ``sign`` is +-1, 0 at
+    +-0 and NaN at NaN.  There is no step count in the math (no bias correction) and no per-tensor norm,
+    so the flat GPU step is ONE ``lion_step`` launch per range (22 B per element: w, g, m read, w, m and
+    the bf16 shadow written; Adam moves 30), it updates by ranges like SGD / Adam (``supports_ranges()``;
+    with clipping the whole norm comes first, as for Adam) and the sharded step needs no collective of
+    its own.  The rate is ``hp[0]``: a captured step follows a changed lr and ``lr_schedule``.  Edge
+    behaviour, beside LAMB's: no non-finite guard without ``max_grad_norm`` -- a NaN gradient element
+    makes that element's ``m``, ``c``, ``sign(c)`` and ``w`` NaN (``torch.sign`` alone would give 0 there: the
+    torch twin puts the NaN back), an infinite one moves ``w`` by ``lr`` and leaves ``m`` infinite; with
+    ``max_grad_norm`` such a step is skipped whole (``w``, ``m``, shadow and EMA stay).  State: ``exp_avg``
+    (fp32, shaped like the master, zero at first) and the host's ``step``; there is no ``exp_avg_sq``."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, max_grad_norm=None, ema_decay=None,
+                 ema_warmup=True, lr_schedule=None):
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"Lion: betas must be two numbers in [0, 1); got {betas!r}")
+        self._check_ema_decay(ema_decay)
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                      lr_schedule=self._check_schedule(lr_schedule)))
+
+    def _begin_ranges(self, s):
+        return self._buf("exp_avg", s.f.master)     # (no launch: nothing counts steps on the device)
+
+    def _update_native(self, s, sl, zero):
+        f, g = s.f, s.group
+        p, grad, m, shadow = _cut(sl, f.master, f.grad, s.ctx, f.shadow)
+        _ext.C().lion_step(p, grad, m, shadow, s.hp, f.grad_scale, *g["betas"], g["weight_decay"], zero_ranges=zero,
+                           clip=s.cl)
+
+    def _update_torch(self, s, sl, p, g_, ratio):
+        g = s.group
+        self._lion_torch(p, g_, _cut(sl, s.ctx)[0], s.lr, *g["betas"], g["weight_decay"])
+
+    def _loose_update(self, group, cl, loose):
+        lr, (b1, b2), wd = group["lr"], group["betas"], group["weight_decay"]
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if cl is not None:
+                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+            ps = self.state.setdefault(p, {})
+            if "exp_avg" not in ps:
+                ps["exp_avg"] = torch.zeros_like(p)
+            self._lion_torch(p.data, p.grad, ps["exp_avg"], lr, b1, b2, wd)
+
+    @staticmethod
+    def _lion_torch(p, g, m, lr, b1, b2, wd):
+        c = m * b1 + g * (1 - b1)
+        s = torch.where(c != c, c, c.sign())      # (torch.sign(NaN) is 0; the kernel's is NaN)
+        if wd != 0:
+            p.mul_(1 - lr * wd)
+        p.add_(s, alpha=-lr)
+        m.mul_(b2).add_(g, alpha=1 - b2)
+
+
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     max_grad_norm: float | None = None, ema_decay: float | None = None, ema_warmup: bool = True,
                     lr_schedule: dict | None = None, **lars):
@@ -1449,13 +1519,14 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     weight EMA of every optimizer (None: off).  lr_schedule: the per-step schedule of every optimizer
     (a dict, see the module docstring; None: off).  "lars": SGD with
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
-    "sgd" takes them too); Adam and AdamW refuse them.  "lamb": Lamb, which takes
-    ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords."""
+    "sgd" takes them too); Adam, AdamW and Lion refuse them.  "lamb": Lamb, which takes
+    ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords.  "lion": Lion at its
+    default betas (0.9, 0.99); ``momentum`` is ignored, as for Adam."""
     name = name.lower()
     if max_grad_norm is not None and max_grad_norm <= 0:
         max_grad_norm = None
     allowed = {"lamb_exclude_1d"} if name == "lamb" else \
-        set() if name in ("adam", "adamw") else {"lars_trust", "lars_eps", "lars_exclude_1d"}
+        set() if name in ("adam", "adamw", "lion") else {"lars_trust", "lars_eps", "lars_exclude_1d"}
     bad = set(lars) - allowed
     if bad:
         raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
@@ -1473,4 +1544,6 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
         return Adam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     if name == "adamw":
         return AdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
+    if name == "lion":
+        return Lion(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     raise ValueError(f"unknown optimizer {name!r}")

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ldnn  # noqa: E402
 from ldnn.models import CrossEntropyLoss, build_model, dataset_for, xavier_init  # noqa: E402
 from ldnn.data.datasets import SHAPES  # noqa: E402
-from ldnn.optim import SGD, Adam, Lamb  # noqa: E402
+from ldnn.optim import SGD, Adam, Lamb, Lion  # noqa: E402
 
 
 def run(step, steps, warmup):
@@ -39,9 +39,10 @@ def main():
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--conv-impl", type=int, default=0, help="0 = LDS-DMA fast path, 1 = generic conv kernel only")
     ap.add_argument("--graph", action="store_true", help="replay the ldnn step from one hipGraph (train.graphed)")
-    ap.add_argument("--optimizer", choices=["sgd", "adam", "lamb"], default="sgd",
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "lamb", "lion"], default="sgd",
                     help="sgd = momentum 0.9; adam = the reference config (BAR/main.py:53, lr 1e-3); lamb = Lamb "
-                         "(lr 1e-3, weight decay 1e-2); the stock baseline of lamb is torch's Adam")
+                         "(lr 1e-3, weight decay 1e-2); lion = Lion (lr 1e-4, weight decay 0.1); the stock baseline "
+                         "of lamb and lion is torch's Adam")
     ap.add_argument("--clip", type=float, default=0.0,
                     help="max_grad_norm of the ldnn optimizer (global-norm clipping; 0 = off, 1e30 = the clipped "
                          "kernels with unchanged math)")
@@ -88,6 +89,7 @@ def main():
         kw["lr_schedule"] = dict(kind=a.lr_schedule, total_steps=10000, warmup_steps=10)
     opt = (Adam(m.parameters(), lr=1e-3, **kw) if a.optimizer == "adam"
            else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
+           else Lion(m.parameters(), lr=1e-4, weight_decay=0.1, **kw) if a.optimizer == "lion"
            else SGD(m.parameters(), lr=0.01, momentum=0.9, **kw))
     crit = CrossEntropyLoss(label_smoothing=a.label_smoothing)
     xb = x.bfloat16()
@@ -145,7 +147,7 @@ def main():
         from ldnn.ops import _ext
 
         _ext._DISABLED = True
-        ropt = (torch.optim.Adam(ref.parameters(), lr=1e-3) if a.optimizer in ("adam", "lamb") else
+        ropt = (torch.optim.Adam(ref.parameters(), lr=1e-3) if a.optimizer in ("adam", "lamb", "lion") else
                 torch.optim.SGD(ref.parameters(), lr=0.01, momentum=0.9))
         ce = nn.CrossEntropyLoss(label_smoothing=a.label_smoothing)
         xc = x.contiguous(memory_format=torch.channels_last)

@@ -14,7 +14,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ldnn  # noqa: E402
 from ldnn.models import CrossEntropyLoss, build_model, xavier_init  # noqa: E402
-from ldnn.optim import SGD, Adam, Lamb  # noqa: E402
+from ldnn.optim import SGD, Adam, Lamb, Lion  # noqa: E402
 from ldnn.parallel.comm import TorchComm  # noqa: E402
 from ldnn.parallel.ddp import DataParallel  # noqa: E402
 from ldnn.train.trainer import train_local_epoch  # noqa: E402
@@ -43,9 +43,9 @@ def main():
                          "the same parameters as with it off")
     ap.add_argument("--shard", action="store_true",
                     help="DataParallel(shard_optimizer=True): reduce-scatter + sharded optimizer + weight all-gather")
-    ap.add_argument("--optimizer", choices=["sgd", "adam", "lamb"], default="sgd",
-                    help="lamb: Lamb(lr=1e-3, weight_decay=1e-2).  With --shard the sharded run must also give the "
-                         "parameters of the unsharded LAMB run")
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "lamb", "lion"], default="sgd",
+                    help="lamb: Lamb(lr=1e-3, weight_decay=1e-2); lion: Lion(lr=1e-4, weight_decay=1e-2).  With "
+                         "--shard the sharded run must also give the parameters of the unsharded LAMB / Lion run")
     ap.add_argument("--comm-dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--gossip", type=int, default=0,
                     help="1 / 2: per-step ring / double-ring gossip (DataParallel(gossip=...)): the graphed chain "
@@ -85,6 +85,7 @@ def main():
             kw.update(lars_trust=a.lars, weight_decay=1e-4)
         opt = (SGD(m.parameters(), lr=0.02, momentum=0.9, **kw) if a.optimizer == "sgd"
                else Lamb(m.parameters(), lr=1e-3, weight_decay=1e-2, **kw) if a.optimizer == "lamb"
+               else Lion(m.parameters(), lr=1e-4, weight_decay=1e-2, **kw) if a.optimizer == "lion"
                else Adam(m.parameters(), lr=1e-3, **kw))
         batches = []
         for x, y in zip(xs, ys):
@@ -139,7 +140,7 @@ def main():
             print("GRAPHED_DP_OK", flush=True)
         D.teardown(ctx)
         return
-    if (a.clip > 0 or a.lars > 0 or a.optimizer == "lamb") and a.shard:
+    if (a.clip > 0 or a.lars > 0 or a.optimizer in ("lamb", "lion")) and a.shard:
         mu, _ = run(N, r, TorchComm(), shard=False)
         gotu = torch.cat([p.detach().flatten().cpu() for p in mu.parameters()])
         torch.manual_seed(0)
@@ -148,7 +149,7 @@ def main():
         p0 = torch.cat([p.detach().flatten() for p in m0.parameters()])
         du, dr = (got - p0).double(), (gotu - p0).double()
         err = (du - dr).norm().item() / max(dr.norm().item(), 1e-12)
-        print(f"rank {r}: clipped / LARS / LAMB sharded vs unsharded relative update difference {err:.3e}", flush=True)
+        print(f"rank {r}: clipped / LARS / LAMB / Lion sharded vs unsharded relative update difference {err:.3e}", flush=True)
         ok = ok and err < (2e-2 if a.comm_dtype == "fp32" else 5e-2)
     if a.oneshot:
         c1 = TorchComm()
