@@ -2037,7 +2037,8 @@ void gap_linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optiona
     bp = b->data_ptr<float>();
   }
   check(ldnn::gap_linear_fwd(bf16_ptr(x), bf16_ptr(w), bp, bf16_mut(pooled), bf16_mut(logits), (int)N, (int)HW,
-                             (int)C, (int)w.stride(0), (int)ncls, (int)logits.stride(0), cur_stream(x)),
+                             (int)C, (int)w.stride(0), (int)ncls, (int)logits.stride(0), (int)logits.size(1),
+                             cur_stream(x)),
         "gap_linear_fwd");
 }
 

@@ -390,8 +390,9 @@ hipError_t standin_copy(const float* src, float* dst, int64_t n, int blocks, int
 
 // ---- pooled classifier head (gap_head.hip): global average pool + Linear (<= 16 classes)
 bool gap_linear_ok(int N, int HW, int C, int ncls);
+// logits: [N][ncols] with row stride ldl, ncols >= ncls; columns [ncls, min(ncols, 16)) are written as zeros
 hipError_t gap_linear_fwd(const uint16_t* x, const uint16_t* W, const float* b, uint16_t* pooled, uint16_t* logits,
-                          int N, int HW, int C, int ldw, int ncls, int ldl, hipStream_t s);
+                          int N, int HW, int C, int ldw, int ncls, int ldl, int ncols, hipStream_t s);
 hipError_t gap_linear_bwd(const uint16_t* g, const uint16_t* pooled, const uint16_t* W, float* dW, float* db,
                           uint16_t* dx, int N, int HW, int C, int ldg, int ldw, int lddw, int ncls, float beta_w,
                           float beta_b, hipStream_t s);

@@ -22,11 +22,12 @@ constexpr int kHeadMaxC = 4096;   // pooled features held in LDS (fp32) per forw
 constexpr int kHeadMaxN = 65536;  // batch rows (the backward stages 256 at a time)
 
 // x [N][HW][C] bf16, W [ncls_pad][ldw] bf16 (rows >= ncls zero), b [ncls_pad] fp32
-// -> pooled [N][C] bf16, logits [N][ldl] bf16 (columns < ncls_pad written)
+// -> pooled [N][C] bf16, logits [N][ncols] bf16 with row stride ldl (every column < min(ncols, 16) is
+// written, those >= ncls as zeros; nothing of a row behind ncols is touched)
 __global__ __launch_bounds__(256) void gap_linear_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
                                                              const float* __restrict__ b, bf16_t* __restrict__ pooled,
                                                              bf16_t* __restrict__ logits, int HW, int C, int ldw,
-                                                             int ncls, int ldl) {
+                                                             int ncls, int ldl, int ncols) {
   __shared__ float pl[kHeadMaxC];
   const int n = blockIdx.x, tid = threadIdx.x;
   const float inv = 1.f / (float)HW;
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256) void gap_linear_fwd_kernel(const bf16_t* __res
   }
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) acc += __shfl_xor(acc, o, 64);
-  if (q == 0 && k < ldl) logits[(size_t)n * ldl + k] = k < ncls ? f2bf(acc + (b ? b[k] : 0.f)) : (bf16_t)0;
+  if (q == 0 && k < ncols) logits[(size_t)n * ldl + k] = k < ncls ? f2bf(acc + (b ? b[k] : 0.f)) : (bf16_t)0;
 }
 
 // g [N][ldg] bf16 (dlogits, columns >= ncls zero), pooled [N][C] bf16, W [ncls][ldw] bf16
@@ -159,9 +160,10 @@ bool gap_linear_ok(int N, int HW, int C, int ncls) {
 }
 
 hipError_t gap_linear_fwd(const uint16_t* x, const uint16_t* W, const float* b, uint16_t* pooled, uint16_t* logits,
-                          int N, int HW, int C, int ldw, int ncls, int ldl, hipStream_t s) {
-  if (!gap_linear_ok(N, HW, C, ncls) || ldw % 8 != 0 || ldl < ncls) return hipErrorInvalidValue;
-  gap_linear_fwd_kernel<<<N, 256, 0, s>>>(x, W, b, pooled, logits, HW, C, ldw, ncls, ldl);
+                          int N, int HW, int C, int ldw, int ncls, int ldl, int ncols, hipStream_t s) {
+  if (!gap_linear_ok(N, HW, C, ncls) || ldw % 8 != 0 || ncols < ncls || (N > 1 && ldl < ncols))
+    return hipErrorInvalidValue;
+  gap_linear_fwd_kernel<<<N, 256, 0, s>>>(x, W, b, pooled, logits, HW, C, ldw, ncls, ldl, ncols);
   return hipGetLastError();
 }
 
