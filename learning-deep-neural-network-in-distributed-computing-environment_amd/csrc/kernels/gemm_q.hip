@@ -105,34 +105,73 @@ __device__ __forceinline__ void dma1(__amdgpu_buffer_rsrc_t rs, char* dst, const
 __device__ __forceinline__ uint32_t lds_addr(const char* p) {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
-template <bool KC, bool ASM = true>
-__device__ __forceinline__ bf16x8 frag(const char* lds, int rt, int kk, int lane) {
-  if constexpr (KC && !ASM) {
-    return read_frag<true, BM>(lds, rt, kk, lane);
-  } else if constexpr (KC) {
-    const int row = rt * 16 + (lane & 15);
-    const int chunk = kk * 4 + (lane >> 4);
+// The asm reads take a per-lane base register plus an immediate offset: with one wave per
+// SIMD nothing hides address arithmetic between two MFMAs, and everything in a fragment's
+// address that depends on the lane or the wave is the same for every K-tile:
+//   k-strided image  (kb*16 + rt)*256 + ((q ^ sw)*32) + pp*8,  kb = kk*4 + g,  sw = (g & 1) << 2
+//     = [g*4096 + w*2048 + ((q ^ sw)*32) + pp*8]  +  kk*16384 + r*256        (rt = w*8 + r)
+//     two bases: the lo and hi halves (q, 4 + q) differ by +-128 with sw
+//   k-contiguous image  row*128 + ((chunk ^ (row & 7)) << 4),  row = rt*16 + (lane & 15), chunk = kk*4 + g
+//     = [(w*128 + (lane & 15))*128 + (((kk*4 + g) ^ (lane & 7)) << 4)]  +  r*2048
+//     one base per kk (kk flips bit 2 of the swizzled chunk: +-64 by lane)
+// The operand's place in the stage (kTile) joins the immediate (< 2^16); the stage (kStage)
+// does not fit, so the bases are moved from stage to stage once per K-tile (FragBase::flip).
+struct FragBase {
+  uint32_t b[2];
+  __device__ __forceinline__ void pin() {  // keep the bases in registers: never rematerialised in the loop
+    asm volatile("" : "+v"(b[0]), "+v"(b[1]));
+  }
+  __device__ __forceinline__ void flip(int delta) {
+    b[0] += (uint32_t)delta;
+    b[1] += (uint32_t)delta;
+    pin();
+  }
+};
+template <bool KC>
+__device__ __forceinline__ FragBase frag_base(const char* smem, int w, int lane) {
+  const int g = lane >> 4;
+  FragBase fb;
+  if constexpr (KC) {
+    const uint32_t row = lds_addr(smem) + (uint32_t)((w * 128 + (lane & 15)) * 128);
+    fb.b[0] = row + (uint32_t)((g ^ (lane & 7)) << 4);
+    fb.b[1] = row + (uint32_t)(((4 + g) ^ (lane & 7)) << 4);
+  } else {
+    const int q = (lane & 15) >> 2, pp = lane & 3, sw = (g & 1) << 2;
+    const uint32_t blk = lds_addr(smem) + (uint32_t)(g * 4096 + w * 2048 + pp * 8);
+    fb.b[0] = blk + (uint32_t)((q ^ sw) * 32);
+    fb.b[1] = blk + (uint32_t)(((4 + q) ^ sw) * 32);
+  }
+  fb.pin();
+  return fb;
+}
+// fragment r (0..7) of the wave's row tiles, k-sub kk, of operand `opnd` (0: A, 1: B) of the
+// stage the bases point at; opnd, kk and r are constants once the callers' loops are unrolled
+template <bool KC>
+__device__ __forceinline__ bf16x8 frag(const FragBase& fb, int opnd, int kk, int r) {
+  if constexpr (KC) {
     bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(lds) + (uint32_t)(row * 128 + ((chunk ^ (row & 7)) << 4)))
-                 : "memory");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(fb.b[kk]), "i"(opnd * kTile + r * 2048) : "memory");
     return v;
   } else {
-    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-    const int kb = kk * 4 + g;
-    const int sw = (kb & 1) << 2;
-    const uint32_t blk = lds_addr(lds) + (uint32_t)((kb * (BM / 16) + rt) * 256);
     bf16x4 lo, hi;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(blk + ((q ^ sw) * 32) + pp * 8) : "memory");
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(blk + (((4 + q) ^ sw) * 32) + pp * 8) : "memory");
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+                 : "=v"(lo) : "v"(fb.b[0]), "i"(opnd * kTile + kk * 16384 + r * 256) : "memory");
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+                 : "=v"(hi) : "v"(fb.b[1]), "i"(opnd * kTile + kk * 16384 + r * 256) : "memory");
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   }
 }
 __device__ __forceinline__ void lgkm_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-template <bool KC, bool ASM>
+template <bool KC>
+__device__ __forceinline__ void read8(bf16x8 (&f)[8], const FragBase& fb, int opnd, int kk) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) f[i] = frag<KC>(fb, opnd, kk, i);
+}
+// compiler-tracked reads of the all-k-contiguous kernels
 __device__ __forceinline__ void read8(bf16x8 (&f)[8], const char* lds, int rt0, int kk, int lane) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = frag<KC, ASM>(lds, rt0 + i, kk, lane);
+  for (int i = 0; i < 8; ++i) f[i] = read_frag<true, BM>(lds, rt0 + i, kk, lane);
 }
 
 // 64 MFMAs: acc[n-tile j][m-tile i] += B_j^T A_i (MFMA-A <- B fragment: lanes own 4 consecutive columns)
@@ -577,6 +616,24 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
     issue<B_KC>(ob, dst + kTile, k0, p.K, kend, wid);
   };
 
+  // asm fragment reads: per-lane bases, pointing at stage 0; they follow the K loop from stage to
+  // stage (one flip per K-tile, after the last read of `cur`: the next reads are of `nxt`, which
+  // is the following tile's `cur`)
+  FragBase ba{}, bb{};
+  int flip = kStage;
+  if constexpr (kAsm) {
+    ba = frag_base<A_KC>(smem, wm, lane);
+    bb = frag_base<B_KC>(smem, wn, lane);
+  }
+  auto frag_a = [&](const char* st, int kk, int r) {
+    if constexpr (kAsm) return frag<A_KC>(ba, 0, kk, r);
+    else return read_frag<true, BM>(st, wm * 8 + r, kk, lane);
+  };
+  auto frag_b = [&](const char* st, int kk, int r) {
+    if constexpr (kAsm) return frag<B_KC>(bb, 1, kk, r);
+    else return read_frag<true, BM>(st + kTile, wn * 8 + r, kk, lane);
+  };
+
   bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
   mma_fence();
   if (nk > 0) {
@@ -584,8 +641,13 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
     stage(1, smem + kStage);
     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // tile 0 landed, tile 1 in flight
     barrier();
-    read8<A_KC, kAsm>(fa0, smem, wm * 8, 0, lane);
-    read8<B_KC, kAsm>(fb0, smem + kTile, wn * 8, 0, lane);
+    if constexpr (kAsm) {
+      read8<A_KC>(fa0, ba, 0, 0);
+      read8<B_KC>(fb0, bb, 1, 0);
+    } else {
+      read8(fa0, smem, wm * 8, 0, lane);
+      read8(fb0, smem + kTile, wn * 8, 0, lane);
+    }
   }
   for (int t = 0; t < nk; ++t) {
     char* const cur = smem + (t & 1) * kStage;
@@ -596,13 +658,18 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
     mma(acc, fa0, fb0, [&](int q) {
       const int r = q >> 1;
       if ((kRead || t == 0) && !(q & 1) && r < 16) {
-        if (r < 8) fa1[r] = frag<A_KC, kAsm>(cur, wm * 8 + r, 1, lane);
-        else fb1[r - 8] = frag<B_KC, kAsm>(cur + kTile, wn * 8 + r - 8, 1, lane);
+        if (r < 8) fa1[r] = frag_a(cur, 1, r);
+        else fb1[r - 8] = frag_b(cur, 1, r - 8);
       }
     });
     // one barrier per K-tile: every wave finished reading `cur`, tile t+1 (own DMA waited) published
     if (kWait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     barrier();
+    if constexpr (kAsm) {
+      ba.flip(flip);
+      bb.flip(flip);
+      flip = -flip;
+    }
     // sub-step 1: tile t+2's DMA into `cur` and tile t+1's first fragments, between the MFMAs
     const int k2 = kbase + (t + 2) * BK;
     const __amdgpu_buffer_rsrc_t ra = rsrc_at<A_KC>(oa, k2, kend), rb = rsrc_at<B_KC>(ob, k2, kend);
@@ -614,8 +681,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
       if constexpr (XF & 8) {
         const int rr = q >> 1, r = (q - 32) >> 1;
         if (kRead && q < 32 && (q & 1)) {
-          if (rr < 8) fa0[rr] = frag<A_KC, kAsm>(nxt, wm * 8 + rr, 0, lane);
-          else fb0[rr - 8] = frag<B_KC, kAsm>(nxt + kTile, wn * 8 + rr - 8, 0, lane);
+          if (rr < 8) fa0[rr] = frag_a(nxt, 0, rr);
+          else fb0[rr - 8] = frag_b(nxt, 0, rr - 8);
         }
         if (kDma && q >= 32 && !(q & 1)) {
           if (r < 8) dma1<XF>(ra, cur, oa, r, killa, wid);
@@ -628,8 +695,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
           else dma1<XF>(rb, cur + kTile, ob, r - 8, killb, wid);
         }
         if (kRead && q >= 32 && (q & 1)) {
-          if (rr < 8) fa0[rr] = frag<A_KC, kAsm>(nxt, wm * 8 + rr, 0, lane);
-          else fb0[rr - 8] = frag<B_KC, kAsm>(nxt + kTile, wn * 8 + rr - 8, 0, lane);
+          if (rr < 8) fa0[rr] = frag_a(nxt, 0, rr);
+          else fb0[rr - 8] = frag_b(nxt, 0, rr - 8);
         }
       } else {
         const int r = q >> 2;
@@ -639,13 +706,20 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
         }
         const int rr = q >> 1;
         if (kRead && (q & 1) && rr < 16) {
-          if (rr < 8) fa0[rr] = frag<A_KC, kAsm>(nxt, wm * 8 + rr, 0, lane);
-          else fb0[rr - 8] = frag<B_KC, kAsm>(nxt + kTile, wn * 8 + rr - 8, 0, lane);
+          if (rr < 8) fa0[rr] = frag_a(nxt, 0, rr);
+          else fb0[rr - 8] = frag_b(nxt, 0, rr - 8);
         }
       }
     });
   }
   mma_fence();
+
+  // the asm kernels' fragment bases share their lane arithmetic (lane & 15, lane >> 4, ...) with the
+  // epilogue's; left to itself the compiler keeps those values from before the K loop and spills
+  // them at the epilogue's register peak, reloading one in every row of the store loop.  An opaque
+  // copy of the lane makes the epilogue derive its own after the loop.
+  int lane_e = lane;
+  if constexpr (kAsm) asm volatile("" : "+v"(lane_e));
 
   GemmParams pe = p;
   if (gridDim.y > 1) {
@@ -672,16 +746,16 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_kernel(GemmParams p) {
                                            EPI == EPI_BIAS_RELU_MASK || EPI == EPI_BIAS_RELU_HEAD ||
                                            EPI == EPI_DRELU_MASK) && (XF & 128) == 0;
     if constexpr (EPI == EPI_BIAS_RELU_HEAD) {
-      epilogue_bf16<EPI>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane);
+      epilogue_bf16<EPI>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane_e);
     } else if constexpr (kBf16Epi) {
-      if (p.variant & 8192) epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane);
-      else epilogue_bf16<EPI>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane);
+      if (p.variant & 8192) epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane_e);
+      else epilogue_bf16<EPI>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane_e);
     } else {
-      epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane);
+      epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane_e);
     }
   } else {
     barrier();  // every wave is done with the operand stages: LDS belongs to the epilogue
-    epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane);
+    epilogue_q<EPI, OUT_F32, XF>(pe, acc, smem, wid, m0 + wm * 128, n0 + wn * 128, lane_e);
   }
 }
 
