@@ -87,6 +87,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "EnhancedCNNs, in one native pass each way (dropout.hip) whose mask is a counter hash of "
                         "(--seed, rank, global epoch, module, step): nothing is stored for the backward, a resumed run "
                         "replays the masks, and validation and the final test run without it")
+    p.add_argument("--norm", choices=["batch", "group"], default="batch",
+                   help="normalisation layer of the EnhancedCNNs and ResNets: batch (default, BatchNorm2d) or group "
+                        "(GroupNorm under the same parameter names: statistics per sample, so the result does not "
+                        "depend on which samples share a batch; no running statistics, train and eval are the same "
+                        "function; native NHWC bf16 passes with the residual add and the ReLU fused, group_norm.hip).  "
+                        "The MLPs and LeNet-5 have no normalisation layer and refuse group")
+    p.add_argument("--gn_groups", type=int, default=32, metavar="G",
+                   help="--norm group: number of channel groups (default 32); must divide every normalised width")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
                    help="Mixup of every training batch with a permutation of itself, lam ~ Beta(ALPHA, ALPHA), one "
                         "draw per batch, in one native pass (mix.hip) that also writes the class-probability targets "
@@ -254,6 +262,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "dropout", 0.0) > 0:
         # the static engine's layer chain has no pass between a layer's epilogue and the next GEMM
         why = "--dropout runs on the autograd path"
+    elif getattr(args, "norm", "batch") == "group":
+        # the static engine is a chain of GEMMs: it has no normalisation pass
+        why = "--norm group runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -314,6 +325,12 @@ def main(argv=None):
     for flag, v in (("--mix_prob", args.mix_prob), ("--mix_switch_prob", args.mix_switch_prob)):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} must be in [0, 1], got {v}")
+    from .models import NORM_MODELS
+    if args.norm == "group" and args.model not in NORM_MODELS:
+        raise SystemExit(f"--norm group: --model {args.model} has no normalisation layer "
+                         f"(models with one: {', '.join(NORM_MODELS)})")
+    if args.norm == "group" and args.gn_groups < 1:
+        raise SystemExit(f"--gn_groups must be >= 1, got {args.gn_groups}")
     from . import prepare
     from .data.loader import get_loaders
     from .data.mix import BatchMix
@@ -335,7 +352,10 @@ def main(argv=None):
     comm = default_comm(args.oneshot_bytes)
 
     dataset = args.dataset or dataset_for(args.model)
-    model = build_model(args.model, dropout=args.dropout)
+    try:
+        model = build_model(args.model, dropout=args.dropout, norm=args.norm, gn_groups=args.gn_groups)
+    except ValueError as e:   # (a --gn_groups that does not divide a width)
+        raise SystemExit(str(e))
     xavier_init(model)
     use_engine = resolve_engine(args, model, dev, world)
     if use_engine:

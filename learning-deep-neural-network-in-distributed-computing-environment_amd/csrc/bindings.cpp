@@ -1761,6 +1761,85 @@ void bn_bwd(const at::Tensor& x, const at::Tensor& y, const at::Tensor& dy, cons
         "bn_backward");
 }
 
+// ---- GroupNorm: x, y, residual, dy, dx, dres dense NHWC bf16 [N][H][W][C]; mean, rstd fp32 [N*G]
+const uint16_t* gn_act(const at::Tensor& t, const at::Tensor& x, const char* name) {
+  check_dev(t, at::kBFloat16, name);
+  TORCH_CHECK(t.sizes() == x.sizes() && t.is_contiguous(), "group_norm: ", name, " must be dense NHWC like x");
+  TORCH_CHECK(t.device() == x.device(), "group_norm: ", name, " is on another device than x");
+  TORCH_CHECK(aligned16(t.data_ptr()), "group_norm: ", name, " must be 16-byte aligned");
+  return bf16_ptr(t);
+}
+
+// (only the workspace is read with 16-byte loads; the per-channel and per-group vectors are read by element)
+float* gn_vec(const c10::optional<at::Tensor>& t, int64_t n, const at::Tensor& x, const char* name,
+              bool vector_loads = false) {
+  float* p = fptr_opt(t, n, name);
+  if (p != nullptr) {
+    TORCH_CHECK(t->device() == x.device(), "group_norm: ", name, " is on another device than x");
+    TORCH_CHECK(!vector_loads || aligned16(p), "group_norm: ", name, " must be 16-byte aligned");
+  }
+  return p;
+}
+
+ldnn::GnArgs gn_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma, const at::Tensor& mean,
+                     const at::Tensor& rstd, const at::Tensor& ws, int64_t G, bool relu,
+                     const c10::optional<at::Tensor>& mask) {
+  check_dev(x, at::kBFloat16, "x");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "group_norm: x must be dense NHWC [N][H][W][C]");
+  TORCH_CHECK(aligned16(x.data_ptr()), "group_norm: x must be 16-byte aligned");
+  const int64_t N = x.size(0), P = x.size(1) * x.size(2), C = x.size(3);
+  TORCH_CHECK(C % 8 == 0, "group_norm: C must be a multiple of 8, got ", C);
+  TORCH_CHECK(G >= 1 && C % G == 0, "group_norm: ", G, " groups do not divide ", C, " channels");
+  TORCH_CHECK(N <= 65535 && C <= (1 << 20), "group_norm: at most 65535 samples and 2^20 channels");
+  ldnn::GnArgs a{};
+  a.x = bf16_ptr(x);
+  a.N = N, a.P = P, a.C = (int)C, a.G = (int)G;
+  a.relu = relu ? 1 : 0;
+  a.gamma = gn_vec(gamma, C, x, "gamma");
+  a.mean = gn_vec(mean, N * G, x, "mean");
+  a.rstd = gn_vec(rstd, N * G, x, "rstd");
+  a.ws = gn_vec(ws, ldnn::gn_workspace_floats(N, P, (int)C, (int)G), x, "ws", true);
+  if (mask.has_value()) {
+    check_dev(*mask, at::kByte, "mask");
+    TORCH_CHECK(relu && mask->is_contiguous() && mask->numel() == x.numel() / 8 && mask->device() == x.device(),
+                "group_norm: mask needs relu and N*H*W*C/8 bytes on x's device");
+    a.mask = mask->data_ptr<uint8_t>();
+  }
+  return a;
+}
+
+void gn_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& residual,
+            const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta, const at::Tensor& mean,
+            const at::Tensor& rstd, const at::Tensor& ws, int64_t G, double eps, bool relu,
+            const c10::optional<at::Tensor>& mask, bool apply_only) {
+  ldnn::GnArgs a = gn_args(x, gamma, mean, rstd, ws, G, relu, mask);
+  a.apply_only = apply_only ? 1 : 0;
+  a.y = const_cast<uint16_t*>(gn_act(y, x, "y"));
+  TORCH_CHECK(y.data_ptr() != x.data_ptr(), "gn_fwd: in-place is not supported");
+  if (residual.has_value()) a.residual = gn_act(*residual, x, "residual");
+  a.beta = gn_vec(beta, x.size(3), x, "beta");
+  a.eps = (float)eps;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check(ldnn::gn_forward(a, cur_stream(x)), "gn_forward");
+}
+
+void gn_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, const c10::optional<at::Tensor>& dres,
+            const c10::optional<at::Tensor>& gamma, const at::Tensor& mean, const at::Tensor& rstd,
+            const at::Tensor& ws, const c10::optional<at::Tensor>& dgamma, const c10::optional<at::Tensor>& dbeta,
+            int64_t G, bool relu, const c10::optional<at::Tensor>& mask, bool grad_assign, bool apply_only) {
+  ldnn::GnArgs a = gn_args(x, gamma, mean, rstd, ws, G, relu, mask);
+  a.apply_only = apply_only ? 1 : 0;
+  TORCH_CHECK(relu == mask.has_value(), "gn_bwd: the backward of a relu forward reads its bit mask");
+  const uint16_t* g = gn_act(dy, x, "dy");
+  uint16_t* d = const_cast<uint16_t*>(gn_act(dx, x, "dx"));
+  uint16_t* dr = dres.has_value() ? const_cast<uint16_t*>(gn_act(*dres, x, "dres")) : nullptr;
+  TORCH_CHECK(d != a.x && d != g && dr != d, "gn_bwd: in-place is not supported");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::gn_backward(a, g, d, dr, gn_vec(dgamma, x.size(3), x, "dgamma"), gn_vec(dbeta, x.size(3), x, "dbeta"),
+                          grad_assign, cur_stream(x)),
+        "gn_backward");
+}
+
 // x [N][H][W][C], y [N][P][Q][C] dense bf16; argmax uint8 [N][P][Q][C] for max pooling
 void pool_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& argmax, int64_t R,
               int64_t S, int64_t stride, int64_t pad, bool is_max, bool nchw_out) {
@@ -2506,6 +2585,18 @@ PYBIND11_MODULE(_C, m) {
         py::arg("gamma"), py::arg("save_mean"), py::arg("save_invstd"), py::arg("ws"), py::arg("dgamma"),
         py::arg("dbeta"), py::arg("relu"), py::arg("mask") = py::none(), py::arg("grad_assign") = false,
         py::arg("dy2") = py::none(), py::arg("stats_ready") = false);
+  m.def("gn_fwd", &gn_fwd, "y = relu?(group_norm(x) (+ residual)) over dense NHWC bf16; writes mean / rstd [N*G]",
+        py::arg("x"), py::arg("y"), py::arg("residual"), py::arg("gamma"), py::arg("beta"), py::arg("mean"),
+        py::arg("rstd"), py::arg("ws"), py::arg("groups"), py::arg("eps"), py::arg("relu"),
+        py::arg("mask") = py::none(), py::arg("apply_only") = false);
+  m.def("gn_bwd", &gn_bwd, "backward of gn_fwd: dx, optional dres, dgamma / dbeta stored (grad_assign) or added",
+        py::arg("x"), py::arg("dy"), py::arg("dx"), py::arg("dres"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("ws"), py::arg("dgamma"), py::arg("dbeta"), py::arg("groups"), py::arg("relu"),
+        py::arg("mask") = py::none(), py::arg("grad_assign") = false, py::arg("apply_only") = false);
+  m.def("gn_workspace_floats", &ldnn::gn_workspace_floats, "fp32 scratch of one GroupNorm call (nothing to zero)",
+        py::arg("N"), py::arg("P"), py::arg("C"), py::arg("G"));
+  m.def("gn_slabs", &ldnn::gn_slabs, "pixel slabs per sample of the GroupNorm statistics passes", py::arg("N"),
+        py::arg("P"), py::arg("C"), py::arg("G"));
   m.def("pool_fwd", &pool_fwd, py::arg("x"), py::arg("y"), py::arg("argmax"), py::arg("R"), py::arg("S"),
         py::arg("stride"), py::arg("pad"), py::arg("is_max"), py::arg("nchw_out") = false);
   m.def("pool_bwd", &pool_bwd, py::arg("dy"), py::arg("argmax"), py::arg("dx"), py::arg("R"), py::arg("S"),

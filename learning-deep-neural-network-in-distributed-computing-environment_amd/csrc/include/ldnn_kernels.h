@@ -299,6 +299,34 @@ hipError_t pool2d_bwd(const uint16_t* dy, const uint8_t* argmax, uint16_t* dx, i
 hipError_t global_avgpool_fwd(const uint16_t* x, uint16_t* y, int N, int HW, int C, hipStream_t s);
 hipError_t global_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int HW, int C, hipStream_t s);
 
+// ---- GroupNorm on dense NHWC bf16 [N][P][C] (group_norm.hip), C % 8 == 0, C % G == 0
+// Statistics per (sample, group of C / G neighbouring channels), biased variance; residual add and
+// ReLU fused into the apply pass.  No atomics: a shape has one summation order.
+struct GnArgs {
+  const uint16_t* x;          // [N][P][C] input
+  const uint16_t* residual;   // optional [N][P][C] added before the ReLU (forward)
+  uint16_t* y;                // [N][P][C] output (forward)
+  const float* gamma;         // [C] (nullable: affine=False)
+  const float* beta;
+  float* mean;                // [N][G] written by the forward, read by the backward
+  float* rstd;
+  float* ws;                  // [gn_workspace_floats] fp32 scratch, nothing to zero or keep
+  uint8_t* mask;              // [N*P*C/8] ReLU bits in bn_fwd's layout: written by a relu forward with a
+                              // backward pending, required by the backward of a relu forward
+  int64_t N, P;
+  int C, G;
+  float eps;
+  int relu;
+  int apply_only;             // measurements: the streaming pass alone, with the coefficients the
+                              // previous whole call of this direction left in ws
+};
+int64_t gn_workspace_floats(int64_t N, int64_t P, int C, int G);
+int gn_slabs(int64_t N, int64_t P, int C, int G);   // pixel slabs per sample of the statistics passes
+hipError_t gn_forward(const GnArgs& a, hipStream_t s);
+// dx, optionally dres = the masked dy; dgamma / dbeta (nullable) stored when grad_assign, else added
+hipError_t gn_backward(const GnArgs& a, const uint16_t* dy, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
+                       bool grad_assign, hipStream_t s);
+
 // ---- elementwise / activations (bf16 storage, fp32 math) ---------------------
 enum Act : int { ACT_RELU = 0, ACT_SIGMOID = 1 };
 hipError_t act_fwd(const uint16_t* x, uint16_t* y, int64_t n, int act, hipStream_t s);

@@ -5,28 +5,42 @@ from __future__ import annotations
 import torch.nn as nn
 
 from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock  # noqa: F401
-from .layers import CrossEntropyLoss, Dropout, Linear, reseed_dropout  # noqa: F401
+from .layers import NORMS, CrossEntropyLoss, Dropout, GroupNorm, Linear, reseed_dropout  # noqa: F401
 from .mlp import MLP, mlp2, mlp3  # noqa: F401
 from .resnet import ResNet, resnet18  # noqa: F401
 
 # name -> (constructor, input kind for the synthetic dataset)
 REGISTRY = {
-    "enhanced_cnn": (lambda nc=10, dropout=0.0: EnhancedCNNModel(nc, dropout=dropout), "cifar10"),
-    "enhanced_cnn_small": (lambda nc=10, dropout=0.0: EnhancedCNNSmall(nc, dropout=dropout), "cifar10"),
+    "enhanced_cnn": (lambda nc=10, dropout=0.0, **norm: EnhancedCNNModel(nc, dropout=dropout, **norm), "cifar10"),
+    "enhanced_cnn_small": (lambda nc=10, dropout=0.0, **norm: EnhancedCNNSmall(nc, dropout=dropout, **norm), "cifar10"),
     "lenet5": (lambda nc=10, dropout=0.0: LeNet5(nc, dropout=dropout), "mnist"),
     "mlp2": (lambda nc=10, dropout=0.0: mlp2(784, 1024, nc, dropout=dropout), "mnist"),
     "mlp3": (lambda nc=10, dropout=0.0: mlp3(784, 4096, nc, dropout=dropout), "mnist"),
     "mlp3_small": (lambda nc=10, dropout=0.0: mlp3(784, 1024, nc, dropout=dropout), "mnist"),
-    "resnet18": (lambda nc=1000, dropout=0.0: resnet18(nc, dropout=dropout), "imagenet"),
-    "resnet18_cifar": (lambda nc=10, dropout=0.0: resnet18(nc, dropout=dropout), "cifar10"),
+    "resnet18": (lambda nc=1000, dropout=0.0, **norm: resnet18(nc, dropout=dropout, **norm), "imagenet"),
+    "resnet18_cifar": (lambda nc=10, dropout=0.0, **norm: resnet18(nc, dropout=dropout, **norm), "cifar10"),
 }
 
 
-def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0) -> nn.Module:
+# the models that have normalisation layers, hence a ``norm`` choice
+NORM_MODELS = ("enhanced_cnn", "enhanced_cnn_small", "resnet18", "resnet18_cifar")
+
+
+def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0, norm: str = "batch",
+                gn_groups: int = 32) -> nn.Module:
     """``dropout``: the rate of the model's Dropout modules (MLPs: after every hidden layer; LeNet-5:
-    after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist."""
+    after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist.
+    ``norm``: "batch" (BatchNorm2d, the default) or "group" (GroupNorm with ``gn_groups`` groups under
+    the same attribute names, so the ``weight`` / ``bias`` keys are the BatchNorm model's and there are
+    no buffers); the MLPs and LeNet-5 have no normalisation layer and refuse "group"."""
     ctor, _ = REGISTRY[name]
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
     kw = {"dropout": dropout} if dropout else {}
+    if norm == "group":
+        if name not in NORM_MODELS:
+            raise ValueError(f"norm='group': {name} has no normalisation layer")
+        kw.update(norm=norm, gn_groups=gn_groups)
     return ctor(**kw) if num_classes is None else ctor(num_classes, **kw)
 
 

@@ -14,16 +14,18 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..ops import functional as LF
-from .layers import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, pair_conv_bn
+from .layers import (AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, make_norm,
+                     pair_conv_bn)
 
 
 class ConvBNReLU(nn.Sequential):
-    """Sequential(conv, bn, relu) -- same state_dict keys (prep.0 / prep.1) -- whose
-    BN and ReLU run as one fused pass."""
+    """Sequential(conv, norm, relu) -- same state_dict keys (prep.0 / prep.1) -- whose
+    norm and ReLU run as one fused pass."""
 
     def __init__(self, *mods):
         super().__init__(*mods)
-        pair_conv_bn(self[0], self[1])
+        if isinstance(self[1], BatchNorm2d):
+            pair_conv_bn(self[0], self[1])
 
     def forward(self, x):
         return self[1].act(self[0](x), relu=True)
@@ -31,27 +33,39 @@ class ConvBNReLU(nn.Sequential):
 
 class ResBlock(nn.Module):
     """conv3x3(stride)-BN-ReLU-conv3x3-BN + shortcut (1x1 conv + BN when the shape
-    changes) -> add -> ReLU; convs without bias (BAR/model.py:52-72)."""
+    changes) -> add -> ReLU; convs without bias (BAR/model.py:52-72).  ``norm="group"``: a
+    GroupNorm under every BN's attribute name (bn1, bn2, shortcut.1)."""
 
-    def __init__(self, in_channels, out_channels, stride=1):
+    def __init__(self, in_channels, out_channels, stride=1, norm: str = "batch", gn_groups: int = 32):
         super().__init__()
         self.conv1 = Conv2d(in_channels, out_channels, kernel_size=3, stride=stride, padding=1, bias=False)
-        self.bn1 = BatchNorm2d(out_channels)
+        self.bn1 = make_norm(norm, out_channels, gn_groups)
         self.conv2 = Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False)
-        self.bn2 = BatchNorm2d(out_channels)
+        self.bn2 = make_norm(norm, out_channels, gn_groups)
         self.shortcut = nn.Sequential()
         if stride != 1 or in_channels != out_channels:
             self.shortcut = nn.Sequential(
                 Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False),
-                BatchNorm2d(out_channels),
+                make_norm(norm, out_channels, gn_groups),
             )
         self.relu = ReLU()
-        pair_conv_bn(self.conv1, self.bn1)
-        pair_conv_bn(self.conv2, self.bn2)
-        if len(self.shortcut):
-            pair_conv_bn(self.shortcut[0], self.shortcut[1])
+        self.group_norm = norm == "group"
+        if not self.group_norm:
+            pair_conv_bn(self.conv1, self.bn1)
+            pair_conv_bn(self.conv2, self.bn2)
+            if len(self.shortcut):
+                pair_conv_bn(self.shortcut[0], self.shortcut[1])
 
     def forward(self, x):
+        if self.group_norm:
+            # conv -> gn(+ReLU), conv -> gn(+ residual + ReLU); the shortcut's GroupNorm output is
+            # the residual of the main branch's pass.  No twins: autograd sums x's two gradients
+            if len(self.shortcut):
+                c1, sc = LF.conv2d_pair(x, LF.shortcut_input(x), self.conv1, self.shortcut[0])
+                res = self.shortcut[1].act(sc)
+            else:
+                c1, res = self.conv1(x), LF.shortcut_input(x)
+            return self.bn2.act(self.conv2(self.bn1.act(c1, relu=True)), residual=res, relu=True)
         # BAR/model.py:67-72 with BN+ReLU and BN+residual-add+ReLU each fused into one pass;
         # the shortcut reads x's twin (LF.shortcut_input), so the producer of x sums the two
         # branch gradients in its own backward kernels instead of a separate add
@@ -75,17 +89,19 @@ def _head(x, pool, fc, drop=None):
 
 
 class EnhancedCNNModel(nn.Module):
-    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0):
+    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
+                 gn_groups: int = 32):
         super().__init__()
+        nk = dict(norm=norm, gn_groups=gn_groups)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
-            BatchNorm2d(64),
+            make_norm(norm, 64, gn_groups),
             ReLU(),
         )
-        self.layer1 = nn.Sequential(ResBlock(64, 128, stride=2), ResBlock(128, 128, stride=1))
-        self.layer2 = nn.Sequential(ResBlock(128, 256, stride=2), ResBlock(256, 256, stride=1))
-        self.layer3 = nn.Sequential(ResBlock(256, 512, stride=2), ResBlock(512, 512, stride=1))
-        self.layer4 = nn.Sequential(ResBlock(512, 1024, stride=2), ResBlock(1024, 1024, stride=1))
+        self.layer1 = nn.Sequential(ResBlock(64, 128, stride=2, **nk), ResBlock(128, 128, stride=1, **nk))
+        self.layer2 = nn.Sequential(ResBlock(128, 256, stride=2, **nk), ResBlock(256, 256, stride=1, **nk))
+        self.layer3 = nn.Sequential(ResBlock(256, 512, stride=2, **nk), ResBlock(512, 512, stride=1, **nk))
+        self.layer4 = nn.Sequential(ResBlock(512, 1024, stride=2, **nk), ResBlock(1024, 1024, stride=1, **nk))
         self.pool = AdaptiveAvgPool2d(1)
         self.fc = Linear(1024, num_classes)
         if dropout:   # (none constructed at rate 0: named_modules() stay the reference's)
@@ -103,16 +119,18 @@ class EnhancedCNNModel(nn.Module):
 class EnhancedCNNSmall(nn.Module):
     """The reference's commented-out smaller model (BAR/model.py:4-50)."""
 
-    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0):
+    def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
+                 gn_groups: int = 32):
         super().__init__()
+        nk = dict(norm=norm, gn_groups=gn_groups)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
-            BatchNorm2d(64),
+            make_norm(norm, 64, gn_groups),
             ReLU(),
         )
-        self.layer1 = ResBlock(64, 128, stride=2)
-        self.layer2 = ResBlock(128, 256, stride=2)
-        self.layer3 = ResBlock(256, 512, stride=2)
+        self.layer1 = ResBlock(64, 128, stride=2, **nk)
+        self.layer2 = ResBlock(128, 256, stride=2, **nk)
+        self.layer3 = ResBlock(256, 512, stride=2, **nk)
         self.pool = AdaptiveAvgPool2d(1)
         self.fc = Linear(512, num_classes)
         if dropout:

@@ -179,6 +179,39 @@ class BatchNorm2d(nn.BatchNorm2d):
         return LF.batch_norm_act(x, self, residual, relu)
 
 
+class GroupNorm(nn.GroupNorm):
+    """nn.GroupNorm (its parameter names and init; no buffers) with the surface of
+    ``BatchNorm2d``: statistics per sample and channel group, so the result does not depend on
+    which samples share a batch and train and eval mode are the same function.  On the GPU fp32
+    statistics over NHWC bf16 activations in the native kernels (group_norm.hip), with optional
+    residual-add + ReLU fused into the same pass (``act``)."""
+
+    def __init__(self, num_groups, num_channels, eps: float = 1e-5, affine: bool = True, device=None, dtype=None):
+        super().__init__(num_groups, num_channels, eps=eps, affine=affine, device=device, dtype=dtype)
+        self._ldnn_flat = None
+
+    def forward(self, x):
+        return LF.group_norm_act(x, self)
+
+    def act(self, x, residual=None, relu: bool = False):
+        """relu?(gn(x) + residual) in one fused pass."""
+        return LF.group_norm_act(x, self, residual, relu)
+
+
+NORMS = ("batch", "group")
+
+
+def make_norm(norm: str, channels: int, gn_groups: int = 32):
+    """The normalisation layer of a CNN: ``BatchNorm2d(channels)`` or ``GroupNorm(gn_groups, channels)``."""
+    if norm == "batch":
+        return BatchNorm2d(channels)
+    if norm != "group":
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+    if gn_groups < 1 or channels % gn_groups:
+        raise ValueError(f"gn_groups={gn_groups} does not divide the {channels} channels of a normalised layer")
+    return GroupNorm(gn_groups, channels)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def forward(self, x):
         return LF.pool2d(x, self, True)

@@ -7,27 +7,36 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..ops import functional as LF
-from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, pair_conv_bn
+from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, make_norm, pair_conv_bn
 
 
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, norm: str = "batch", gn_groups: int = 32):
         super().__init__()
         self.conv1 = Conv2d(inplanes, planes, 3, stride, 1, bias=False)
-        self.bn1 = BatchNorm2d(planes)
+        self.bn1 = make_norm(norm, planes, gn_groups)
         self.relu = ReLU()
         self.conv2 = Conv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = BatchNorm2d(planes)
+        self.bn2 = make_norm(norm, planes, gn_groups)
         self.downsample = downsample
-        pair_conv_bn(self.conv1, self.bn1)
-        pair_conv_bn(self.conv2, self.bn2)
-        if downsample is not None:
-            pair_conv_bn(downsample[0], downsample[1])
+        self.group_norm = norm == "group"
+        if not self.group_norm:
+            pair_conv_bn(self.conv1, self.bn1)
+            pair_conv_bn(self.conv2, self.bn2)
+            if downsample is not None:
+                pair_conv_bn(downsample[0], downsample[1])
 
     def forward(self, x):
         xs = LF.shortcut_input(x)   # (x's twin: see models/cnn.py ResBlock)
+        if self.group_norm:   # (as models/cnn.py ResBlock: the shortcut GroupNorm's output is the residual)
+            if self.downsample is not None:
+                c1, sc = LF.conv2d_pair(x, xs, self.conv1, self.downsample[0])
+                xs = self.downsample[1].act(sc)
+            else:
+                c1 = self.conv1(x)
+            return self.bn2.act(self.conv2(self.bn1.act(c1, relu=True)), residual=xs, relu=True)
         if self.downsample is not None:
             # conv1 and the 1x1 shortcut conv of x in one launch; conv2's BN, the shortcut BN, the add
             # and the ReLU in one pass
@@ -39,14 +48,17 @@ class BasicBlock(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=1000, in_channels=3, width=64, dropout: float = 0.0):
+    def __init__(self, layers=(2, 2, 2, 2), num_classes=1000, in_channels=3, width=64, dropout: float = 0.0,
+                 norm: str = "batch", gn_groups: int = 32):
         super().__init__()
         self.inplanes = width
+        self._norm = dict(norm=norm, gn_groups=gn_groups)
         self.conv1 = Conv2d(in_channels, width, 7, 2, 3, bias=False)
-        self.bn1 = BatchNorm2d(width)
+        self.bn1 = make_norm(norm, width, gn_groups)
         self.relu = ReLU()
         self.maxpool = MaxPool2d(3, 2, 1)
-        pair_conv_bn(self.conv1, self.bn1)
+        if norm == "batch":
+            pair_conv_bn(self.conv1, self.bn1)
         self.layer1 = self._make(width, layers[0], 1)
         self.layer2 = self._make(width * 2, layers[1], 2)
         self.layer3 = self._make(width * 4, layers[2], 2)
@@ -58,21 +70,25 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
     def _make(self, planes, blocks, stride):
         down = None
         if stride != 1 or self.inplanes != planes:
-            down = nn.Sequential(Conv2d(self.inplanes, planes, 1, stride, bias=False), BatchNorm2d(planes))
-        layers = [BasicBlock(self.inplanes, planes, stride, down)]
+            down = nn.Sequential(Conv2d(self.inplanes, planes, 1, stride, bias=False),
+                                 make_norm(channels=planes, **self._norm))
+        layers = [BasicBlock(self.inplanes, planes, stride, down, **self._norm)]
         self.inplanes = planes
-        layers += [BasicBlock(planes, planes) for _ in range(1, blocks)]
+        layers += [BasicBlock(planes, planes, **self._norm) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = LF.bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)   # maxpool(relu(bn1(conv1 x)))
+        if self._norm["norm"] == "group":
+            x = self.maxpool(self.bn1.act(self.conv1(x), relu=True))
+        else:
+            x = LF.bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)   # maxpool(relu(bn1(conv1 x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         if hasattr(self, "drop"):
@@ -80,5 +96,5 @@ class ResNet(nn.Module):
         return self.fc(x)
 
 
-def resnet18(num_classes=1000, in_channels=3, dropout=0.0):
-    return ResNet((2, 2, 2, 2), num_classes, in_channels, dropout=dropout)
+def resnet18(num_classes=1000, in_channels=3, dropout=0.0, norm: str = "batch", gn_groups: int = 32):
+    return ResNet((2, 2, 2, 2), num_classes, in_channels, dropout=dropout, norm=norm, gn_groups=gn_groups)

@@ -874,6 +874,109 @@ def batch_norm2d(x, mod):
     return F.batch_norm(x.float(), rm, rv, mod.weight, mod.bias, training, mom, mod.eps)
 
 
+# ------------------------------------------------------------------ GroupNorm
+def _gn_workspace(mod, n: int, dev) -> torch.Tensor:
+    """The module's persistent GroupNorm scratch (slab partials + coefficients; nothing in it is
+    kept between launches or needs zeroing).  It grows with the largest call seen, so a captured
+    step -- warmed up at its own shape first -- allocates nothing new."""
+    ws = mod.__dict__.get("_ldnn_gn_ws")
+    if ws is None or ws.device != dev or ws.numel() < n:
+        ws = mod.__dict__["_ldnn_gn_ws"] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
+def _dense_nhwc(t: torch.Tensor) -> bool:
+    """A logical [N, C, H, W] bf16 tensor that is a view of a dense, 16-byte aligned NHWC buffer
+    (what every native conv / norm / pool op returns)."""
+    if t.dtype != torch.bfloat16 or t.dim() != 4:
+        return False
+    N, C, H, W = t.shape
+    want = (H * W * C, 1, W * C, C)
+    return (all(sz == 1 or st == w for sz, st, w in zip(t.shape, t.stride(), want))
+            and t.numel() > 0 and t.data_ptr() % 16 == 0)
+
+
+class _GroupNormNative(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, mod, flat, relu):
+        C_ = _ext.C()
+        N, C, H, W = x.shape
+        G, dev = mod.num_groups, x.device
+        xb = x.as_strided((N, H, W, C), (H * W * C, W * C, C, 1), x.storage_offset())
+        rb = None
+        if residual is not None:
+            rb = as_nhwc(residual if residual.dtype == torch.bfloat16 else residual.to(torch.bfloat16), C,
+                         zero_pad=False)
+        y = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=dev)
+        ws = _gn_workspace(mod, C_.gn_workspace_floats(N, H * W, C, G), dev)
+        mean = torch.empty(N * G, dtype=torch.float32, device=dev)
+        rstd = torch.empty(N * G, dtype=torch.float32, device=dev)
+        gamma = flat.master_storage(weight)[:C] if weight is not None else None
+        beta = flat.master_storage(bias)[:C] if bias is not None else None
+        # the ReLU leaves a bit mask for the backward (which then never reads y); only when one will run
+        mask = (torch.empty(N * H * W * C // 8, dtype=torch.uint8, device=dev)
+                if relu and any(ctx.needs_input_grad) else None)
+        C_.gn_fwd(xb, y, rb, gamma, beta, mean, rstd, ws, G, mod.eps, relu, mask=mask)
+        ctx.save_for_backward(xb, mean, rstd)
+        ctx.mask = mask
+        ctx.meta = (flat, weight, bias, mod, G, residual is not None, residual.dtype if residual is not None else None)
+        ctx.set_materialize_grads(False)
+        return _zpad(nchw_view(y, C))
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return (None,) * 7
+        C_ = _ext.C()
+        xb, mean, rstd = ctx.saved_tensors
+        flat, weight, bias, mod, G, has_res, res_dtype = ctx.meta
+        N, H, W, C = xb.shape
+        g = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), C, zero_pad=False).contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        dx = torch.empty_like(xb)
+        dres = torch.empty_like(xb) if has_res and ctx.needs_input_grad[3] else None
+        gamma = flat.master_storage(weight)[:C] if weight is not None else None
+        dg = flat.grad_storage(weight)[:C] if weight is not None else None
+        db = flat.grad_storage(bias)[:C] if bias is not None else None
+        # first write of the step: the finalize stores dgamma / dbeta instead of adding
+        fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias)) if p is not None]
+        assign = all(f for _, f in fresh)
+        if not assign:   # mixed (only if a caller accumulated one of them): clear the fresh ones
+            for t, f in fresh:
+                if f:
+                    t.zero_()
+        ws = _gn_workspace(mod, C_.gn_workspace_floats(N, H * W, C, G), xb.device)
+        C_.gn_bwd(xb, g, dx, dres, gamma, mean, rstd, ws, dg, db, G, ctx.mask is not None, mask=ctx.mask,
+                  grad_assign=assign)
+        if flat is not None:
+            flat.notify(weight, bias)
+        dresv = nchw_view(dres, C) if dres is not None else None
+        if dresv is not None and res_dtype != torch.bfloat16:
+            dresv = dresv.to(res_dtype)
+        return _zpad(nchw_view(dx, C)), None, None, dresv, None, None, None
+
+
+def group_norm_act(x, mod, residual=None, relu: bool = False):
+    """relu?(GroupNorm(x) (+ residual)) with ``mod``'s (nn.GroupNorm) groups, eps and affine
+    parameters.  GPU, bf16 activations in the dense NHWC layout the native ops produce,
+    C % 8 == 0: the native passes of group_norm.hip (fp32 statistics per sample and group, the add
+    and the ReLU fused into the apply pass; gamma / beta read from the FlatParams master, their
+    gradients written into the flat gradient buffer).  Everything else -- the CPU, other dtypes or
+    layouts, other channel counts, a module not attached to FlatParams -- is F.group_norm in fp32
+    plus the add and the ReLU.  Statistics are per sample: train and eval mode are one function."""
+    flat = getattr(mod, "_ldnn_flat", None)
+    if (_ext.use_native(x) and _dense_nhwc(x) and x.shape[1] % 8 == 0 and x.shape[0] <= 65535
+            and (not mod.affine or flat is not None)):
+        return _GroupNormNative.apply(x, mod.weight, mod.bias, residual, mod, flat, relu)
+    y = F.group_norm(x.float(), mod.num_groups, mod.weight, mod.bias, mod.eps)
+    if residual is not None:
+        y = y + residual
+    if relu:
+        y = F.relu(y)
+    return y.to(torch.bfloat16) if x.is_cuda and x.dtype == torch.bfloat16 else y
+
+
 # ------------------------------------------------------------------ pooling
 class _PoolNative(torch.autograd.Function):
     @staticmethod

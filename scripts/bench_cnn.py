@@ -60,6 +60,9 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="dropout rate of the ldnn model (build_model's keyword: the dropout.hip pass each way at the "
                          "model's dropout sites; 0 = off, no module is built); the stock baseline has none")
+    ap.add_argument("--norm", choices=["batch", "group"], default="batch",
+                    help="normalisation layer of the ldnn model and of the stock baseline (build_model's keyword; "
+                         "group: GroupNorm, 32 groups, the group_norm.hip passes)")
     ap.add_argument("--targets", choices=["hard", "soft", "mix"], default="hard",
                     help="ldnn step: hard = class indices; soft = a pre-mixed batch's class-probability targets "
                          "[B, C] (the loss kernel's soft-target instance); mix = soft plus the batch-mix pass "
@@ -75,7 +78,7 @@ def main():
     y = torch.randint(0, nc, (a.batch,), device="cuda")
 
     torch.manual_seed(0)
-    m = build_model(a.model, dropout=a.dropout)
+    m = build_model(a.model, dropout=a.dropout, norm=a.norm)
     xavier_init(m)
     ldnn.prepare(m, "cuda")
     ldnn.reseed_dropout(m, 0)
@@ -131,7 +134,7 @@ def main():
             gs(*feed())
 
     t = run(step_ldnn, a.steps, a.warmup)
-    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "lr_schedule": a.lr_schedule, "dropout": a.dropout, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
+    rec = {"model": a.model, "batch": a.batch, "optimizer": a.optimizer, "conv_impl": a.conv_impl, "graph": a.graph, "clip": a.clip, "lars": a.lars, "label_smoothing": a.label_smoothing, "ema_decay": a.ema_decay, "lr_schedule": a.lr_schedule, "dropout": a.dropout, "norm": a.norm, "targets": a.targets, "ldnn_ms": round(t * 1e3, 3), "ldnn_samples_per_s": round(a.batch / t, 1)}
     if a.lars > 0:   # (the ratios the timed steps ended on: near 1 keeps the math comparable with --lars 0)
         ls = opt.lars_stats()
         r = ls["ratio"].cpu()[torch.tensor(ls["adapted"])]
@@ -140,7 +143,7 @@ def main():
         import torch.nn as nn
 
         torch.manual_seed(0)
-        ref = build_model(a.model)
+        ref = build_model(a.model, norm=a.norm)
         # swap ldnn layers for stock torch behaviour: run the CPU/fp32 code path under autocast
         ref = ref.cuda().to(memory_format=torch.channels_last)
         os.environ["LDNN_DISABLE_NATIVE"] = "1"
