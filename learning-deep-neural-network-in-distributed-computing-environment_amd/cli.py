@@ -87,12 +87,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "EnhancedCNNs, in one native pass each way (dropout.hip) whose mask is a counter hash of "
                         "(--seed, rank, global epoch, module, step): nothing is stored for the backward, a resumed run "
                         "replays the masks, and validation and the final test run without it")
-    p.add_argument("--norm", choices=["batch", "group"], default="batch",
+    p.add_argument("--norm", choices=["batch", "group", "layer"], default="batch",
                    help="normalisation layer of the EnhancedCNNs and ResNets: batch (default, BatchNorm2d) or group "
                         "(GroupNorm under the same parameter names: statistics per sample, so the result does not "
                         "depend on which samples share a batch; no running statistics, train and eval are the same "
                         "function; native NHWC bf16 passes with the residual add and the ReLU fused, group_norm.hip).  "
-                        "The MLPs and LeNet-5 have no normalisation layer and refuse group")
+                        "The MLPs and LeNet-5 have no normalisation layer and refuse group.  layer: the MLPs only -- a "
+                        "LayerNorm over the width after every hidden Linear, with the activation fused (statistics per "
+                        "row, native bf16 row passes, layer_norm.hip); every other model refuses it")
     p.add_argument("--gn_groups", type=int, default=32, metavar="G",
                    help="--norm group: number of channel groups (default 32); must divide every normalised width")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
@@ -265,6 +267,8 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "norm", "batch") == "group":
         # the static engine is a chain of GEMMs: it has no normalisation pass
         why = "--norm group runs on the autograd path"
+    elif getattr(args, "norm", "batch") == "layer":
+        why = "--norm layer runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -325,7 +329,10 @@ def main(argv=None):
     for flag, v in (("--mix_prob", args.mix_prob), ("--mix_switch_prob", args.mix_switch_prob)):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} must be in [0, 1], got {v}")
-    from .models import NORM_MODELS
+    from .models import LAYER_NORM_MODELS, NORM_MODELS
+    if args.norm == "layer" and args.model not in LAYER_NORM_MODELS:
+        raise SystemExit(f"--norm layer: LayerNorm is built for the MLPs ({', '.join(LAYER_NORM_MODELS)}), "
+                         f"not for --model {args.model}")
     if args.norm == "group" and args.model not in NORM_MODELS:
         raise SystemExit(f"--norm group: --model {args.model} has no normalisation layer "
                          f"(models with one: {', '.join(NORM_MODELS)})")

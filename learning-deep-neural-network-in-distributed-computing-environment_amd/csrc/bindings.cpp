@@ -1840,6 +1840,91 @@ void gn_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, con
         "gn_backward");
 }
 
+// ---- LayerNorm: x, y, dy, dx logical [B][N] bf16 matrices with unit column stride, row strides that are
+// multiples of 8 and 16-byte aligned bases (a dense matrix with N % 8 == 0, or the [B][N] view of a padded
+// [B][ld] buffer); gamma, beta, dgamma, dbeta fp32 of at least N rounded up to 8 elements (the FlatParams
+// storage of a 1-D parameter); mean, rstd fp32 [B]
+int64_t ln_up8(int64_t n) { return (n + 7) / 8 * 8; }
+
+// Row stride of a LayerNorm operand.  The kernels read a row's last 16-byte vector whole and write an
+// output row's pad columns up to the stride: the storage must hold that.
+int64_t ln_ld(const at::Tensor& t, const at::Tensor& x, const char* name, bool output) {
+  check_dev(t, at::kBFloat16, name);
+  TORCH_CHECK(t.dim() == 2 && t.numel() > 0, "layer_norm: ", name, " must be a non-empty [B][N] matrix");
+  TORCH_CHECK(t.sizes() == x.sizes(), "layer_norm: ", name, " must have x's shape");
+  TORCH_CHECK(t.device() == x.device(), "layer_norm: ", name, " is on another device than x");
+  const int64_t B = t.size(0), N = t.size(1);
+  TORCH_CHECK(N == 1 || t.stride(1) == 1, "layer_norm: ", name, " must have a unit column stride");
+  const int64_t ld = B == 1 ? ln_up8(N) : t.stride(0);   // (a single row's stride is arbitrary)
+  TORCH_CHECK(ld >= N && ld % 8 == 0, "layer_norm: the row stride of ", name, " (", ld,
+              ") must be a multiple of 8 and at least N = ", N);
+  TORCH_CHECK(aligned16(t.data_ptr()), "layer_norm: ", name, " must be 16-byte aligned");
+  const int64_t have = (int64_t)(t.storage().nbytes() / 2) - t.storage_offset();
+  const int64_t need = output ? B * ld : (B - 1) * ld + ln_up8(N);
+  TORCH_CHECK(need <= have, "layer_norm: the storage of ", name, " does not hold ", B, " rows of stride ", ld);
+  return ld;
+}
+
+float* ln_vec(const c10::optional<at::Tensor>& t, int64_t n, const at::Tensor& x, const char* name) {
+  float* p = fptr_opt(t, n, name);
+  if (p != nullptr) {
+    TORCH_CHECK(t->device() == x.device(), "layer_norm: ", name, " is on another device than x");
+    TORCH_CHECK(aligned16(p), "layer_norm: ", name, " must be 16-byte aligned");
+  }
+  return p;
+}
+
+ldnn::LnArgs ln_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
+                     const c10::optional<at::Tensor>& beta, const at::Tensor& mean, const at::Tensor& rstd,
+                     int64_t act) {
+  ldnn::LnArgs a{};
+  a.ld_x = ln_ld(x, x, "x", false);
+  a.x = bf16_ptr(x);
+  a.B = x.size(0), a.N = x.size(1);
+  TORCH_CHECK(a.N <= ldnn::ln_max_width(), "layer_norm: N = ", a.N, " is wider than the native kernels' ",
+              ldnn::ln_max_width(), " columns");
+  TORCH_CHECK(act >= ldnn::LN_ACT_NONE && act <= ldnn::LN_ACT_SIGMOID, "layer_norm: act must be -1 (none), 0 (relu) ",
+              "or 1 (sigmoid), got ", act);
+  TORCH_CHECK(gamma.has_value() == beta.has_value(), "layer_norm: gamma and beta come together");
+  a.gamma = ln_vec(gamma, ln_up8(a.N), x, "gamma");
+  a.beta = ln_vec(beta, ln_up8(a.N), x, "beta");
+  a.mean = ln_vec(mean, a.B, x, "mean");
+  a.rstd = ln_vec(rstd, a.B, x, "rstd");
+  a.act = (int)act;
+  return a;
+}
+
+void ln_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& gamma,
+            const c10::optional<at::Tensor>& beta, const at::Tensor& mean, const at::Tensor& rstd, double eps,
+            int64_t act) {
+  ldnn::LnArgs a = ln_args(x, gamma, beta, mean, rstd, act);
+  a.eps = (float)eps;
+  const int64_t ld_y = ln_ld(y, x, "y", true);
+  TORCH_CHECK(y.data_ptr() != x.data_ptr(), "ln_fwd: in-place is not supported");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check(ldnn::ln_forward(a, bf16_mut(y), ld_y, cur_stream(x)), "ln_forward");
+}
+
+void ln_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, const c10::optional<at::Tensor>& gamma,
+            const c10::optional<at::Tensor>& beta, const at::Tensor& mean, const at::Tensor& rstd,
+            const c10::optional<at::Tensor>& ws, const c10::optional<at::Tensor>& dgamma,
+            const c10::optional<at::Tensor>& dbeta, int64_t act, bool grad_assign) {
+  ldnn::LnArgs a = ln_args(x, gamma, beta, mean, rstd, act);
+  const int64_t ld_dy = ln_ld(dy, x, "dy", false), ld_dx = ln_ld(dx, x, "dx", true);
+  TORCH_CHECK(dx.data_ptr() != x.data_ptr() && dx.data_ptr() != dy.data_ptr(), "ln_bwd: in-place is not supported");
+  TORCH_CHECK(dgamma.has_value() == dbeta.has_value(), "ln_bwd: dgamma and dbeta come together");
+  TORCH_CHECK(dgamma.has_value() == gamma.has_value(), "ln_bwd: dgamma / dbeta belong to an affine layer's gamma / beta");
+  float* w = nullptr;
+  if (gamma.has_value()) {
+    TORCH_CHECK(ws.has_value(), "ln_bwd: an affine layer needs the workspace");
+    w = ln_vec(ws, ldnn::ln_workspace_floats(a.B, a.N), x, "ws");
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::ln_backward(a, bf16_ptr(dy), ld_dy, bf16_mut(dx), ld_dx, w, ln_vec(dgamma, ln_up8(a.N), x, "dgamma"),
+                          ln_vec(dbeta, ln_up8(a.N), x, "dbeta"), grad_assign, cur_stream(x)),
+        "ln_backward");
+}
+
 // x [N][H][W][C], y [N][P][Q][C] dense bf16; argmax uint8 [N][P][Q][C] for max pooling
 void pool_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& argmax, int64_t R,
               int64_t S, int64_t stride, int64_t pad, bool is_max, bool nchw_out) {
@@ -2597,6 +2682,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("N"), py::arg("P"), py::arg("C"), py::arg("G"));
   m.def("gn_slabs", &ldnn::gn_slabs, "pixel slabs per sample of the GroupNorm statistics passes", py::arg("N"),
         py::arg("P"), py::arg("C"), py::arg("G"));
+  m.def("ln_fwd", &ln_fwd, "y = act(layer_norm(x)) over the rows of a [B][N] bf16 matrix; writes mean / rstd [B]",
+        py::arg("x"), py::arg("y"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"),
+        py::arg("eps"), py::arg("act"));
+  m.def("ln_bwd", &ln_bwd, "backward of ln_fwd: dx; dgamma / dbeta stored (grad_assign) or added",
+        py::arg("x"), py::arg("dy"), py::arg("dx"), py::arg("gamma"), py::arg("beta"), py::arg("mean"),
+        py::arg("rstd"), py::arg("ws"), py::arg("dgamma"), py::arg("dbeta"), py::arg("act"),
+        py::arg("grad_assign") = false);
+  m.def("ln_workspace_floats", &ldnn::ln_workspace_floats, "fp32 scratch of an affine LayerNorm backward",
+        py::arg("B"), py::arg("N"));
+  m.def("ln_max_width", &ldnn::ln_max_width, "widest row of the native LayerNorm kernels");
   m.def("pool_fwd", &pool_fwd, py::arg("x"), py::arg("y"), py::arg("argmax"), py::arg("R"), py::arg("S"),
         py::arg("stride"), py::arg("pad"), py::arg("is_max"), py::arg("nchw_out") = false);
   m.def("pool_bwd", &pool_bwd, py::arg("dy"), py::arg("argmax"), py::arg("dx"), py::arg("R"), py::arg("S"),

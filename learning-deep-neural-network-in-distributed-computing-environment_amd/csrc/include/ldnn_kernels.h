@@ -327,6 +327,28 @@ hipError_t gn_forward(const GnArgs& a, hipStream_t s);
 hipError_t gn_backward(const GnArgs& a, const uint16_t* dy, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
                        bool grad_assign, hipStream_t s);
 
+// ---- LayerNorm over the last dimension of a logical [B][N] bf16 matrix (layer_norm.hip), activation fused
+// Row strides ld >= N in elements, ld % 8 == 0, bases 16-byte aligned; N <= ln_max_width(), any N >= 1
+// (the last vector's lanes beyond N are selected away and may hold anything, NaN included).  The
+// outputs' pad columns N <= c < ld are written as zeros.  No atomics: a shape has one summation order.
+enum LnAct : int { LN_ACT_NONE = -1, LN_ACT_RELU = 0, LN_ACT_SIGMOID = 1 };   // (relu / sigmoid as Act)
+struct LnArgs {
+  const uint16_t* x;     // [B][N], row stride ld_x
+  const float* gamma;    // [up8(N)] (only the first N are used); both null: no affine
+  const float* beta;
+  float* mean;           // [B] written by the forward, read by the backward
+  float* rstd;
+  int64_t B, N, ld_x;
+  float eps;
+  int act;               // LnAct
+};
+int ln_max_width();                                   // widest native row
+int64_t ln_workspace_floats(int64_t B, int64_t N);    // fp32 scratch of a backward with dgamma / dbeta
+hipError_t ln_forward(const LnArgs& a, uint16_t* y, int64_t ld_y, hipStream_t s);
+// dx; dgamma / dbeta ([N], exactly when gamma / beta are given) stored when grad_assign, else added
+hipError_t ln_backward(const LnArgs& a, const uint16_t* dy, int64_t ld_dy, uint16_t* dx, int64_t ld_dx, float* ws,
+                       float* dgamma, float* dbeta, bool grad_assign, hipStream_t s);
+
 // ---- elementwise / activations (bf16 storage, fp32 math) ---------------------
 enum Act : int { ACT_RELU = 0, ACT_SIGMOID = 1 };
 hipError_t act_fwd(const uint16_t* x, uint16_t* y, int64_t n, int act, hipStream_t s);

@@ -198,7 +198,31 @@ class GroupNorm(nn.GroupNorm):
         return LF.group_norm_act(x, self, residual, relu)
 
 
-NORMS = ("batch", "group")
+class LayerNorm(nn.LayerNorm):
+    """nn.LayerNorm over the last dimension (its parameter names and init; no buffers) for the [B, N]
+    activations of the MLPs: statistics per row, so the result does not depend on which samples share
+    a batch and train and eval mode are the same function.  On the GPU fp32 statistics over bf16 rows
+    in the native kernels (layer_norm.hip), with the layer's activation fused into the same pass
+    (``act``)."""
+
+    def __init__(self, normalized_shape: int, eps: float = 1e-5, elementwise_affine: bool = True, device=None,
+                 dtype=None):
+        if not isinstance(normalized_shape, int):
+            raise ValueError("ldnn LayerNorm normalises the last dimension: normalized_shape must be an int, got "
+                             f"{normalized_shape!r}")
+        super().__init__(normalized_shape, eps=eps, elementwise_affine=elementwise_affine, device=device, dtype=dtype)
+        self._ldnn_flat = None
+
+    def forward(self, x):
+        return LF.layer_norm_act(x, self)
+
+    def act(self, x, act: str = "none"):
+        """act(ln(x)) in one fused pass; ``act`` in none | relu | sigmoid."""
+        return LF.layer_norm_act(x, self, act)
+
+
+# "batch" and "group" are the CNNs' choices (make_norm), "layer" the MLPs' (models/mlp.py)
+NORMS = ("batch", "group", "layer")
 
 
 def make_norm(norm: str, channels: int, gn_groups: int = 32):
@@ -206,7 +230,7 @@ def make_norm(norm: str, channels: int, gn_groups: int = 32):
     if norm == "batch":
         return BatchNorm2d(channels)
     if norm != "group":
-        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+        raise ValueError(f"the normalisation layer of a CNN is 'batch' or 'group', got {norm!r}")
     if gn_groups < 1 or channels % gn_groups:
         raise ValueError(f"gn_groups={gn_groups} does not divide the {channels} channels of a normalised layer")
     return GroupNorm(gn_groups, channels)

@@ -977,6 +977,134 @@ def group_norm_act(x, mod, residual=None, relu: bool = False):
     return y.to(torch.bfloat16) if x.is_cuda and x.dtype == torch.bfloat16 else y
 
 
+# ------------------------------------------------------------------ LayerNorm
+def _ln_workspace(mod, n: int, dev) -> torch.Tensor:
+    """The module's persistent LayerNorm scratch (the backward's dgamma / dbeta partial rows; nothing
+    in it is kept between launches or needs zeroing).  It grows with the largest call seen, so a
+    captured step -- warmed up at its own shape first -- allocates nothing new."""
+    ws = mod.__dict__.get("_ldnn_ln_ws")
+    if ws is None or ws.device != dev or ws.numel() < n:
+        ws = mod.__dict__["_ldnn_ln_ws"] = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    return ws
+
+
+def _ln_ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else _up8(t.shape[1])   # (a single row's stride is arbitrary)
+
+
+def _ln_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` ([B, N] bf16) as an operand of the LayerNorm kernels: itself when it is a view with a unit
+    column stride, a row stride that is a multiple of 8 (and no more than twice the row: a column
+    slice of a much wider matrix is not worth an output of that stride), a 16-byte aligned base and a
+    storage that holds every row's last vector whole -- what an ldnn ``Linear`` hands on, or a dense
+    matrix with N % 8 == 0.  Anything else is copied once into the [B, N] view of a [B, up8(N)]
+    buffer (whose pad columns may hold anything: the kernels select them away)."""
+    B, N = t.shape
+    npad, ld = _up8(N), _ln_ld(t)
+    if ((t.stride(1) == 1 or N == 1) and ld % 8 == 0 and npad <= ld <= 2 * npad and t.data_ptr() % 16 == 0
+            and t.storage_offset() + (B - 1) * ld + npad <= t.untyped_storage().nbytes() // t.element_size()):
+        return t
+    buf = torch.empty(B, npad, dtype=torch.bfloat16, device=t.device)
+    v = buf if npad == N else buf[:, :N]
+    v.copy_(t)
+    return v
+
+
+def _ln_out_like(x2: torch.Tensor) -> torch.Tensor:
+    """The output operand for ``x2``: the [B, N] view of a fresh buffer with x2's row stride."""
+    B, N = x2.shape
+    ld = _ln_ld(x2)
+    buf = torch.empty(B, ld, dtype=torch.bfloat16, device=x2.device)
+    return buf if ld == N else buf[:, :N]
+
+
+class _LayerNormNative(torch.autograd.Function):
+    """layer_norm.hip: the forward saves x, mean and rstd; the backward recomputes the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, flat, act):
+        C_ = _ext.C()
+        x2 = _ln_rows(x)
+        B, N = x2.shape
+        y = _ln_out_like(x2)
+        mean = torch.empty(B, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(B, dtype=torch.float32, device=x.device)
+        # the padded fp32 master storage (up8(N) floats; the kernels use the first N)
+        gamma = flat.master_storage(weight) if weight is not None else None
+        beta = flat.master_storage(bias) if bias is not None else None
+        C_.ln_fwd(x2, y, gamma, beta, mean, rstd, mod.eps, -1 if act is None else act)
+        ctx.save_for_backward(x2, mean, rstd)
+        ctx.meta = (flat, weight, bias, mod, act)
+        if y.stride(0) != N:
+            y._ldnn_zpad = True   # the kernel wrote the pad columns' zeros, also under sigmoid
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        C_ = _ext.C()
+        x2, mean, rstd = ctx.saved_tensors
+        flat, weight, bias, mod, act = ctx.meta
+        B, N = x2.shape
+        g = _ln_rows(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16))
+        dx = _ln_out_like(x2)
+        gamma = beta = dg = db = ws = None
+        assign = False
+        if weight is not None:
+            gamma, beta = flat.master_storage(weight), flat.master_storage(bias)
+            dg, db = flat.grad_storage(weight), flat.grad_storage(bias)
+            # first write of the step: the finalize stores dgamma / dbeta instead of adding
+            fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias))]
+            assign = all(f for _, f in fresh)
+            if not assign:   # mixed (only if a caller accumulated one of them): clear the fresh one
+                for t, f in fresh:
+                    if f:
+                        t.zero_()
+            ws = _ln_workspace(mod, C_.ln_workspace_floats(B, N), x2.device)
+        C_.ln_bwd(x2, g, dx, gamma, beta, mean, rstd, ws, dg, db, -1 if act is None else act, grad_assign=assign)
+        if weight is not None:
+            flat.notify(weight, bias)
+        return dx, None, None, None, None, None
+
+
+_LN_MAX_WIDTH = None
+
+
+def _ln_max_width() -> int:
+    global _LN_MAX_WIDTH
+    if _LN_MAX_WIDTH is None:
+        _LN_MAX_WIDTH = int(_ext.C().ln_max_width())
+    return _LN_MAX_WIDTH
+
+
+def layer_norm_act(x, mod, act: str = "none"):
+    """act(LayerNorm(x)) over the last dimension with ``mod``'s (nn.LayerNorm over one dimension) eps
+    and affine parameters; ``act`` in none | relu | sigmoid.  GPU, bf16, a 2-D activation with a unit
+    column stride and at most ``ln_max_width()`` columns: the native passes of layer_norm.hip (fp32
+    statistics per row, the activation fused; gamma / beta read from the FlatParams master, their
+    gradients written into the flat gradient buffer; only mean and rstd are saved).  A [B, N] view of
+    a padded buffer -- what an ldnn ``Linear`` hands on -- is processed in place of a copy and the
+    result is such a view with the input's row stride and zeroed pad columns, so the next ``Linear``
+    widens it without a copy or a fill.  Everything else -- the CPU, other dtypes or ranks, wider
+    rows, an affine module not attached to FlatParams -- is F.layer_norm in fp32 plus the activation.
+    Statistics are per row: train and eval mode are one function."""
+    a = ACTS[act]
+    N = x.shape[-1]
+    if len(mod.normalized_shape) != 1 or mod.normalized_shape[0] != N:
+        raise ValueError(f"layer_norm_act: the module normalises {tuple(mod.normalized_shape)}, the input's last "
+                         f"dimension is {N}")
+    flat = getattr(mod, "_ldnn_flat", None)
+    if (_ext.use_native(x) and x.dtype == torch.bfloat16 and x.dim() == 2 and x.numel() > 0
+            and (x.stride(1) == 1 or N == 1) and N <= _ln_max_width()
+            and (mod.weight is None or (flat is not None and mod.bias is not None))):
+        return _LayerNormNative.apply(x, mod.weight, mod.bias, mod, flat, a)
+    y = F.layer_norm(x.float(), (N,), mod.weight, mod.bias, mod.eps)
+    if a == 0:
+        y = F.relu(y)
+    elif a == 1:
+        y = torch.sigmoid(y)
+    return y.to(torch.bfloat16) if x.is_cuda and x.dtype == torch.bfloat16 else y
+
+
 # ------------------------------------------------------------------ pooling
 class _PoolNative(torch.autograd.Function):
     @staticmethod

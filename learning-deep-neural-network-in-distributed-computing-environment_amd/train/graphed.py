@@ -35,6 +35,10 @@ What makes the ldnn step capturable:
   reads the ticket its forward wrote in the same replay; ``reseed_dropout`` writes seed and
   count from the host between replays, and a changed ``module.p`` is written before a replay
   like a changed lr (a host compare per module) -- no capture bakes a rate or a seed in;
+* LayerNorm (models.layers.LayerNorm, ``norm="layer"``) needs no check either: it has no host
+  state at all.  eps and the activation are kernel arguments that never change, mean / rstd are
+  graph-pool tensors, gamma / beta are read from the flat master, and the module's workspace
+  (``_ldnn_ln_ws``) was sized by the warm-up steps, so capture and replay allocate nothing;
 * every native op writes into caller-provided / caching-allocator tensors
   (graph-pool allocations during capture).
 

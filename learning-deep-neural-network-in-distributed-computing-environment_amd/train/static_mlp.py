@@ -122,6 +122,8 @@ class StaticMLPEngine:
 
         if not isinstance(model, MLP):
             raise TypeError("StaticMLPEngine drives ldnn.models.mlp.MLP models")
+        if getattr(model, "norms", None):   # (a chain of GEMMs: there is no normalisation pass to run them in)
+            raise ValueError("StaticMLPEngine: a norm='layer' MLP runs on the autograd path")
         self.device = torch.device(device or "cuda")
         if not _ext.use_native(torch.empty(0, device=self.device)):
             raise RuntimeError("StaticMLPEngine needs the native extension on a GPU")

@@ -60,9 +60,10 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="dropout rate of the ldnn model (build_model's keyword: the dropout.hip pass each way at the "
                          "model's dropout sites; 0 = off, no module is built); the stock baseline has none")
-    ap.add_argument("--norm", choices=["batch", "group"], default="batch",
+    ap.add_argument("--norm", choices=["batch", "group", "layer"], default="batch",
                     help="normalisation layer of the ldnn model and of the stock baseline (build_model's keyword; "
-                         "group: GroupNorm, 32 groups, the group_norm.hip passes)")
+                         "group: GroupNorm, 32 groups, the group_norm.hip passes; layer: with --model mlp2 / mlp3 / "
+                         "mlp3_small, a LayerNorm after every hidden Linear, the layer_norm.hip passes)")
     ap.add_argument("--targets", choices=["hard", "soft", "mix"], default="hard",
                     help="ldnn step: hard = class indices; soft = a pre-mixed batch's class-probability targets "
                          "[B, C] (the loss kernel's soft-target instance); mix = soft plus the batch-mix pass "
