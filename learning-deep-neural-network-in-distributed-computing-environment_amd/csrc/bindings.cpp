@@ -1366,14 +1366,81 @@ ConvWs conv_ws(const ldnn::ConvShape& s, int op, const at::Tensor& like) {
   return w;
 }
 
-float* fptr_opt(const c10::optional<at::Tensor>& t, int64_t n, const char* name);
-const ldnn::BnFin* bn_fwd_fin(ldnn::BnFin& fin, const ldnn::ConvShape& s, const c10::optional<at::Tensor>& bn_ws,
-                              const c10::optional<at::Tensor>& bn_gamma, const c10::optional<at::Tensor>& bn_beta,
-                              const c10::optional<at::Tensor>& bn_running_mean,
-                              const c10::optional<at::Tensor>& bn_running_var,
-                              const c10::optional<at::Tensor>& bn_save_mean,
-                              const c10::optional<at::Tensor>& bn_save_invstd, double bn_eps, double bn_momentum,
-                              const c10::optional<at::Tensor>& bn_num_batches);
+using OptTensor = c10::optional<at::Tensor>;
+
+// Optional fp32 vector of at least n elements (nullptr when absent).  on: the tensor whose device it has to
+// share; align16: it is read with 16-byte loads.
+float* fptr_opt(const OptTensor& t, int64_t n, const char* name, const at::Tensor* on = nullptr,
+                bool align16 = false) {
+  if (!t.has_value()) return nullptr;
+  check_dev(*t, at::kFloat, name);
+  TORCH_CHECK(t->is_contiguous() && t->numel() >= n, name, ": bad tensor");
+  TORCH_CHECK(on == nullptr || t->device() == on->device(), name, " is on another device than its activations");
+  TORCH_CHECK(!align16 || aligned16(t->data_ptr()), name, " must be 16-byte aligned");
+  return t->data_ptr<float>();
+}
+
+// Optional bf16 operand laid out like ref: ref's sizes, dense (nullptr when absent).
+const uint16_t* like(const OptTensor& t, const at::Tensor& ref, const char* who, const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_dev(*t, at::kBFloat16, name);
+  TORCH_CHECK(t->sizes() == ref.sizes() && t->is_contiguous(), who, ": ", name, " must be dense, with the sizes of ",
+              ref.sizes());
+  return bf16_ptr(*t);
+}
+
+// Optional ReLU bit mask of `elems` activations: elems / 8 dense bytes (nullptr when absent).
+uint8_t* relu_mask(const OptTensor& mask, int64_t elems, const char* who) {
+  if (!mask.has_value()) return nullptr;
+  check_dev(*mask, at::kByte, "mask");
+  TORCH_CHECK(mask->is_contiguous() && mask->numel() == elems / 8, who, ": mask must be ", elems / 8, " dense bytes");
+  return mask->data_ptr<uint8_t>();
+}
+
+// What every BatchNorm binding fills into BnArgs from its [C] fp32 tensors; the site adds what is its own
+// (x, y, training, relu, mask, dy2) and the checks of the pointers it requires.
+ldnn::BnArgs bn_args(int64_t M, int64_t C, const OptTensor& gamma, const OptTensor& beta,
+                     const OptTensor& running_mean, const OptTensor& running_var, const OptTensor& save_mean,
+                     const OptTensor& save_invstd, const OptTensor& ws, double eps, double momentum,
+                     const OptTensor& num_batches) {
+  ldnn::BnArgs a{};
+  a.M = (int)M;
+  a.C = (int)C;
+  a.gamma = fptr_opt(gamma, C, "gamma");
+  a.beta = fptr_opt(beta, C, "beta");
+  a.running_mean = fptr_opt(running_mean, C, "running_mean");
+  a.running_var = fptr_opt(running_var, C, "running_var");
+  a.save_mean = fptr_opt(save_mean, C, "save_mean");
+  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
+  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
+  a.eps = (float)eps;
+  a.momentum = (float)momentum;
+  if (num_batches.has_value()) {
+    check_dev(*num_batches, at::kLong, "num_batches");
+    a.num_batches = num_batches->data_ptr<int64_t>();
+  }
+  return a;
+}
+// (a backward reads gamma, the saved statistics and the workspace)
+ldnn::BnArgs bn_bwd_args(int64_t M, int64_t C, const OptTensor& gamma, const OptTensor& save_mean,
+                         const OptTensor& save_invstd, const OptTensor& ws) {
+  return bn_args(M, C, gamma, c10::nullopt, c10::nullopt, c10::nullopt, save_mean, save_invstd, ws, 0.0, 0.0,
+                 c10::nullopt);
+}
+
+// The fused next-BN statistics state of a forward conv (nullptr without bn_ws).
+const ldnn::BnFin* bn_fwd_fin(ldnn::BnFin& fin, const ldnn::ConvShape& s, const OptTensor& bn_ws,
+                              const OptTensor& bn_gamma, const OptTensor& bn_beta, const OptTensor& bn_running_mean,
+                              const OptTensor& bn_running_var, const OptTensor& bn_save_mean,
+                              const OptTensor& bn_save_invstd, double bn_eps, double bn_momentum,
+                              const OptTensor& bn_num_batches) {
+  if (!bn_ws.has_value()) return nullptr;
+  const ldnn::BnArgs a = bn_args((int64_t)s.N * s.P * s.Q, s.K, bn_gamma, bn_beta, bn_running_mean, bn_running_var,
+                                 bn_save_mean, bn_save_invstd, bn_ws, bn_eps, bn_momentum, bn_num_batches);
+  TORCH_CHECK(a.save_mean && a.save_invstd, "conv: fused BN statistics need save_mean / save_invstd");
+  fin = ldnn::bn_forward_fin_conv(a);
+  return &fin;
+}
 
 // Returns whether the following BatchNorm's statistics were accumulated and
 // finalized by the conv epilogue (bn_ws given, LDS-DMA path, no epilogue op).
@@ -1418,40 +1485,6 @@ bool conv_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& y, int
                          finp, &done, xs),
         "conv2d_fwd");
   return done;
-}
-
-// The fused next-BN statistics state of a forward conv (nullptr without bn_ws).
-const ldnn::BnFin* bn_fwd_fin(ldnn::BnFin& fin, const ldnn::ConvShape& s, const c10::optional<at::Tensor>& bn_ws,
-                              const c10::optional<at::Tensor>& bn_gamma, const c10::optional<at::Tensor>& bn_beta,
-                              const c10::optional<at::Tensor>& bn_running_mean,
-                              const c10::optional<at::Tensor>& bn_running_var,
-                              const c10::optional<at::Tensor>& bn_save_mean,
-                              const c10::optional<at::Tensor>& bn_save_invstd, double bn_eps, double bn_momentum,
-                              const c10::optional<at::Tensor>& bn_num_batches) {
-  const ldnn::BnFin* finp = nullptr;
-  if (bn_ws.has_value()) {
-    const int C = s.K;
-    ldnn::BnArgs a{};
-    a.M = s.N * s.P * s.Q;
-    a.C = C;
-    a.gamma = fptr_opt(bn_gamma, C, "bn_gamma");
-    a.beta = fptr_opt(bn_beta, C, "bn_beta");
-    a.running_mean = fptr_opt(bn_running_mean, C, "bn_running_mean");
-    a.running_var = fptr_opt(bn_running_var, C, "bn_running_var");
-    a.save_mean = fptr_opt(bn_save_mean, C, "bn_save_mean");
-    a.save_invstd = fptr_opt(bn_save_invstd, C, "bn_save_invstd");
-    TORCH_CHECK(a.save_mean && a.save_invstd, "conv: fused BN statistics need save_mean / save_invstd");
-    a.ws = fptr_opt(bn_ws, ldnn::bn_workspace_floats(C), "bn_ws");
-    a.eps = (float)bn_eps;
-    a.momentum = (float)bn_momentum;
-    if (bn_num_batches.has_value()) {
-      check_dev(*bn_num_batches, at::kLong, "bn_num_batches");
-      a.num_batches = bn_num_batches->data_ptr<int64_t>();
-    }
-    fin = ldnn::bn_forward_fin_conv(a);
-    finp = &fin;
-  }
-  return finp;
 }
 
 c10::optional<at::Tensor> opt_item(const py::dict& d, const char* k) {
@@ -1511,23 +1544,13 @@ const ldnn::BnBwdFuse* bn_bwd_fuse(ldnn::BnBwdFuse& fuse, const ldnn::ConvShape&
     const int64_t M = (int64_t)s.N * s.H * s.W;
     check_dev(*bn_x, at::kBFloat16, "bn_x");
     TORCH_CHECK(bn_x->is_contiguous() && bn_x->numel() == M * C, "conv_dgrad: bn_x must be dense [M][C] like dx");
-    ldnn::BnArgs a{};
-    a.M = (int)M;
-    a.C = C;
-    a.gamma = fptr_opt(bn_gamma, C, "bn_gamma");
-    a.save_mean = fptr_opt(bn_save_mean, C, "bn_save_mean");
-    a.save_invstd = fptr_opt(bn_save_invstd, C, "bn_save_invstd");
+    const ldnn::BnArgs a = bn_bwd_args(M, C, bn_gamma, bn_save_mean, bn_save_invstd, bn_ws);
     TORCH_CHECK(a.save_mean && a.save_invstd, "conv_dgrad: the BN statistics need save_mean / save_invstd");
-    a.ws = fptr_opt(bn_ws, ldnn::bn_workspace_floats(C), "bn_ws");
     TORCH_CHECK(a.ws != nullptr, "conv_dgrad: bn_ws");
     fuse.fin = ldnn::bn_backward_fin_conv(a, fptr_opt(bn_dgamma, C, "bn_dgamma"), fptr_opt(bn_dbeta, C, "bn_dbeta"),
                                           bn_assign);
     fuse.x = bf16_ptr(*bn_x);
-    if (bn_mask.has_value()) {
-      check_dev(*bn_mask, at::kByte, "bn_mask");
-      TORCH_CHECK(bn_mask->is_contiguous() && bn_mask->numel() == M * C / 8, "conv_dgrad: bn_mask [M][C/8]");
-      fuse.mask = bn_mask->data_ptr<uint8_t>();
-    }
+    fuse.mask = relu_mask(bn_mask, M * C, "conv_dgrad");
     fp = &fuse;
   }
   return fp;
@@ -1658,13 +1681,6 @@ void conv_wgrad(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& dw,
         "conv2d_wgrad");
 }
 
-float* fptr_opt(const c10::optional<at::Tensor>& t, int64_t n, const char* name) {
-  if (!t.has_value()) return nullptr;
-  check_dev(*t, at::kFloat, name);
-  TORCH_CHECK(t->is_contiguous() && t->numel() >= n, name, ": bad tensor");
-  return t->data_ptr<float>();
-}
-
 // x, y, residual: dense [M][C] bf16 (NHWC flattened); stats: [C] fp32; ws: fp32 [4C + 2C]
 void bn_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& residual,
             const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
@@ -1677,37 +1693,17 @@ void bn_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Te
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && y.sizes() == x.sizes() && y.is_contiguous(), "bn: [M][C] dense");
   const int64_t M = x.size(0), C = x.size(1);
   TORCH_CHECK(C % 8 == 0, "bn: C must be a multiple of 8");
-  ldnn::BnArgs a{};
+  // (num_batches counts training-mode calls only)
+  ldnn::BnArgs a = bn_args(M, C, gamma, beta, running_mean, running_var, save_mean, save_invstd, ws, eps, momentum,
+                           training ? num_batches : OptTensor());
   a.x = bf16_ptr(x);
   a.y = bf16_mut(y);
-  if (residual.has_value()) {
-    check_dev(*residual, at::kBFloat16, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes() && residual->is_contiguous(), "bn: residual layout");
-    a.residual = bf16_ptr(*residual);
-  }
-  a.gamma = fptr_opt(gamma, C, "gamma");
-  a.beta = fptr_opt(beta, C, "beta");
-  a.running_mean = fptr_opt(running_mean, C, "running_mean");
-  a.running_var = fptr_opt(running_var, C, "running_var");
-  a.save_mean = fptr_opt(save_mean, C, "save_mean");
-  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
-  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
-  a.M = (int)M;
-  a.C = (int)C;
-  a.eps = (float)eps;
-  a.momentum = (float)momentum;
+  a.residual = like(residual, x, "bn", "residual");
   a.training = training ? 1 : 0;
   a.relu = relu ? 1 : 0;
   TORCH_CHECK(training || (a.running_mean && a.running_var), "bn: eval mode needs running statistics");
-  if (mask.has_value()) {  // ReLU bit mask [M][C/8] for the backward
-    check_dev(*mask, at::kByte, "mask");
-    TORCH_CHECK(relu && mask->is_contiguous() && mask->numel() == M * C / 8, "bn: mask needs relu and [M][C/8] bytes");
-    a.mask = mask->data_ptr<uint8_t>();
-  }
-  if (num_batches.has_value() && training) {
-    check_dev(*num_batches, at::kLong, "num_batches");
-    a.num_batches = num_batches->data_ptr<int64_t>();
-  }
+  TORCH_CHECK(relu || !mask.has_value(), "bn: mask needs relu");
+  a.mask = relu_mask(mask, M * C, "bn");   // [M][C/8], for the backward
   if (stats_ready) {  // the producing conv's epilogue already finalized scale / shift into ws
     TORCH_CHECK(training, "bn: stats_ready is a training-mode path");
     check(ldnn::bn_forward_apply(a, cur_stream(x)), "bn_forward_apply");
@@ -1730,32 +1726,14 @@ void bn_bwd(const at::Tensor& x, const at::Tensor& y, const at::Tensor& dy, cons
                   dx.sizes() == x.sizes() && dx.is_contiguous(),
               "bn_bwd: [M][C] dense tensors");
   const int64_t M = x.size(0), C = x.size(1);
-  ldnn::BnArgs a{};
+  ldnn::BnArgs a = bn_bwd_args(M, C, gamma, save_mean, save_invstd, ws);
   a.x = bf16_ptr(x);
   a.y = bf16_mut(y);
-  a.gamma = fptr_opt(gamma, C, "gamma");
-  a.save_mean = fptr_opt(save_mean, C, "save_mean");
-  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
-  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
-  a.M = (int)M;
-  a.C = (int)C;
   a.relu = relu ? 1 : 0;
-  if (mask.has_value()) {  // relu'(y) from the forward's bit mask instead of y
-    check_dev(*mask, at::kByte, "mask");
-    TORCH_CHECK(relu && mask->is_contiguous() && mask->numel() == M * C / 8, "bn_bwd: mask needs relu, [M][C/8]");
-    a.mask = mask->data_ptr<uint8_t>();
-  }
-  if (dy2.has_value()) {
-    check_dev(*dy2, at::kBFloat16, "dy2");
-    TORCH_CHECK(dy2->sizes() == x.sizes() && dy2->is_contiguous(), "bn_bwd: dy2 layout");
-    a.dy2 = bf16_ptr(*dy2);
-  }
-  uint16_t* dr = nullptr;
-  if (dres.has_value()) {
-    check_dev(*dres, at::kBFloat16, "dres");
-    TORCH_CHECK(dres->sizes() == x.sizes() && dres->is_contiguous(), "bn_bwd: dres layout");
-    dr = bf16_mut(*dres);
-  }
+  TORCH_CHECK(relu || !mask.has_value(), "bn_bwd: mask needs relu");
+  a.mask = relu_mask(mask, M * C, "bn_bwd");   // relu'(y) from the forward's bit mask instead of y
+  a.dy2 = like(dy2, x, "bn_bwd", "dy2");
+  uint16_t* dr = const_cast<uint16_t*>(like(dres, x, "bn_bwd", "dres"));
   check(ldnn::bn_backward(a, bf16_ptr(dy), bf16_mut(dx), dr, fptr_opt(dgamma, C, "dgamma"),
                           fptr_opt(dbeta, C, "dbeta"), cur_stream(x), grad_assign, stats_ready),
         "bn_backward");
@@ -1768,17 +1746,6 @@ const uint16_t* gn_act(const at::Tensor& t, const at::Tensor& x, const char* nam
   TORCH_CHECK(t.device() == x.device(), "group_norm: ", name, " is on another device than x");
   TORCH_CHECK(aligned16(t.data_ptr()), "group_norm: ", name, " must be 16-byte aligned");
   return bf16_ptr(t);
-}
-
-// (only the workspace is read with 16-byte loads; the per-channel and per-group vectors are read by element)
-float* gn_vec(const c10::optional<at::Tensor>& t, int64_t n, const at::Tensor& x, const char* name,
-              bool vector_loads = false) {
-  float* p = fptr_opt(t, n, name);
-  if (p != nullptr) {
-    TORCH_CHECK(t->device() == x.device(), "group_norm: ", name, " is on another device than x");
-    TORCH_CHECK(!vector_loads || aligned16(p), "group_norm: ", name, " must be 16-byte aligned");
-  }
-  return p;
 }
 
 ldnn::GnArgs gn_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma, const at::Tensor& mean,
@@ -1795,16 +1762,13 @@ ldnn::GnArgs gn_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma
   a.x = bf16_ptr(x);
   a.N = N, a.P = P, a.C = (int)C, a.G = (int)G;
   a.relu = relu ? 1 : 0;
-  a.gamma = gn_vec(gamma, C, x, "gamma");
-  a.mean = gn_vec(mean, N * G, x, "mean");
-  a.rstd = gn_vec(rstd, N * G, x, "rstd");
-  a.ws = gn_vec(ws, ldnn::gn_workspace_floats(N, P, (int)C, (int)G), x, "ws", true);
-  if (mask.has_value()) {
-    check_dev(*mask, at::kByte, "mask");
-    TORCH_CHECK(relu && mask->is_contiguous() && mask->numel() == x.numel() / 8 && mask->device() == x.device(),
-                "group_norm: mask needs relu and N*H*W*C/8 bytes on x's device");
-    a.mask = mask->data_ptr<uint8_t>();
-  }
+  // (only the workspace is read with 16-byte loads; the per-channel and per-group vectors are read by element)
+  a.gamma = fptr_opt(gamma, C, "gamma", &x);
+  a.mean = fptr_opt(mean, N * G, "mean", &x);
+  a.rstd = fptr_opt(rstd, N * G, "rstd", &x);
+  a.ws = fptr_opt(ws, ldnn::gn_workspace_floats(N, P, (int)C, (int)G), "ws", &x, true);
+  TORCH_CHECK(!mask.has_value() || (relu && mask->device() == x.device()), "group_norm: mask needs relu, x's device");
+  a.mask = relu_mask(mask, x.numel(), "group_norm");
   return a;
 }
 
@@ -1817,7 +1781,7 @@ void gn_fwd(const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Te
   a.y = const_cast<uint16_t*>(gn_act(y, x, "y"));
   TORCH_CHECK(y.data_ptr() != x.data_ptr(), "gn_fwd: in-place is not supported");
   if (residual.has_value()) a.residual = gn_act(*residual, x, "residual");
-  a.beta = gn_vec(beta, x.size(3), x, "beta");
+  a.beta = fptr_opt(beta, x.size(3), "beta", &x);
   a.eps = (float)eps;
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   check(ldnn::gn_forward(a, cur_stream(x)), "gn_forward");
@@ -1835,8 +1799,8 @@ void gn_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, con
   uint16_t* dr = dres.has_value() ? const_cast<uint16_t*>(gn_act(*dres, x, "dres")) : nullptr;
   TORCH_CHECK(d != a.x && d != g && dr != d, "gn_bwd: in-place is not supported");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  check(ldnn::gn_backward(a, g, d, dr, gn_vec(dgamma, x.size(3), x, "dgamma"), gn_vec(dbeta, x.size(3), x, "dbeta"),
-                          grad_assign, cur_stream(x)),
+  check(ldnn::gn_backward(a, g, d, dr, fptr_opt(dgamma, x.size(3), "dgamma", &x),
+                          fptr_opt(dbeta, x.size(3), "dbeta", &x), grad_assign, cur_stream(x)),
         "gn_backward");
 }
 
@@ -1865,15 +1829,6 @@ int64_t ln_ld(const at::Tensor& t, const at::Tensor& x, const char* name, bool o
   return ld;
 }
 
-float* ln_vec(const c10::optional<at::Tensor>& t, int64_t n, const at::Tensor& x, const char* name) {
-  float* p = fptr_opt(t, n, name);
-  if (p != nullptr) {
-    TORCH_CHECK(t->device() == x.device(), "layer_norm: ", name, " is on another device than x");
-    TORCH_CHECK(aligned16(p), "layer_norm: ", name, " must be 16-byte aligned");
-  }
-  return p;
-}
-
 ldnn::LnArgs ln_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
                      const c10::optional<at::Tensor>& beta, const at::Tensor& mean, const at::Tensor& rstd,
                      int64_t act) {
@@ -1886,10 +1841,10 @@ ldnn::LnArgs ln_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma
   TORCH_CHECK(act >= ldnn::LN_ACT_NONE && act <= ldnn::LN_ACT_SIGMOID, "layer_norm: act must be -1 (none), 0 (relu) ",
               "or 1 (sigmoid), got ", act);
   TORCH_CHECK(gamma.has_value() == beta.has_value(), "layer_norm: gamma and beta come together");
-  a.gamma = ln_vec(gamma, ln_up8(a.N), x, "gamma");
-  a.beta = ln_vec(beta, ln_up8(a.N), x, "beta");
-  a.mean = ln_vec(mean, a.B, x, "mean");
-  a.rstd = ln_vec(rstd, a.B, x, "rstd");
+  a.gamma = fptr_opt(gamma, ln_up8(a.N), "gamma", &x, true);
+  a.beta = fptr_opt(beta, ln_up8(a.N), "beta", &x, true);
+  a.mean = fptr_opt(mean, a.B, "mean", &x, true);
+  a.rstd = fptr_opt(rstd, a.B, "rstd", &x, true);
   a.act = (int)act;
   return a;
 }
@@ -1917,11 +1872,12 @@ void ln_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, con
   float* w = nullptr;
   if (gamma.has_value()) {
     TORCH_CHECK(ws.has_value(), "ln_bwd: an affine layer needs the workspace");
-    w = ln_vec(ws, ldnn::ln_workspace_floats(a.B, a.N), x, "ws");
+    w = fptr_opt(ws, ldnn::ln_workspace_floats(a.B, a.N), "ws", &x, true);
   }
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  check(ldnn::ln_backward(a, bf16_ptr(dy), ld_dy, bf16_mut(dx), ld_dx, w, ln_vec(dgamma, ln_up8(a.N), x, "dgamma"),
-                          ln_vec(dbeta, ln_up8(a.N), x, "dbeta"), grad_assign, cur_stream(x)),
+  check(ldnn::ln_backward(a, bf16_ptr(dy), ld_dy, bf16_mut(dx), ld_dx, w,
+                          fptr_opt(dgamma, ln_up8(a.N), "dgamma", &x, true),
+                          fptr_opt(dbeta, ln_up8(a.N), "dbeta", &x, true), grad_assign, cur_stream(x)),
         "ln_backward");
 }
 
@@ -1967,12 +1923,7 @@ void pool_bwd(const at::Tensor& dy, const c10::optional<at::Tensor>& argmax, con
     am = argmax->data_ptr<uint8_t>();
     TORCH_CHECK(argmax->is_contiguous() && ((uintptr_t)am & 7) == 0, "pool: argmax must be dense and 8-B aligned");
   }
-  const uint16_t* d2 = nullptr;
-  if (dy2.has_value()) {
-    check_dev(*dy2, at::kBFloat16, "dy2");
-    TORCH_CHECK(dy2->sizes() == dy.sizes() && dy2->is_contiguous(), "pool_bwd: dy2 layout");
-    d2 = bf16_ptr(*dy2);
-  }
+  const uint16_t* d2 = like(dy2, dy, "pool_bwd", "dy2");
   check(ldnn::pool2d_bwd(bf16_ptr(dy), am, bf16_mut(dx), (int)dx.size(0), (int)dx.size(1), (int)dx.size(2),
                          (int)dx.size(3), (int)P, (int)Q, (int)R, (int)S, (int)stride, (int)pad,
                          is_max, cur_stream(dy), d2, (int)cl),
@@ -1981,33 +1932,6 @@ void pool_bwd(const at::Tensor& dy, const c10::optional<at::Tensor>& argmax, con
 
 // y = relu(bn_a(x) + bn_b(r)): residual block tail whose shortcut carries its own BatchNorm
 // (the shortcut BN's output is never stored).  x, r, y: [M][C] dense bf16.
-ldnn::BnArgs dual_args(const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
-                       const c10::optional<at::Tensor>& beta, const c10::optional<at::Tensor>& running_mean,
-                       const c10::optional<at::Tensor>& running_var, const at::Tensor& save_mean,
-                       const at::Tensor& save_invstd, const at::Tensor& ws, double eps, double momentum,
-                       const c10::optional<at::Tensor>& num_batches) {
-  const int64_t M = x.size(0), C = x.size(1);
-  ldnn::BnArgs a{};
-  a.x = bf16_ptr(x);
-  a.gamma = fptr_opt(gamma, C, "gamma");
-  a.beta = fptr_opt(beta, C, "beta");
-  a.running_mean = fptr_opt(running_mean, C, "running_mean");
-  a.running_var = fptr_opt(running_var, C, "running_var");
-  a.save_mean = fptr_opt(save_mean, C, "save_mean");
-  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
-  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
-  a.M = (int)M;
-  a.C = (int)C;
-  a.eps = (float)eps;
-  a.momentum = (float)momentum;
-  a.training = 1;
-  if (num_batches.has_value()) {
-    check_dev(*num_batches, at::kLong, "num_batches");
-    a.num_batches = num_batches->data_ptr<int64_t>();
-  }
-  return a;
-}
-
 void bn_dual_fwd(const at::Tensor& x, const at::Tensor& r, const at::Tensor& y, const c10::optional<at::Tensor>& mask,
                  const c10::optional<at::Tensor>& gamma_a, const c10::optional<at::Tensor>& beta_a,
                  const c10::optional<at::Tensor>& rm_a, const c10::optional<at::Tensor>& rv_a,
@@ -2022,15 +1946,14 @@ void bn_dual_fwd(const at::Tensor& x, const at::Tensor& r, const at::Tensor& y, 
     TORCH_CHECK(t->dim() == 2 && t->is_contiguous() && t->sizes() == x.sizes(), "bn_dual_fwd: [M][C] dense");
   }
   TORCH_CHECK(x.size(1) % 8 == 0, "bn_dual_fwd: C % 8");
-  ldnn::BnArgs a = dual_args(x, gamma_a, beta_a, rm_a, rv_a, mean_a, invstd_a, ws_a, eps_a, mom_a, nb_a);
-  ldnn::BnArgs b = dual_args(r, gamma_b, beta_b, rm_b, rv_b, mean_b, invstd_b, ws_b, eps_b, mom_b, nb_b);
+  const int64_t M = x.size(0), C = x.size(1);
+  ldnn::BnArgs a = bn_args(M, C, gamma_a, beta_a, rm_a, rv_a, mean_a, invstd_a, ws_a, eps_a, mom_a, nb_a);
+  ldnn::BnArgs b = bn_args(M, C, gamma_b, beta_b, rm_b, rv_b, mean_b, invstd_b, ws_b, eps_b, mom_b, nb_b);
+  a.x = bf16_ptr(x), b.x = bf16_ptr(r);
+  a.training = b.training = 1;
   a.y = bf16_mut(y);
   a.relu = 1;
-  if (mask.has_value()) {
-    check_dev(*mask, at::kByte, "mask");
-    TORCH_CHECK(mask->is_contiguous() && mask->numel() == x.numel() / 8, "bn_dual_fwd: mask [M][C/8]");
-    a.mask = mask->data_ptr<uint8_t>();
-  }
+  a.mask = relu_mask(mask, M * C, "bn_dual_fwd");
   check(ldnn::bn_dual_forward(a, b, ready_a, ready_b, cur_stream(x)), "bn_dual_forward");
 }
 
@@ -2046,26 +1969,15 @@ void bn_dual_bwd(const at::Tensor& x, const at::Tensor& r, const at::Tensor& y, 
     check_dev(*t, at::kBFloat16, "bn_dual_bwd tensor");
     TORCH_CHECK(t->dim() == 2 && t->is_contiguous() && t->sizes() == x.sizes(), "bn_dual_bwd: [M][C] dense");
   }
-  const int64_t C = x.size(1);
-  ldnn::BnArgs a = dual_args(x, gamma_a, c10::nullopt, c10::nullopt, c10::nullopt, mean_a, invstd_a, ws_a, 0.0, 0.0,
-                             c10::nullopt);
-  ldnn::BnArgs b = dual_args(r, gamma_b, c10::nullopt, c10::nullopt, c10::nullopt, mean_b, invstd_b, ws_b, 0.0, 0.0,
-                             c10::nullopt);
+  const int64_t M = x.size(0), C = x.size(1);
+  ldnn::BnArgs a = bn_bwd_args(M, C, gamma_a, mean_a, invstd_a, ws_a);
+  ldnn::BnArgs b = bn_bwd_args(M, C, gamma_b, mean_b, invstd_b, ws_b);
+  a.x = bf16_ptr(x), b.x = bf16_ptr(r);
+  a.training = b.training = 1;
   a.relu = 1;
-  if (mask.has_value()) {
-    check_dev(*mask, at::kByte, "mask");
-    TORCH_CHECK(mask->is_contiguous() && mask->numel() == x.numel() / 8, "bn_dual_bwd: mask [M][C/8]");
-    a.mask = mask->data_ptr<uint8_t>();
-  } else {
-    check_dev(y, at::kBFloat16, "y");
-    TORCH_CHECK(y.sizes() == x.sizes() && y.is_contiguous(), "bn_dual_bwd: y layout");
-    a.y = bf16_mut(y);
-  }
-  if (dy2.has_value()) {
-    check_dev(*dy2, at::kBFloat16, "dy2");
-    TORCH_CHECK(dy2->sizes() == x.sizes() && dy2->is_contiguous(), "bn_dual_bwd: dy2 layout");
-    a.dy2 = bf16_ptr(*dy2);
-  }
+  a.mask = relu_mask(mask, M * C, "bn_dual_bwd");
+  if (!mask.has_value()) a.y = const_cast<uint16_t*>(like(y, x, "bn_dual_bwd", "y"));   // (not read beside the mask)
+  a.dy2 = like(dy2, x, "bn_dual_bwd", "dy2");
   check(ldnn::bn_dual_backward(a, b, bf16_ptr(dy), bf16_mut(dx), bf16_mut(dr), fptr_opt(dgamma_a, C, "dgamma_a"),
                                fptr_opt(dbeta_a, C, "dbeta_a"), fptr_opt(dgamma_b, C, "dgamma_b"),
                                fptr_opt(dbeta_b, C, "dbeta_b"), assign_a, assign_b, cur_stream(x)),
@@ -2082,35 +1994,16 @@ bool bn_pool_fwd(const at::Tensor& x, const at::Tensor& y, const at::Tensor& arg
   check_dev(x, at::kBFloat16, "x");
   check_dev(y, at::kBFloat16, "y");
   check_dev(argmax, at::kByte, "argmax");
-  uint16_t* xam_p = nullptr;
-  if (xam.has_value()) {
-    check_dev(*xam, at::kBFloat16, "xam");
-    TORCH_CHECK(xam->sizes() == y.sizes() && xam->is_contiguous(), "bn_pool_fwd: xam must be laid out as y");
-    xam_p = bf16_mut(*xam);
-  }
+  uint16_t* xam_p = const_cast<uint16_t*>(like(xam, y, "bn_pool_fwd", "xam"));
   TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.is_contiguous() && y.is_contiguous() && argmax.is_contiguous() &&
                   argmax.sizes() == y.sizes() && y.size(0) == x.size(0) && y.size(3) == x.size(3),
               "bn_pool_fwd: dense NHWC x / y / argmax");
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  ldnn::BnArgs a{};
+  ldnn::BnArgs a = bn_args(N * H * W, C, gamma, beta, running_mean, running_var, save_mean, save_invstd, ws, eps,
+                           momentum, num_batches);
   a.x = bf16_ptr(x);
-  a.gamma = fptr_opt(gamma, C, "gamma");
-  a.beta = fptr_opt(beta, C, "beta");
-  a.running_mean = fptr_opt(running_mean, C, "running_mean");
-  a.running_var = fptr_opt(running_var, C, "running_var");
-  a.save_mean = fptr_opt(save_mean, C, "save_mean");
-  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
-  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
-  a.M = (int)(N * H * W);
-  a.C = (int)C;
-  a.eps = (float)eps;
-  a.momentum = (float)momentum;
   a.training = 1;
   a.relu = 1;
-  if (num_batches.has_value()) {
-    check_dev(*num_batches, at::kLong, "num_batches");
-    a.num_batches = num_batches->data_ptr<int64_t>();
-  }
   uint8_t* am = argmax.data_ptr<uint8_t>();
   TORCH_CHECK(((uintptr_t)am & 7) == 0, "bn_pool_fwd: argmax must be 8-B aligned");
   check(ldnn::bn_maxpool_forward(a, (int)N, (int)H, (int)W, (int)y.size(1), (int)y.size(2), (int)pad, bf16_mut(y),
@@ -2133,28 +2026,13 @@ void bn_pool_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& ar
                   dy.size(0) == x.size(0) && dy.size(3) == x.size(3),
               "bn_pool_bwd: dense NHWC tensors");
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  ldnn::BnArgs a{};
+  ldnn::BnArgs a = bn_bwd_args(N * H * W, C, gamma, save_mean, save_invstd, ws);
   a.x = bf16_ptr(x);
-  a.gamma = fptr_opt(gamma, C, "gamma");
-  a.save_mean = fptr_opt(save_mean, C, "save_mean");
-  a.save_invstd = fptr_opt(save_invstd, C, "save_invstd");
-  a.ws = fptr_opt(ws, ldnn::bn_workspace_floats((int)C), "ws");
-  a.M = (int)(N * H * W);
-  a.C = (int)C;
   a.relu = 1;
-  if (dy2.has_value()) {
-    check_dev(*dy2, at::kBFloat16, "dy2");
-    TORCH_CHECK(dy2->sizes() == dy.sizes() && dy2->is_contiguous(), "bn_pool_bwd: dy2 layout");
-    a.dy2 = bf16_ptr(*dy2);
-  }
+  a.dy2 = like(dy2, dy, "bn_pool_bwd", "dy2");
   const uint8_t* am = argmax.data_ptr<uint8_t>();
   TORCH_CHECK(((uintptr_t)am & 7) == 0, "bn_pool_bwd: argmax must be 8-B aligned");
-  const uint16_t* xam_p = nullptr;
-  if (xam.has_value()) {
-    check_dev(*xam, at::kBFloat16, "xam");
-    TORCH_CHECK(xam->sizes() == dy.sizes() && xam->is_contiguous(), "bn_pool_bwd: xam must be laid out as dy");
-    xam_p = bf16_ptr(*xam);
-  }
+  const uint16_t* xam_p = like(xam, dy, "bn_pool_bwd", "xam");
   check(ldnn::bn_maxpool_backward(a, (int)N, (int)H, (int)W, (int)dy.size(1), (int)dy.size(2), (int)pad,
                                   bf16_ptr(dy), am, bf16_mut(dx), fptr_opt(dgamma, C, "dgamma"),
                                   fptr_opt(dbeta, C, "dbeta"), cur_stream(x), grad_assign, xam_p),

@@ -46,6 +46,17 @@ def _fire_pre_hooks(mods, x) -> bool:
 
 
 def _to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """The cast alone: strides and memory format stay (a channels_last tensor stays NHWC)."""
+    return x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+
+
+def _from_bf16(t: torch.Tensor, dtype) -> torch.Tensor:
+    """A native op's bf16 result (a gradient) in the dtype its consumer handed in."""
+    return t if dtype == torch.bfloat16 else t.to(dtype)
+
+
+def _bf16_rows(x: torch.Tensor) -> torch.Tensor:
+    """bf16 with a unit last stride, copying only if needed (GEMM and row-kernel operands)."""
     if x.dtype == torch.bfloat16:
         return x if x.stride(-1) == 1 else x.contiguous()
     return x.to(torch.bfloat16).contiguous()
@@ -72,7 +83,7 @@ class _LinearActNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, flat):
         C = _ext.C()
-        x = _to_bf16(x)
+        x = _bf16_rows(x)
         w = flat.shadow_storage(weight)
         npad, kpad = w.shape
         K = weight.shape[1]
@@ -115,7 +126,7 @@ class _LinearActNative(torch.autograd.Function):
         x2, y = ctx.saved_tensors
         flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
         npad = y.shape[1]
-        g = _padded_rows_view(_to_bf16(gy.reshape(-1, gy.shape[-1])), npad)
+        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
         if ctx.act is not None:
             gz = torch.empty_like(y)
             if bias is not None:   # activation backward + the bias gradient's column sums in one pass
@@ -170,7 +181,7 @@ class _ActNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, act):
         C = _ext.C()
-        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+        xb = _to_bf16(x)
         if _flat_dense(xb) is None:
             xb = xb.contiguous()
         y = torch.empty_like(xb)  # keeps the memory format (channels_last stays NHWC)
@@ -183,7 +194,7 @@ class _ActNative(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        g = gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16)
+        g = _to_bf16(gy)
         if g.stride() != y.stride():
             g = g.contiguous(memory_format=torch.channels_last) if y.dim() == 4 and not y.is_contiguous() \
                 else g.contiguous()
@@ -209,7 +220,7 @@ class _SoftmaxXentNative(torch.autograd.Function):
     def forward(ctx, logits, labels, stats, label_smoothing=0.0):
         C = _ext.C()
         B, n = logits.shape
-        lg = logits if (logits.dtype == torch.bfloat16 and logits.stride(1) == 1) else logits.to(torch.bfloat16).contiguous()
+        lg = _bf16_rows(logits)
         ld = lg.stride(0)
         dfull = torch.empty(B * ld, dtype=torch.bfloat16, device=lg.device).view(B, ld)
         # one launch: the kernel's last block writes [mean loss, #correct] into `out`
@@ -471,7 +482,7 @@ class _Conv2dNative(torch.autograd.Function):
         xb, y, xs = ctx.saved_tensors
         stride, pad, flat, weight, bias, relu, Cin, in_dtype = ctx.meta
         kp = y.shape[3]
-        g = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), kp)
+        g = as_nhwc(_to_bf16(gy), kp)
         if relu:
             gz = torch.empty_like(y)
             if bias is not None:   # ReLU backward + the bias gradient's column sums in one pass
@@ -495,9 +506,7 @@ class _Conv2dNative(torch.autograd.Function):
                 # the BN's backward finds its statistics finalized if this dx reaches it unchanged
                 src.pre = (dxb.data_ptr(), dxb._version)
             ctx.bnsrc = None
-            dx = _zpad(nchw_view(dxb, Cin))   # (weight pad channels are zero)
-            if in_dtype != torch.bfloat16:
-                dx = dx.to(in_dtype)
+            dx = _from_bf16(_zpad(nchw_view(dxb, Cin)), in_dtype)   # (weight pad channels are zero)
         else:
             C.conv_wgrad(g, xb, dw, stride, pad, beta, real_channels=Cin, s2d_xs=xs)
         flat.notify(weight, bias)
@@ -546,14 +555,12 @@ class _Conv2dPairNative(torch.autograd.Function):
             job = []
             for g, (weight, st, pd) in ((g0, c0), (g1, c1)):
                 sh = flat.shadow_storage(weight)
-                gb = as_nhwc(g if g.dtype == torch.bfloat16 else g.to(torch.bfloat16), sh.shape[0])
+                gb = as_nhwc(_to_bf16(g), sh.shape[0])
                 job.append((gb, sh, torch.empty_like(xb), flat.grad_storage(weight), st, pd, flat.grad_beta(weight)))
             (ga, sa, xa, wa, sta, pa, ba), (gc, sc, xc, wc, stc, pc, bc) = job
             C.conv_bwd2(xb, ga, sa, xa, wa, sta, pa, ba, gc, sc, xc, wc, stc, pc, bc, Cin)
             flat.notify(c0[0], c1[0])
-            dxs = [_zpad(nchw_view(xa, Cin)), _zpad(nchw_view(xc, Cin))]
-            if in_dtype != torch.bfloat16:
-                dxs = [d.to(in_dtype) for d in dxs]
+            dxs = [_from_bf16(_zpad(nchw_view(t, Cin)), in_dtype) for t in (xa, xc)]
             return dxs[0], dxs[1], None, None, None, None, None
         dxs = []
         for k, (g, (weight, st, pd)) in enumerate(((g0, c0), (g1, c1))):
@@ -561,13 +568,13 @@ class _Conv2dPairNative(torch.autograd.Function):
                 dxs.append(None)
                 continue
             sh = flat.shadow_storage(weight)
-            gb = as_nhwc(g if g.dtype == torch.bfloat16 else g.to(torch.bfloat16), sh.shape[0])
+            gb = as_nhwc(_to_bf16(g), sh.shape[0])
             dw, beta = flat.grad_storage(weight), flat.grad_beta(weight)
             if ctx.needs_input_grad[k]:
                 dxb = torch.empty_like(xb)
                 C.conv_bwd(gb, sh, dxb, xb, dw, st, pd, beta, Cin)
                 dx = _zpad(nchw_view(dxb, Cin))
-                dxs.append(dx if in_dtype == torch.bfloat16 else dx.to(in_dtype))
+                dxs.append(_from_bf16(dx, in_dtype))
             else:
                 C.conv_wgrad(gb, xb, dw, st, pd, beta, real_channels=Cin)
                 dxs.append(None)
@@ -619,15 +626,19 @@ def conv2d(x, mod, relu: bool = False, bn=None):
     return F.relu(y) if relu else y
 
 
-def _bn_workspace(mod, C: int, dev, C_) -> torch.Tensor:
-    """The module's persistent BN workspace (zeroed once: the kernels keep their
-    accumulators clear), so a BN costs no zero-fill launch per call."""
-    ws = getattr(mod, "_ldnn_bn_ws", None)
-    n = C_.bn_workspace_floats(C)
+def _module_ws(mod, attr: str, n: int, dev, zero: bool = False) -> torch.Tensor:
+    """A norm module's persistent fp32 scratch, kept as ``mod.<attr>``.  It grows with the largest
+    call seen, so a captured step -- warmed up at its own shape first -- allocates nothing new.
+    ``zero``: zeroed once (the BN kernels keep their accumulators clear: no zero-fill launch per
+    call); the GroupNorm / LayerNorm scratch keeps nothing between launches and needs no zeroing."""
+    ws = mod.__dict__.get(attr)
     if ws is None or ws.device != dev or ws.numel() < n:
-        ws = torch.zeros(n, dtype=torch.float32, device=dev)
-        mod._ldnn_bn_ws = ws
+        ws = mod.__dict__[attr] = (torch.zeros if zero else torch.empty)(max(n, 1), dtype=torch.float32, device=dev)
     return ws
+
+
+def _bn_workspace(mod, C: int, dev, C_) -> torch.Tensor:
+    return _module_ws(mod, "_ldnn_bn_ws", C_.bn_workspace_floats(C), dev, zero=True)
 
 
 def _with_twin(y: torch.Tensor, twin: torch.Tensor) -> torch.Tensor:
@@ -649,22 +660,32 @@ def shortcut_input(x: torch.Tensor) -> torch.Tensor:
     return x if t is None else t
 
 
+def _bn_stats_source(mod, x2, C: int):
+    """Where a BN forward over ``x2`` takes its batch statistics from: (running_mean, running_var,
+    save_mean, save_invstd, momentum, num_batches, stats_ready).  stats_ready: the producing conv's
+    epilogue already accumulated + finalized them for this very buffer (_conv_bn_stats_done; a
+    training-mode path); otherwise this BN's own pass, with its bookkeeping (_bn_train_state)."""
+    pre = mod.__dict__.pop("_ldnn_pre", None)
+    if pre is not None and mod.training and pre[0] == x2.data_ptr():
+        return None, None, pre[1], pre[2], 0.0, None, True
+    rm, rv, mom, nbt = _bn_train_state(mod, x2.device)
+    smean = torch.empty(C, dtype=torch.float32, device=x2.device)
+    return rm, rv, smean, torch.empty_like(smean), mom or 0.0, nbt, False
+
+
 class _BatchNormNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, mod, flat, relu):
         C_ = _ext.C()
         N, C, H, W = x.shape
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), C, zero_pad=False)
+        xb = as_nhwc(_to_bf16(x), C, zero_pad=False)
         x2 = xb.view(-1, C)
         r2 = None
         if residual is not None:
-            rb = residual if residual.dtype == torch.bfloat16 else residual.to(torch.bfloat16)
-            r2 = as_nhwc(rb, C, zero_pad=False).reshape(-1, C)
+            r2 = as_nhwc(_to_bf16(residual), C, zero_pad=False).reshape(-1, C)
         y = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=x.device)
         dev = x.device
         ws = _bn_workspace(mod, C, dev, C_)
-        smean = torch.empty(C, dtype=torch.float32, device=dev)
-        sinv = torch.empty(C, dtype=torch.float32, device=dev)
         gamma = flat.master_storage(weight)[:C] if weight is not None else None
         beta = flat.master_storage(bias)[:C] if bias is not None else None
         training = mod.training or not mod.track_running_stats
@@ -672,17 +693,9 @@ class _BatchNormNative(torch.autograd.Function):
         # y's bytes); only when a backward will run
         mask = (torch.empty(x2.shape[0] * C // 8, dtype=torch.uint8, device=dev)
                 if relu and any(ctx.needs_input_grad) and BN_RELU_MASK else None)
-        pre = mod.__dict__.pop("_ldnn_pre", None)
-        if pre is not None and mod.training and pre[0] == x2.data_ptr():
-            # statistics already accumulated + finalized by the producing conv's epilogue
-            smean, sinv = pre[1], pre[2]
-            C_.bn_fwd(x2, y.view(-1, C), r2, gamma, beta, None, None, smean, sinv, ws, mod.eps, 0.0, True, relu,
-                      None, stats_ready=True, mask=mask)
-        else:
-            rm, rv, mom, nbt = _bn_train_state(mod, dev)
-            C_.bn_fwd(x2, y.view(-1, C), r2, gamma, beta, rm if (training and mod.training) or not training else None,
-                      rv if (training and mod.training) or not training else None, smean, sinv, ws, mod.eps,
-                      mom or 0.0, training, relu, nbt, mask=mask)
+        rm, rv, smean, sinv, mom, nbt, ready = _bn_stats_source(mod, x2, C)
+        C_.bn_fwd(x2, y.view(-1, C), r2, gamma, beta, rm, rv, smean, sinv, ws, mod.eps, mom, training, relu, nbt,
+                  stats_ready=ready, mask=mask)
         ctx.mask = mask
         ctx.save_for_backward(x2, y if mask is None else x2.new_empty(0), smean, sinv)
         ctx.meta = (flat, weight, bias, relu, residual is not None, ws, (N, C, H, W), x.dtype)
@@ -703,24 +716,15 @@ class _BatchNormNative(torch.autograd.Function):
             gy, gy_twin = gy_twin, None
         if gy is None:
             return None, None, None, None, None, None, None
-        g2 = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), C, zero_pad=False)
-        g2 = g2.contiguous().view(-1, C)
+        g2 = as_nhwc(_to_bf16(gy), C, zero_pad=False).contiguous().view(-1, C)
         gt = None
         if gy_twin is not None:   # the shortcut branch's gradient of the same output: summed in the kernels
-            gt = as_nhwc(gy_twin if gy_twin.dtype == torch.bfloat16 else gy_twin.to(torch.bfloat16), C,
-                         zero_pad=False).contiguous().view(-1, C)
+            gt = as_nhwc(_to_bf16(gy_twin), C, zero_pad=False).contiguous().view(-1, C)
         dx = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=x2.device)
         dres = torch.empty_like(dx) if has_res and ctx.needs_input_grad[3] else None
         gamma = flat.master_storage(weight)[:C] if weight is not None else None
-        dg = flat.grad_storage(weight)[:C] if weight is not None else None
-        db = flat.grad_storage(bias)[:C] if bias is not None else None
         # first write of the step: the finalize stores dgamma / dbeta instead of adding
-        fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias)) if p is not None]
-        assign = all(f for _, f in fresh)
-        if not assign:  # mixed (only if a caller accumulated one of them): clear the fresh ones
-            for t, f in fresh:
-                if f:
-                    t.zero_()
+        dg, db, assign = flat.affine_grads(weight, bias)
         mask = ctx.mask
         yv = y.view(-1, C) if mask is None else x2   # (y is not read when the mask is given)
         pre = ctx.bnsrc.pre if ctx.bnsrc is not None else None
@@ -733,11 +737,8 @@ class _BatchNormNative(torch.autograd.Function):
         C_.bn_bwd(x2, yv, g2, dx.view(-1, C), dres.view(-1, C) if dres is not None else None, gamma,
                   smean, sinv, ws, dg, db, relu, mask=mask, grad_assign=assign, dy2=gt, stats_ready=ready)
         flat.notify(weight, bias)
-        dxv = nchw_view(dx, C)
         dresv = nchw_view(dres, C) if dres is not None else None
-        if in_dtype != torch.bfloat16:
-            dxv = dxv.to(in_dtype)
-        return dxv, None, None, dresv, None, None, None
+        return _from_bf16(nchw_view(dx, C), in_dtype), None, None, dresv, None, None, None
 
 
 class _BatchNormDualNative(torch.autograd.Function):
@@ -751,35 +752,22 @@ class _BatchNormDualNative(torch.autograd.Function):
         C_ = _ext.C()
         N, C, H, W = x.shape
         dev = x.device
-        x2 = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), C, zero_pad=False).reshape(-1, C)
-        r2 = as_nhwc(r if r.dtype == torch.bfloat16 else r.to(torch.bfloat16), C, zero_pad=False).reshape(-1, C)
+        x2 = as_nhwc(_to_bf16(x), C, zero_pad=False).reshape(-1, C)
+        r2 = as_nhwc(_to_bf16(r), C, zero_pad=False).reshape(-1, C)
         y = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=dev)
         mask = (torch.empty(x2.shape[0] * C // 8, dtype=torch.uint8, device=dev)
                 if any(ctx.needs_input_grad) and BN_RELU_MASK else None)
 
-        def state(mod, t2, w, b):
-            st = dict(ws=_bn_workspace(mod, C, dev, C_), gamma=flat.master_storage(w)[:C],
-                      beta=flat.master_storage(b)[:C])
-            pre = mod.__dict__.pop("_ldnn_pre", None)
-            if pre is not None and pre[0] == t2.data_ptr():
-                # statistics already accumulated + finalized by the producing conv's epilogue
-                st.update(rm=None, rv=None, mom=0.0, nb=None, mean=pre[1], invstd=pre[2], ready=True)
-            else:
-                rm, rv, mom, nbt = _bn_train_state(mod, dev)
-                st.update(rm=rm, rv=rv, mom=mom or 0.0, nb=nbt, mean=torch.empty(C, dtype=torch.float32, device=dev),
-                          invstd=torch.empty(C, dtype=torch.float32, device=dev), ready=False)
-            return st
+        def state(mod, t2, w, b):   # one BN's run of bn_dual_fwd's arguments
+            rm, rv, mean, invstd, mom, nbt, ready = _bn_stats_source(mod, t2, C)
+            return (flat.master_storage(w)[:C], flat.master_storage(b)[:C], rm, rv, mean, invstd,
+                    _bn_workspace(mod, C, dev, C_), mod.eps, mom, nbt, ready)
 
         sa, sb = state(mod_a, x2, wa, ba), state(mod_b, r2, wb, bb)
-        C_.bn_dual_fwd(x2, r2, y.view(-1, C), mask,
-                       sa["gamma"], sa["beta"], sa["rm"], sa["rv"], sa["mean"], sa["invstd"], sa["ws"], mod_a.eps,
-                       sa["mom"], sa["nb"], sa["ready"],
-                       sb["gamma"], sb["beta"], sb["rm"], sb["rv"], sb["mean"], sb["invstd"], sb["ws"], mod_b.eps,
-                       sb["mom"], sb["nb"], sb["ready"])
+        C_.bn_dual_fwd(x2, r2, y.view(-1, C), mask, *sa, *sb)
         ctx.mask = mask
-        ctx.save_for_backward(x2, r2, y.view(-1, C) if mask is None else x2.new_empty(0), sa["mean"], sa["invstd"],
-                              sb["mean"], sb["invstd"])
-        ctx.meta = (flat, (wa, ba, sa["ws"]), (wb, bb, sb["ws"]), (N, C, H, W), x.dtype, r.dtype)
+        ctx.save_for_backward(x2, r2, y.view(-1, C) if mask is None else x2.new_empty(0), sa[4], sa[5], sb[4], sb[5])
+        ctx.meta = (flat, (wa, ba, sa[6]), (wb, bb, sb[6]), (N, C, H, W), x.dtype, r.dtype)
         ctx.set_materialize_grads(False)
         return nchw_view(y, C), nchw_view(y, C)
 
@@ -794,40 +782,24 @@ class _BatchNormDualNative(torch.autograd.Function):
             return (None,) * 9
 
         def nhwc2(t):
-            return as_nhwc(t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16), C,
-                           zero_pad=False).contiguous().view(-1, C)
+            return as_nhwc(_to_bf16(t), C, zero_pad=False).contiguous().view(-1, C)
 
         g2 = nhwc2(gy)
         gt = nhwc2(gy_twin) if gy_twin is not None else None
         dx = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=x2.device)
         dr = torch.empty_like(dx)
 
-        def grads(w, b):
-            dg, db = flat.grad_storage(w)[:C], flat.grad_storage(b)[:C]
-            fresh = [(dg, flat.grad_beta(w) == 0.0), (db, flat.grad_beta(b) == 0.0)]
-            assign = all(f for _, f in fresh)
-            if not assign:   # mixed (only if a caller accumulated one of them): clear the fresh ones
-                for t, f in fresh:
-                    if f:
-                        t.zero_()
-            return flat.master_storage(w)[:C], dg, db, assign
-
-        ga, dga, dba, asa = grads(wa, ba)
-        gb, dgb, dbb, asb = grads(wb, bb)
         C_.bn_dual_bwd(x2, r2, y2 if ctx.mask is None else x2, ctx.mask, g2, gt, dx.view(-1, C), dr.view(-1, C),
-                       ga, mean_a, inv_a, ws_a, dga, dba, asa, gb, mean_b, inv_b, ws_b, dgb, dbb, asb)
+                       flat.master_storage(wa)[:C], mean_a, inv_a, ws_a, *flat.affine_grads(wa, ba),
+                       flat.master_storage(wb)[:C], mean_b, inv_b, ws_b, *flat.affine_grads(wb, bb))
         flat.notify(wa, ba)
         flat.notify(wb, bb)
-        dxv, drv = nchw_view(dx, C), nchw_view(dr, C)
-        if x_dtype != torch.bfloat16:
-            dxv = dxv.to(x_dtype)
-        if r_dtype != torch.bfloat16:
-            drv = drv.to(r_dtype)
-        return dxv, drv, None, None, None, None, None, None, None
+        return (_from_bf16(nchw_view(dx, C), x_dtype), _from_bf16(nchw_view(dr, C), r_dtype),
+                None, None, None, None, None, None, None)
 
 
 # y = relu(bn_a(x) + bn_b(r)) in one pass (LDNN_BN_DUAL=0: bn_b's apply + bn_a's residual pass)
-BN_DUAL_FUSED = __import__("os").environ.get("LDNN_BN_DUAL", "1") != "0"
+BN_DUAL_FUSED = os.environ.get("LDNN_BN_DUAL", "1") != "0"
 
 
 def batch_norm_dual_act(x, mod_a, r, mod_b):
@@ -844,7 +816,7 @@ def batch_norm_dual_act(x, mod_a, r, mod_b):
 
 # BatchNorm + ReLU keeps a bit mask of the output for its backward (measured A/B in
 # profiles/, LDNN_BN_RELU_MASK=0 reads the bf16 output instead)
-BN_RELU_MASK = __import__("os").environ.get("LDNN_BN_RELU_MASK", "1") != "0"
+BN_RELU_MASK = os.environ.get("LDNN_BN_RELU_MASK", "1") != "0"
 
 
 def batch_norm_act(x, mod, residual=None, relu: bool = False):
@@ -875,16 +847,6 @@ def batch_norm2d(x, mod):
 
 
 # ------------------------------------------------------------------ GroupNorm
-def _gn_workspace(mod, n: int, dev) -> torch.Tensor:
-    """The module's persistent GroupNorm scratch (slab partials + coefficients; nothing in it is
-    kept between launches or needs zeroing).  It grows with the largest call seen, so a captured
-    step -- warmed up at its own shape first -- allocates nothing new."""
-    ws = mod.__dict__.get("_ldnn_gn_ws")
-    if ws is None or ws.device != dev or ws.numel() < n:
-        ws = mod.__dict__["_ldnn_gn_ws"] = torch.empty(n, dtype=torch.float32, device=dev)
-    return ws
-
-
 def _dense_nhwc(t: torch.Tensor) -> bool:
     """A logical [N, C, H, W] bf16 tensor that is a view of a dense, 16-byte aligned NHWC buffer
     (what every native conv / norm / pool op returns)."""
@@ -905,10 +867,9 @@ class _GroupNormNative(torch.autograd.Function):
         xb = x.as_strided((N, H, W, C), (H * W * C, W * C, C, 1), x.storage_offset())
         rb = None
         if residual is not None:
-            rb = as_nhwc(residual if residual.dtype == torch.bfloat16 else residual.to(torch.bfloat16), C,
-                         zero_pad=False)
+            rb = as_nhwc(_to_bf16(residual), C, zero_pad=False)
         y = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=dev)
-        ws = _gn_workspace(mod, C_.gn_workspace_floats(N, H * W, C, G), dev)
+        ws = _module_ws(mod, "_ldnn_gn_ws", C_.gn_workspace_floats(N, H * W, C, G), dev)   # (partials + coefficients)
         mean = torch.empty(N * G, dtype=torch.float32, device=dev)
         rstd = torch.empty(N * G, dtype=torch.float32, device=dev)
         gamma = flat.master_storage(weight)[:C] if weight is not None else None
@@ -931,29 +892,21 @@ class _GroupNormNative(torch.autograd.Function):
         xb, mean, rstd = ctx.saved_tensors
         flat, weight, bias, mod, G, has_res, res_dtype = ctx.meta
         N, H, W, C = xb.shape
-        g = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), C, zero_pad=False).contiguous()
+        g = as_nhwc(_to_bf16(gy), C, zero_pad=False).contiguous()
         if g.data_ptr() % 16:
             g = g.clone()
         dx = torch.empty_like(xb)
         dres = torch.empty_like(xb) if has_res and ctx.needs_input_grad[3] else None
-        gamma = flat.master_storage(weight)[:C] if weight is not None else None
-        dg = flat.grad_storage(weight)[:C] if weight is not None else None
-        db = flat.grad_storage(bias)[:C] if bias is not None else None
-        # first write of the step: the finalize stores dgamma / dbeta instead of adding
-        fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias)) if p is not None]
-        assign = all(f for _, f in fresh)
-        if not assign:   # mixed (only if a caller accumulated one of them): clear the fresh ones
-            for t, f in fresh:
-                if f:
-                    t.zero_()
-        ws = _gn_workspace(mod, C_.gn_workspace_floats(N, H * W, C, G), xb.device)
+        gamma, dg, db, assign = None, None, None, True
+        if weight is not None:   # first write of the step: the finalize stores dgamma / dbeta instead of adding
+            gamma = flat.master_storage(weight)[:C]
+            dg, db, assign = flat.affine_grads(weight, bias)
+        ws = _module_ws(mod, "_ldnn_gn_ws", C_.gn_workspace_floats(N, H * W, C, G), xb.device)
         C_.gn_bwd(xb, g, dx, dres, gamma, mean, rstd, ws, dg, db, G, ctx.mask is not None, mask=ctx.mask,
                   grad_assign=assign)
-        if flat is not None:
+        if weight is not None:
             flat.notify(weight, bias)
-        dresv = nchw_view(dres, C) if dres is not None else None
-        if dresv is not None and res_dtype != torch.bfloat16:
-            dresv = dresv.to(res_dtype)
+        dresv = _from_bf16(nchw_view(dres, C), res_dtype) if dres is not None else None
         return _zpad(nchw_view(dx, C)), None, None, dresv, None, None, None
 
 
@@ -978,16 +931,6 @@ def group_norm_act(x, mod, residual=None, relu: bool = False):
 
 
 # ------------------------------------------------------------------ LayerNorm
-def _ln_workspace(mod, n: int, dev) -> torch.Tensor:
-    """The module's persistent LayerNorm scratch (the backward's dgamma / dbeta partial rows; nothing
-    in it is kept between launches or needs zeroing).  It grows with the largest call seen, so a
-    captured step -- warmed up at its own shape first -- allocates nothing new."""
-    ws = mod.__dict__.get("_ldnn_ln_ws")
-    if ws is None or ws.device != dev or ws.numel() < n:
-        ws = mod.__dict__["_ldnn_ln_ws"] = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-    return ws
-
-
 def _ln_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else _up8(t.shape[1])   # (a single row's stride is arbitrary)
 
@@ -1045,21 +988,15 @@ class _LayerNormNative(torch.autograd.Function):
         x2, mean, rstd = ctx.saved_tensors
         flat, weight, bias, mod, act = ctx.meta
         B, N = x2.shape
-        g = _ln_rows(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16))
+        g = _ln_rows(_to_bf16(gy))
         dx = _ln_out_like(x2)
         gamma = beta = dg = db = ws = None
         assign = False
         if weight is not None:
             gamma, beta = flat.master_storage(weight), flat.master_storage(bias)
-            dg, db = flat.grad_storage(weight), flat.grad_storage(bias)
             # first write of the step: the finalize stores dgamma / dbeta instead of adding
-            fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias))]
-            assign = all(f for _, f in fresh)
-            if not assign:   # mixed (only if a caller accumulated one of them): clear the fresh one
-                for t, f in fresh:
-                    if f:
-                        t.zero_()
-            ws = _ln_workspace(mod, C_.ln_workspace_floats(B, N), x2.device)
+            dg, db, assign = flat.affine_grads(weight, bias)
+            ws = _module_ws(mod, "_ldnn_ln_ws", C_.ln_workspace_floats(B, N), x2.device)   # (the partial rows)
         C_.ln_bwd(x2, g, dx, gamma, beta, mean, rstd, ws, dg, db, -1 if act is None else act, grad_assign=assign)
         if weight is not None:
             flat.notify(weight, bias)
@@ -1112,7 +1049,7 @@ class _PoolNative(torch.autograd.Function):
         C_ = _ext.C()
         N, C, H, W = x.shape
         cp = _up8(C)
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), cp)
+        xb = as_nhwc(_to_bf16(x), cp)
         P, Q = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
         y = torch.empty(N, P, Q, cp, dtype=torch.bfloat16, device=x.device)
         am = torch.empty(N, P, Q, cp, dtype=torch.uint8, device=x.device) if is_max else None
@@ -1131,14 +1068,14 @@ class _PoolNative(torch.autograd.Function):
         if gy is None:
             return None, None, None, None, None
         am = ctx.saved_tensors[0] if is_max else None
-        g = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), cp).contiguous()
+        g = as_nhwc(_to_bf16(gy), cp).contiguous()
         gt = None
         if gy_twin is not None:
-            gt = as_nhwc(gy_twin if gy_twin.dtype == torch.bfloat16 else gy_twin.to(torch.bfloat16), cp).contiguous()
+            gt = as_nhwc(_to_bf16(gy_twin), cp).contiguous()
         dx = torch.empty(N, H, W, cp, dtype=torch.bfloat16, device=gy.device)
         C_.pool_bwd(g, am, dx, k, k, stride, pad, is_max, dy2=gt)
         out = _zpad(nchw_view(dx, C))   # (pooled gradient of zero pad channels)
-        return (out if in_dtype == torch.bfloat16 else out.to(in_dtype)), None, None, None, None
+        return _from_bf16(out, in_dtype), None, None, None, None
 
 
 class _BnReluMaxPoolNative(torch.autograd.Function):
@@ -1150,7 +1087,7 @@ class _BnReluMaxPoolNative(torch.autograd.Function):
     def forward(ctx, x, weight, bias, mod, flat, pad):
         C_ = _ext.C()
         N, C, H, W = x.shape
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), C, zero_pad=False).contiguous()
+        xb = as_nhwc(_to_bf16(x), C, zero_pad=False).contiguous()
         P, Q = (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1
         dev = x.device
         y = torch.empty(N, P, Q, C, dtype=torch.bfloat16, device=dev)
@@ -1160,16 +1097,8 @@ class _BnReluMaxPoolNative(torch.autograd.Function):
         ws = _bn_workspace(mod, C, dev, C_)
         gamma = flat.master_storage(weight)[:C] if weight is not None else None
         beta = flat.master_storage(bias)[:C] if bias is not None else None
-        pre = mod.__dict__.pop("_ldnn_pre", None)
-        if pre is not None and pre[0] == xb.data_ptr():
-            # statistics already accumulated + finalized by the producing conv's epilogue
-            smean, sinv = pre[1], pre[2]
-            C_.bn_pool_fwd(xb, y, am, gamma, beta, None, None, smean, sinv, ws, mod.eps, 0.0, None, True, pad, xam)
-        else:
-            smean = torch.empty(C, dtype=torch.float32, device=dev)
-            sinv = torch.empty(C, dtype=torch.float32, device=dev)
-            rm, rv, mom, nbt = _bn_train_state(mod, dev)
-            C_.bn_pool_fwd(xb, y, am, gamma, beta, rm, rv, smean, sinv, ws, mod.eps, mom or 0.0, nbt, False, pad, xam)
+        rm, rv, smean, sinv, mom, nbt, ready = _bn_stats_source(mod, xb, C)
+        C_.bn_pool_fwd(xb, y, am, gamma, beta, rm, rv, smean, sinv, ws, mod.eps, mom, nbt, ready, pad, xam)
         ctx.save_for_backward(xb, am, smean, sinv, xam)
         ctx.meta = (flat, weight, bias, ws, pad, C, x.dtype)
         ctx.set_materialize_grads(False)
@@ -1184,30 +1113,21 @@ class _BnReluMaxPoolNative(torch.autograd.Function):
             gy, gy_twin = gy_twin, None
         if gy is None:
             return None, None, None, None, None, None
-        g = as_nhwc(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16), C, zero_pad=False).contiguous()
+        g = as_nhwc(_to_bf16(gy), C, zero_pad=False).contiguous()
         gt = None
         if gy_twin is not None:
-            gt = as_nhwc(gy_twin if gy_twin.dtype == torch.bfloat16 else gy_twin.to(torch.bfloat16), C,
-                         zero_pad=False).contiguous()
+            gt = as_nhwc(_to_bf16(gy_twin), C, zero_pad=False).contiguous()
         dx = torch.empty_like(xb)
         gamma = flat.master_storage(weight)[:C] if weight is not None else None
-        dg = flat.grad_storage(weight)[:C] if weight is not None else None
-        db = flat.grad_storage(bias)[:C] if bias is not None else None
-        fresh = [(t, flat.grad_beta(p) == 0.0) for t, p in ((dg, weight), (db, bias)) if p is not None]
-        assign = all(f for _, f in fresh)
-        if not assign:
-            for t, f in fresh:
-                if f:
-                    t.zero_()
+        dg, db, assign = flat.affine_grads(weight, bias)
         C_.bn_pool_bwd(xb, g, am, dx, gamma, smean, sinv, ws, dg, db, assign, gt, pad, xam)
         flat.notify(weight, bias)
-        dxv = nchw_view(dx, C)
-        return (dxv if in_dtype == torch.bfloat16 else dxv.to(in_dtype)), None, None, None, None, None
+        return _from_bf16(nchw_view(dx, C), in_dtype), None, None, None, None, None
 
 
 # BN + ReLU + max-pool fused (LDNN_BN_POOL=0: the separate BN-apply and pool passes; 1: fused, the
 # backward statistics from the pooled side (x at the argmax); 2: fused, the statistics pass reads x)
-BN_POOL_MODE = int(__import__("os").environ.get("LDNN_BN_POOL", "1"))
+BN_POOL_MODE = int(os.environ.get("LDNN_BN_POOL", "1"))
 BN_POOL_FUSED = BN_POOL_MODE != 0
 
 
@@ -1242,7 +1162,7 @@ class _PoolFlatNative(torch.autograd.Function):
         C_ = _ext.C()
         N, C, H, W = x.shape
         cp = _up8(C)
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), cp)
+        xb = as_nhwc(_to_bf16(x), cp)
         P, Q = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
         y = torch.empty(N, C, P, Q, dtype=torch.bfloat16, device=x.device)
         am = torch.empty(N, P, Q, cp, dtype=torch.uint8, device=x.device) if is_max else None
@@ -1256,11 +1176,11 @@ class _PoolFlatNative(torch.autograd.Function):
         C_ = _ext.C()
         k, stride, pad, is_max, (N, C, H, W, cp), in_dtype = ctx.meta
         am = ctx.saved_tensors[0] if is_max else None
-        g = (gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16)).contiguous()
+        g = _to_bf16(gy).contiguous()
         dx = torch.empty(N, H, W, cp, dtype=torch.bfloat16, device=gy.device)
         C_.pool_bwd(g, am, dx, k, k, stride, pad, is_max, nchw_dy=True)
         out = _zpad(nchw_view(dx, C))
-        return (out if in_dtype == torch.bfloat16 else out.to(in_dtype)), None, None, None, None
+        return _from_bf16(out, in_dtype), None, None, None, None
 
 
 def pool2d(x, mod, is_max: bool):
@@ -1286,7 +1206,7 @@ class _GapNative(torch.autograd.Function):
         C_ = _ext.C()
         N, C, H, W = x.shape
         cp = _up8(C)
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), cp).contiguous()
+        xb = as_nhwc(_to_bf16(x), cp).contiguous()
         y = torch.empty(N, cp, dtype=torch.bfloat16, device=x.device)
         C_.gap_fwd(xb.view(N, H * W, cp), y)
         ctx.meta = (N, C, H, W, cp, x.dtype)
@@ -1305,7 +1225,7 @@ class _GapNative(torch.autograd.Function):
         dx = torch.empty(N, H, W, cp, dtype=torch.bfloat16, device=gy.device)
         C_.gap_bwd(g, dx.view(N, H * W, cp))
         out = nchw_view(dx, C)
-        return out if in_dtype == torch.bfloat16 else out.to(in_dtype)
+        return _from_bf16(out, in_dtype)
 
 
 def adaptive_avg_pool2d(x, output_size):
@@ -1325,7 +1245,7 @@ class _GapLinearNative(torch.autograd.Function):
         N, C, H, W = x.shape
         w = flat.shadow_storage(weight)
         npad = w.shape[0]
-        xb = as_nhwc(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16), C).contiguous()
+        xb = as_nhwc(_to_bf16(x), C).contiguous()
         pooled = torch.empty(N, C, dtype=torch.bfloat16, device=x.device)
         logits = torch.empty(N, npad, dtype=torch.bfloat16, device=x.device)
         b = flat.master_storage(bias) if bias is not None else None
@@ -1342,14 +1262,14 @@ class _GapLinearNative(torch.autograd.Function):
         (pooled,) = ctx.saved_tensors
         N, C, H, W, ncls, in_dtype = ctx.meta
         flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
-        g = gy if (gy.dtype == torch.bfloat16 and gy.stride(1) == 1) else gy.to(torch.bfloat16).contiguous()
+        g = _bf16_rows(gy)
         dx = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=gy.device)
         C_.gap_linear_bwd(g, pooled, flat.shadow_storage(weight), flat.grad_storage(weight),
                           flat.grad_storage(bias) if bias is not None else None, dx.view(N, H * W, C), ncls,
                           beta_w=flat.grad_beta(weight), beta_b=flat.grad_beta(bias) if bias is not None else 0.0)
         flat.notify(weight, bias)
         out = nchw_view(dx, C)
-        return (out if in_dtype == torch.bfloat16 else out.to(in_dtype)), None, None, None
+        return _from_bf16(out, in_dtype), None, None, None
 
 
 # LDNN_GAP_LINEAR=0: the pooled classifier head runs as separate pool + Linear ops (A/B knob)
@@ -1493,7 +1413,7 @@ class _DropoutNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, state):
         C = _ext.C()
-        x2 = _drop_rows(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
+        x2 = _drop_rows(_to_bf16(x))
         y = _drop_out_like(x2)
         ticket = torch.empty(8, dtype=torch.int32, device=x.device)
         C.dropout_fwd(x2, y, state.words, ticket)
@@ -1507,11 +1427,11 @@ class _DropoutNative(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (ticket,) = ctx.saved_tensors
-        g2 = _drop_rows(gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16))
+        g2 = _drop_rows(_to_bf16(gy))
         dx = _drop_out_like(g2)
         _ext.C().dropout_bwd(g2, dx, ticket)
         dx = dx if dx.shape == ctx.shape else dx.view(ctx.shape)
-        return (dx if ctx.in_dtype == torch.bfloat16 else dx.to(ctx.in_dtype)), None
+        return _from_bf16(dx, ctx.in_dtype), None
 
 
 def dropout(x, p: float = 0.5, training: bool = True, state: DropoutState | None = None):

@@ -222,6 +222,20 @@ class FlatParams:
         0.0), without consuming that state."""
         return id(p) in self._stale
 
+    def affine_grads(self, weight, bias):
+        """(dgamma, dbeta, assign) for a norm layer's backward, whose one finalize writes both
+        gradients: the whole grad_storage views (None for a missing parameter; freshness
+        consumed as by grad_beta) and whether that finalize stores (the step's first write)
+        instead of adding.  It stores only when every parameter present is fresh; in the mixed
+        case (a caller accumulated one of them) the fresh ones are cleared and it adds."""
+        views = [None if p is None else self.grad_storage(p) for p in (weight, bias)]
+        fresh = [v for v, p in zip(views, (weight, bias)) if p is not None and self.grad_beta(p) == 0.0]
+        assign = len(fresh) == sum(v is not None for v in views)
+        if not assign:
+            for v in fresh:
+                v.zero_()
+        return views[0], views[1], assign
+
     @torch.no_grad()
     def zero_grad(self, lazy: bool = False):
         """lazy: gradients that native ops write are only marked zero (their first

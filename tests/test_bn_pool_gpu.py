@@ -407,3 +407,83 @@ def test_bn_dual_act_matches_separate_and_fp32(N, C, H, W, twin, use_mask, monke
         assert rel(got, p.grad) < 5e-2
     for got, ref in zip(f["stats"], (ra.running_mean, ra.running_var, rb_.running_mean, rb_.running_var)):
         torch.testing.assert_close(got, ref, rtol=1e-3, atol=1e-3)
+
+
+def _three_backwards(params, flat, run):
+    """``run()`` is one forward + backward of a fused BN path.  A second backward without zero_grad
+    adds the same totals (the finalize adds: rtol 1e-3, atol 1e-5, test_layers_gpu's bound for the
+    same statement); after a lazy zero_grad the third is the step's first write and reproduces the
+    first (its bound for lazy against filled: rtol 1e-4, atol 1e-6).  Not bit equality: BatchNorm's
+    reductions are not claimed to be order-fixed."""
+    run()
+    first = [p.grad.clone() for p in params]
+    assert all(g.abs().max().item() > 0 for g in first)
+    run()
+    for p, g in zip(params, first):
+        torch.testing.assert_close(p.grad, 2 * g, rtol=1e-3, atol=1e-5)
+    flat.zero_grad(lazy=True)
+    assert all(flat.grad_fresh(p) for p in params)
+    run()
+    assert not flat._stale
+    for p, g in zip(params, first):
+        torch.testing.assert_close(p.grad, g, rtol=1e-4, atol=1e-6)
+
+
+def test_bn_dual_act_accumulates_and_lazy_zero_grad_overwrites():
+    torch.manual_seed(12)
+    N, C, H, W = 4, 64, 6, 6
+    ba, bb = BatchNorm2d(C), BatchNorm2d(C)
+    with torch.no_grad():
+        for b in (ba, bb):
+            b.weight.uniform_(-1.0, 1.5)
+            b.bias.uniform_(-0.5, 0.5)
+    ldnn.prepare(torch.nn.ModuleList([ba, bb]), "cuda")
+    x = _cl(torch.randn(N, C, H, W, device="cuda") * 1.5 + 0.2)
+    r = _cl(torch.randn(N, C, H, W, device="cuda") * 0.7 - 0.1)
+    g = torch.randn(N, C, H, W, device="cuda").bfloat16().float()
+
+    def run():
+        y = LF.batch_norm_dual_act(x.clone().requires_grad_(True), ba, r.clone().requires_grad_(True), bb)
+        assert "BatchNormDualNative" in type(y.grad_fn).__name__
+        (y.float() * g).sum().backward()
+
+    _three_backwards((ba.weight, ba.bias, bb.weight, bb.bias), ba._ldnn_flat, run)
+
+
+def test_bn_relu_maxpool_accumulates_and_lazy_zero_grad_overwrites():
+    N, C, H, W, pad = 2, 16, 11, 13, 1
+    bn, _, pool = _stem_pair(C, pad)
+    x = _cl(torch.randn(N, C, H, W, device="cuda") * 2 + 0.3)
+    g = torch.randn(N, C, (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1, device="cuda").bfloat16().float()
+
+    def run():
+        y = LF.bn_relu_maxpool(x.clone().requires_grad_(True), bn, pool)
+        assert "BnReluMaxPoolNative" in type(y.grad_fn).__name__
+        (y.float() * g).sum().backward()
+
+    _three_backwards((bn.weight, bn.bias), bn._ldnn_flat, run)
+
+
+def test_batchnorm_mixed_first_write_clears_only_the_fresh_gradient():
+    """One of weight / bias already written this step, the other still marked zero by the lazy
+    zero_grad: the backward adds onto the written one and clears the fresh one before adding its
+    total.  dgamma / dbeta come from one clean backward of an identically seeded twin."""
+    N, C, H, W = 4, 40, 5, 7
+    x = _cl(torch.randn(N, C, H, W, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3)) * 2 + 0.5)
+    g = torch.randn(N, C, H, W, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4))
+
+    def run(bn):
+        y = bn.act(x.clone().requires_grad_(True), None, True)
+        (y.float() * g).sum().backward()
+
+    (bn, _, _), (twin, _, _) = _stem_pair(C, 1, seed=6), _stem_pair(C, 1, seed=6)
+    run(twin)
+    dgamma, dbeta = twin.weight.grad.clone(), twin.bias.grad.clone()
+    flat = bn._ldnn_flat
+    run(bn)                                    # native ops write both; their buffers now hold old totals
+    flat.zero_grad(lazy=True)
+    bn.weight.grad.fill_(1.0)
+    assert flat.grad_beta(bn.weight) == 0.0    # a caller wrote the weight's gradient: no longer fresh
+    run(bn)
+    torch.testing.assert_close(bn.weight.grad, 1 + dgamma, rtol=1e-3, atol=1e-5)
+    torch.testing.assert_close(bn.bias.grad, dbeta, rtol=1e-3, atol=1e-5)

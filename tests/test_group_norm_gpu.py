@@ -167,6 +167,26 @@ def test_second_backward_accumulates_and_lazy_zero_grad_overwrites():
     torch.testing.assert_close(once_g, ref["dgamma"], rtol=2e-2, atol=2e-2 * ref["dgamma"].abs().max().item())
 
 
+def test_mixed_first_write_clears_only_the_fresh_gradient():
+    """The weight's gradient already written this step, the bias's still marked zero by the lazy
+    zero_grad: the backward adds dgamma onto the written one and clears the stale bias buffer before
+    adding dbeta (0 + total: the same bits as the store).  The totals come from one clean backward
+    of an identically seeded twin."""
+    shape = (3, 128, 5, 7, 32)
+    gn, twin = _module(shape[1], shape[4], seed=1), _module(shape[1], shape[4], seed=1)
+    flat = gn._ldnn_flat
+    x, r, dy = _inputs(shape, False)
+    _native(x, None, dy, twin, True)
+    dgamma, dbeta = twin.weight.grad.clone(), twin.bias.grad.clone()
+    _native(3 * x, None, dy, gn, True)        # native ops write both; their buffers now hold other totals
+    flat.zero_grad(lazy=True)
+    gn.weight.grad.fill_(1.0)
+    assert flat.grad_beta(gn.weight) == 0.0   # a caller wrote the weight's gradient: no longer fresh
+    _native(x, None, dy, gn, True)
+    torch.testing.assert_close(gn.weight.grad, 1 + dgamma, rtol=1e-6, atol=1e-6 * dgamma.abs().max().item())
+    assert torch.equal(gn.bias.grad, dbeta)
+
+
 def test_affine_false():
     gn = _check((3, 128, 5, 7, 32), True, True, affine=False)
     assert list(gn.parameters()) == []

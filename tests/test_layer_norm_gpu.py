@@ -174,6 +174,29 @@ def test_second_backward_accumulates_and_lazy_zero_grad_overwrites():
     assert flat.grad_storage(ln.weight)[N:].abs().max().item() == 0
 
 
+def test_mixed_first_write_clears_only_the_fresh_gradient():
+    """The weight's gradient already written this step, the bias's still marked zero by the lazy
+    zero_grad: the backward adds dgamma onto the written one and clears the stale bias storage (all
+    24 entries of the padded 20) before adding dbeta (0 + total: the same bits as the store).  The
+    totals come from one clean backward of an identically seeded twin."""
+    B, N = 5, 20
+    x, dy, gamma, beta, _ = _case(B, N)
+    ln, twin = _module(N, gamma, beta), _module(N, gamma, beta)
+    flat = ln._ldnn_flat
+    _native(twin, x, dy, "relu")
+    dgamma, dbeta = twin.weight.grad.clone(), twin.bias.grad.clone()
+    _native(ln, 3 * x, dy, "relu")            # native ops write both; their buffers now hold other totals
+    flat.zero_grad(lazy=True)
+    ln.weight.grad.fill_(1.0)
+    assert flat.grad_beta(ln.weight) == 0.0   # a caller wrote the weight's gradient: no longer fresh
+    _native(ln, x, dy, "relu")
+    torch.testing.assert_close(ln.weight.grad, 1 + dgamma, rtol=1e-6, atol=1e-6 * dgamma.abs().max().item())
+    assert torch.equal(ln.bias.grad, dbeta)
+    # the storages' pad entries (20 -> 24) stay zero
+    assert flat.grad_storage(ln.weight)[N:].abs().max().item() == 0
+    assert flat.grad_storage(ln.bias)[N:].abs().max().item() == 0
+
+
 def _up8(n):
     return (n + 7) // 8 * 8
 

@@ -108,6 +108,47 @@ def test_grad_fresh_peeks_without_consuming():
     assert not flat.grad_fresh(w) and flat.grad_beta(w) == 1.0   # ... and later ones accumulate
 
 
+def test_affine_grads_first_write_decision():
+    """FlatParams.affine_grads, the one first-write decision of the norm backwards: the whole padded
+    storage views, `assign` only when every parameter present is fresh (both consumed), and in the
+    mixed case the fresh one cleared over its whole storage, the other left alone."""
+    m = torch.nn.LayerNorm(20)
+    flat = FlatParams(m)
+    w, b = m.weight, m.bias
+    gw, gb = flat.grad_storage(w), flat.grad_storage(b)
+    assert gw.shape == gb.shape == (24,)                      # 20 padded to 24
+
+    def lazy_zero_and_fill():
+        flat.zero_grad(lazy=True)
+        gw.fill_(3.0)
+        gb.fill_(5.0)
+
+    def untouched(t, v):
+        return bool((t == v).all())
+
+    flat.grad_beta(w), flat.grad_beta(b)                      # native ops write both: zero_grad only marks them
+    lazy_zero_and_fill()                                      # both fresh
+    dg, db, assign = flat.affine_grads(w, b)
+    assert assign and untouched(gw, 3.0) and untouched(gb, 5.0)
+    assert dg.shape == db.shape == (24,) and dg.data_ptr() == gw.data_ptr() and db.data_ptr() == gb.data_ptr()
+    assert not flat.grad_fresh(w) and not flat.grad_fresh(b)  # both consumed ...
+    dg, db, assign = flat.affine_grads(w, b)                  # ... so now neither is fresh
+    assert not assign and untouched(gw, 3.0) and untouched(gb, 5.0)
+    for fresh, g_fresh, other, g_other, v_other in ((w, gw, b, gb, 5.0), (b, gb, w, gw, 3.0)):   # mixed, each way
+        lazy_zero_and_fill()
+        assert flat.grad_beta(other) == 0.0                   # a caller wrote `other` already this step
+        _, _, assign = flat.affine_grads(w, b)
+        assert not assign and untouched(g_fresh, 0.0) and untouched(g_other, v_other)
+        assert not flat.grad_fresh(fresh)
+    lazy_zero_and_fill()                                      # bias=None: the weight alone decides
+    dg, db, assign = flat.affine_grads(w, None)
+    assert assign and db is None and dg.data_ptr() == gw.data_ptr() and untouched(gw, 3.0) and untouched(gb, 5.0)
+    assert flat.grad_fresh(b)                                 # (the absent bias is not consumed)
+    dg, db, assign = flat.affine_grads(w, None)
+    assert not assign and db is None and untouched(gw, 3.0)
+    assert flat.affine_grads(None, None) == (None, None, True)
+
+
 @pytest.mark.parametrize("name", ["enhanced_cnn_small", "resnet18"])
 def test_downsample_blocks_cpu_match_separate_convs(name):
     """On the CPU (no native launch) LF.conv2d_pair is the two module calls: the downsampling
