@@ -81,6 +81,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "0 <= eps <= 1) inside the fused loss kernel; 0 (default) = off.  The same criterion serves "
                         "validation and the final test, so the reported val / test losses are the smoothed ones "
                         "(accuracy is unaffected)")
+    p.add_argument("--class_weights", type=str, default="none", metavar="{none,balanced,sqrt,W0,W1,...}",
+                   help="class weights of the cross-entropy (torch's weight=) inside the fused loss kernel, against "
+                        "class-skewed shards; none (default) = off, nothing is built.  balanced: n / (C_present * n_c) "
+                        "over THIS rank's current training shard (absent classes get 0), recomputed at every global "
+                        "epoch and after every re-partition, so ranks differ on purpose under --partition skewed; "
+                        "sqrt: 1 / sqrt(n_c), scaled to a mean per-sample weight of 1; or one finite weight >= 0 per "
+                        "class, comma-separated, written once.  The same criterion serves validation and the final "
+                        "test, so the reported val / test losses are the weighted ones (accuracy is unaffected).  "
+                        "metrics.jsonl then logs class_weight_min / class_weight_max per global epoch")
     p.add_argument("--dropout", type=float, default=0.0, metavar="P",
                    help="dropout at rate P (0 <= P < 1; 0 (default) = off, no module is built) after every hidden "
                         "layer of the MLPs, after LeNet-5's fc1 and fc2, in front of the classifier of the ResNets and "
@@ -252,6 +261,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "label_smoothing", 0.0) > 0:
         # the static engine's head kernels compute the plain loss
         why = "--label_smoothing runs on the autograd path"
+    elif getattr(args, "class_weights", "none") != "none":
+        # ... and has no weighted form
+        why = "--class_weights runs on the autograd path"
     elif getattr(args, "ema_decay", 0.0) > 0:
         # the static engine's wgrad-fused optimizer epilogue has no averaging pass behind it
         why = "--ema_decay runs on the autograd path"
@@ -319,6 +331,11 @@ def main(argv=None):
     schedule_from_args(args, max(args.warmup_steps, 0) + 1)
     if not 0.0 <= args.label_smoothing <= 1.0:
         raise SystemExit(f"--label_smoothing must be in [0, 1], got {args.label_smoothing}")
+    from .data.class_weights import class_weights_from_labels, parse_class_weights
+    try:
+        class_weights = parse_class_weights(args.class_weights)   # (the list's length: once the dataset is known)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
     if not 0.0 <= args.dropout < 1.0:
@@ -341,7 +358,7 @@ def main(argv=None):
     from . import prepare
     from .data.loader import get_loaders
     from .data.mix import BatchMix
-    from .models import CrossEntropyLoss, build_model, dataset_for, xavier_init
+    from .models import CrossEntropyLoss, WeightedCrossEntropyLoss, build_model, dataset_for, xavier_init
     from .optim import StepLR, build_optimizer
     from .parallel.comm import default_comm
     from .parallel.ddp import DataParallel
@@ -359,6 +376,12 @@ def main(argv=None):
     comm = default_comm(args.oneshot_bytes)
 
     dataset = args.dataset or dataset_for(args.model)
+    if class_weights is not None and not isinstance(class_weights, str):
+        from .data.datasets import CLASSES
+        try:
+            parse_class_weights(args.class_weights, CLASSES.get(dataset))
+        except ValueError as e:
+            raise SystemExit(str(e))
     try:
         model = build_model(args.model, dropout=args.dropout, norm=args.norm, gn_groups=args.gn_groups)
     except ValueError as e:   # (a --gn_groups that does not divide a width)
@@ -423,7 +446,18 @@ def main(argv=None):
     train_loader, val_loader, test_loader, trainset, valset, tr_idx, va_idx = loaders[:7]
     fixed_classes = loaders[7] if len(loaders) > 7 else None
 
-    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    if class_weights is None:
+        criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    else:
+        try:   # (a list: checked against the dataset's own class count)
+            w0 = (class_weights_from_labels(trainset.targets[tr_idx], trainset.num_classes, class_weights)
+                  if isinstance(class_weights, str) else parse_class_weights(args.class_weights, trainset.num_classes))
+        except ValueError as e:
+            raise SystemExit(str(e))
+        # the buffer lives on the training device from here on: the step graphs bake its address in,
+        # train_global rewrites its values in place (balanced / sqrt) at every global epoch
+        criterion = WeightedCrossEntropyLoss(weight=torch.from_numpy(w0),
+                                             label_smoothing=args.label_smoothing).to(dev)
     if not use_engine:
         lr_schedule = None
         if args.lr_schedule != "none":    # (every rank enters: the default horizon may take a collective)
@@ -489,7 +523,8 @@ def main(argv=None):
         seed=args.seed, legacy_gossip=args.legacy_gossip, average_buffers=args.average_buffers,
         check_every=args.check_every, progress=not args.quiet, logger=logger, checkpointer=ckpt,
         start_global_epoch=start, histories=hist, dtype=dtype, verbose=not args.quiet, timer=timer,
-        graphs=args.graphs, rng_state=rng_state, ref_samples_per_s=args.ref_samples_per_s)
+        graphs=args.graphs, rng_state=rng_state, ref_samples_per_s=args.ref_samples_per_s,
+        class_weights=class_weights)
     if timer is not None:
         phases = timer.summary()
         logger.log(kind="phase_times", phases=phases)

@@ -483,23 +483,41 @@ void mix3(const at::Tensor& out, const at::Tensor& x, const c10::optional<at::Te
 
 // Self-cleaning [acc0, acc1, counter] of the finalizing softmax-xent, one per
 // (device, stream): the kernels leave it zero, so it is zeroed once at creation.
-int* xent_fin_ws(const at::Tensor& like) {
+// Words 4..6 beside them: the weighted loss's [den, 1 / den, #kept rows] (fp32), written
+// by its pre-pass in front of every weighted launch.
+at::Tensor xent_ws_words(const at::Tensor& like) {
   static std::mutex mu;
   static std::map<std::pair<int, int64_t>, at::Tensor> pools;
   const auto key = std::make_pair((int)like.get_device(), (int64_t)cur_stream(like));
   std::lock_guard<std::mutex> lock(mu);
   auto it = pools.find(key);
-  if (it == pools.end()) it = pools.emplace(key, at::zeros({4}, like.options().dtype(at::kInt))).first;
-  return it->second.data_ptr<int>();
+  if (it == pools.end()) it = pools.emplace(key, at::zeros({8}, like.options().dtype(at::kInt))).first;
+  return it->second;
 }
+int* xent_fin_ws(const at::Tensor& like) { return xent_ws_words(like).data_ptr<int>(); }
+at::Tensor xent_wden_ws(const at::Tensor& like) { return xent_ws_words(like).slice(0, 4, 8).view(at::kFloat); }
 
 // softmax_xent (labels: int64 [B]) and softmax_xent_soft (target: fp32 [B, num_classes]); exactly one is given
 void xent_launch(const at::Tensor& logits, const at::Tensor* labels, const at::Tensor* target,
                  const at::Tensor& dlogits, const c10::optional<at::Tensor>& stats,
                  const c10::optional<at::Tensor>& dbias, int64_t num_classes, double grad_scale,
-                 const c10::optional<at::Tensor>& loss_out, double loss_scale, double label_smoothing) {
+                 const c10::optional<at::Tensor>& loss_out, double loss_scale, double label_smoothing,
+                 bool weighted = false, const c10::optional<at::Tensor>& weight = c10::nullopt,
+                 int64_t ignore_index = -100) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent: label_smoothing must be in [0, 1], got ",
               label_smoothing);
+  // class weights (the *_w entry points): fp32 [num_classes] beside the logits; finite and >= 0 is the
+  // caller's contract (a check would be a host sync)
+  const float* wt = nullptr;
+  if (weight.has_value()) {
+    TORCH_CHECK(weight->is_cuda() && weight->scalar_type() == at::kFloat,
+                "xent: weight must be a float32 GPU tensor, got ", weight->scalar_type(), " on ", weight->device());
+    TORCH_CHECK(weight->device() == logits.device(), "xent: weight is on ", weight->device(), ", logits on ",
+                logits.device());
+    TORCH_CHECK(weight->is_contiguous() && weight->numel() == num_classes, "xent: weight must be ", num_classes,
+                " contiguous floats (one per class), got sizes ", weight->sizes(), " strides ", weight->strides());
+    wt = weight->data_ptr<float>();
+  }
   check_dev(logits, at::kBFloat16, "logits");
   check_dev(dlogits, at::kBFloat16, "dlogits");
   if (labels) check_dev(*labels, at::kLong, "labels");
@@ -552,10 +570,27 @@ void xent_launch(const at::Tensor& logits, const at::Tensor* labels, const at::T
   if (target) {
     const int64_t ldq = target->size(0) > 1 ? target->stride(0) : std::max<int64_t>(num_classes, 1);
     TORCH_CHECK(ldq <= INT32_MAX, "xent: target row stride too large");
+    if (weighted) {
+      check(ldnn::softmax_xent_soft_w(bf16_ptr(logits), target->data_ptr<float>(), (int)ldq, bf16_mut(dlogits), st, db,
+                                      (int)logits.size(0), (int)num_classes, (int)ld, (float)grad_scale, wt,
+                                      cur_stream(logits), loss_out.has_value() ? &fin : nullptr,
+                                      (float)label_smoothing),
+            "softmax_xent_soft_w");
+      return;
+    }
     check(ldnn::softmax_xent_soft(bf16_ptr(logits), target->data_ptr<float>(), (int)ldq, bf16_mut(dlogits), st, db,
                                   (int)logits.size(0), (int)num_classes, (int)ld, (float)grad_scale,
                                   cur_stream(logits), loss_out.has_value() ? &fin : nullptr, (float)label_smoothing),
           "softmax_xent_soft");
+    return;
+  }
+  if (weighted) {
+    TORCH_CHECK(num_classes >= 1, "xent: no classes");
+    check(ldnn::softmax_xent_w(bf16_ptr(logits), labels->data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
+                               (int)logits.size(0), (int)num_classes, (int)ld, wt, ignore_index,
+                               xent_wden_ws(logits).data_ptr<float>(), cur_stream(logits),
+                               loss_out.has_value() ? &fin : nullptr, (float)label_smoothing),
+          "softmax_xent_w");
     return;
   }
   check(ldnn::softmax_xent(bf16_ptr(logits), labels->data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
@@ -578,6 +613,23 @@ void softmax_xent_soft(const at::Tensor& logits, const at::Tensor& target, const
                        double loss_scale, double label_smoothing) {
   xent_launch(logits, nullptr, &target, dlogits, stats, dbias, num_classes, grad_scale, loss_out, loss_scale,
               label_smoothing);
+}
+
+// The weighted forms: class weights (fp32 [num_classes], none = all 1) and, over labels, ignore_index
+void softmax_xent_w(const at::Tensor& logits, const at::Tensor& labels, const at::Tensor& dlogits,
+                    const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias, int64_t num_classes,
+                    const c10::optional<at::Tensor>& loss_out, double label_smoothing,
+                    const c10::optional<at::Tensor>& weight, int64_t ignore_index) {
+  xent_launch(logits, &labels, nullptr, dlogits, stats, dbias, num_classes, 0.0, loss_out, 1.0, label_smoothing,
+              true, weight, ignore_index);
+}
+
+void softmax_xent_soft_w(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& dlogits,
+                         const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias,
+                         int64_t num_classes, double grad_scale, const c10::optional<at::Tensor>& loss_out,
+                         double loss_scale, double label_smoothing, const c10::optional<at::Tensor>& weight) {
+  xent_launch(logits, nullptr, &target, dlogits, stats, dbias, num_classes, grad_scale, loss_out, loss_scale,
+              label_smoothing, true, weight);
 }
 
 // Mixup / CutMix of a batch with its permuted self + the dense soft targets, one launch (mix.hip)
@@ -2424,6 +2476,23 @@ PYBIND11_MODULE(_C, m) {
         py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,
         "softmax_xent with class-probability targets: fp32 [B, num_classes], inner stride 1 (torch's "
         "F.cross_entropy(logits, target, label_smoothing), mean reduction)");
+  m.def("softmax_xent_w", &softmax_xent_w, py::arg("logits"), py::arg("labels"), py::arg("dlogits"),
+        py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("loss_out") = py::none(),
+        py::arg("label_smoothing") = 0.0, py::arg("weight") = py::none(), py::arg("ignore_index") = -100,
+        "softmax_xent with class weights (fp32 [num_classes] on the logits' device, contiguous; finite and >= 0 is "
+        "the caller's contract; none = all 1) and ignore_index (torch's F.cross_entropy(weight=, ignore_index=, "
+        "label_smoothing=), mean reduction): a pre-pass launch sums the kept rows' weights on the device, the "
+        "loss launch divides by it.  loss_out = [weighted mean loss, #correct over kept rows]; stats gains "
+        "[B * mean loss, #correct].  A label outside [0, num_classes) counts as ignored; when nothing is kept "
+        "the loss and the gradient are 0 (torch: NaN)");
+  m.def("softmax_xent_soft_w", &softmax_xent_soft_w, py::arg("logits"), py::arg("target"), py::arg("dlogits"),
+        py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("grad_scale"),
+        py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,
+        py::arg("weight") = py::none(),
+        "softmax_xent_soft with class weights (as softmax_xent_w): targets weight * ((1 - eps) q + eps / C)");
+  m.def("xent_wden_ws", &xent_wden_ws, py::arg("like"),
+        "the current stream's [den, 1 / den, #kept rows, -] fp32 words the last softmax_xent_w pre-pass wrote "
+        "on like's device (a view of the persistent workspace)");
   m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("perm"), py::arg("labels"), py::arg("out"), py::arg("q"),
         py::arg("cutmix"), py::arg("lam"), py::arg("y0") = 0, py::arg("y1") = 0, py::arg("x0") = 0,
         py::arg("x1") = 0,

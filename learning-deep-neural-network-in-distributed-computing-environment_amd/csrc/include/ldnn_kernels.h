@@ -425,6 +425,24 @@ hipError_t softmax_xent(const uint16_t* logits, const int64_t* labels, uint16_t*
 hipError_t softmax_xent_soft(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,
                              float* dbias, int B, int C, int ld, float grad_scale, hipStream_t s,
                              const XentFin* fin = nullptr, float label_smoothing = 0.f);
+// Class weights and ignore_index over labels: torch's F.cross_entropy(logits, labels, weight=, ignore_index=,
+// label_smoothing=) with mean reduction.  weight: fp32 [C] on the device, finite and >= 0 (the caller's
+// contract), nullptr = all 1.  A row whose label is ignore_index -- or outside [0, C), which torch asserts
+// on: here it never indexes anything -- is ignored: a zero gradient row, nothing added to the loss, #correct
+// or dbias.  Two launches: a one-workgroup pre-pass writes wden_ws = {den, den > 0 ? 1 / den : 0, #kept rows}
+// (den = sum of weight[label] over the kept rows, a fixed-order reduction: the same bits on every run; at
+// least 3 floats that persist until the second launch has run), then the loss kernel divides by den from
+// there, so neither a host grad_scale nor fin.scale is taken.  den == 0 (nothing kept, or only classes of
+// weight 0): loss 0 and zero gradients where torch returns NaN.  fin.out = [weighted loss sum / den,
+// #correct over kept rows]; stats[0] gains B * fin.out[0] (with or without fin), stats[1] #correct.
+hipError_t softmax_xent_w(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
+                          float* dbias, int B, int C, int ld, const float* weight, int64_t ignore_index,
+                          float* wden_ws, hipStream_t s, const XentFin* fin = nullptr, float label_smoothing = 0.f);
+// Class weights over probability targets: softmax_xent_soft on t = weight (.) q' (one launch; the divisor
+// stays the host's: grad_scale and fin.scale, 1 / B for torch's mean).  weight as above.
+hipError_t softmax_xent_soft_w(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,
+                               float* dbias, int B, int C, int ld, float grad_scale, const float* weight,
+                               hipStream_t s, const XentFin* fin = nullptr, float label_smoothing = 0.f);
 // out[i] = src[i] * (*scale) over n bf16 (the loss backward's grad_output, read on the device)
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s);
 // ---- batch mixing (mix.hip): Mixup / CutMix of a contiguous [B][n] batch (n = C*H*W elements per image,

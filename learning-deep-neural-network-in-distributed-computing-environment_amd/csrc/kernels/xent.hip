@@ -31,6 +31,19 @@
 // already whole 256-B lines per wave instruction.  The LD = 64 rows instance holds
 // x, q' and the rounded gradient per lane without scratch (compiler output in
 // profiles/r13), so the soft mode keeps the plain mode's split between the kernels.
+//
+// Class weights and ignore_index (torch's weight= / ignore_index=, mean reduction; XM_W for
+// labels, XM_WSOFT for class-probability targets): the soft-target formula applied to
+// t_c = w_c q'_c.  The weights w (fp32 [C], or all 1 when none are given) are staged once per
+// workgroup into LDS.  Under labels the divisor is den = sum of w[label] over the kept rows (a
+// row is kept when its label is neither ignore_index nor outside [0, C)); xent_wden_kernel, one
+// workgroup reducing in a fixed order, writes {den, den > 0 ? 1 / den : 0, #kept} into a
+// persistent workspace in front of the loss launch, which reads 1 / den from there: no host sync,
+// the same bits on every run, and an all-ignored batch gives loss 0 and zero gradients (torch:
+// NaN).  An ignored row writes a zero gradient row and adds nothing to the loss, #correct or
+// dbias.  The finalize writes out[0] = weighted loss sum / den and adds B * out[0] into stats[0]
+// ("loss sum / samples" stays the mean loss).  Under probability targets den = B comes from the
+// host as before.  The PLAIN / SMOOTH / SOFT instances are the code as it was.
 #include <algorithm>
 
 #include "ldnn_common.h"
@@ -43,13 +56,16 @@ namespace {
 constexpr int kRowsPerBlock = 16;  // 4 rows per wave: B = 4096 -> 256 blocks fill the chip
 constexpr int kMaxColsPerLane = 16;  // C <= 1024
 
-enum XentMode { XM_PLAIN = 0, XM_SMOOTH = 1, XM_SOFT = 2 };
+enum XentMode { XM_PLAIN = 0, XM_SMOOTH = 1, XM_SOFT = 2, XM_W = 3, XM_WSOFT = 4 };
 
 // Last-block finalize (fin.out set): every block's statistic atomics are made
 // device-visible before its arrival is counted; the last arrival swaps the sums
 // out of the accumulator (leaving it zero), writes [loss_sum * scale, #correct]
 // and adds both into the running stats.
-__device__ __forceinline__ void xent_finish(const XentFin& fin, float* stats) {
+// XM_W: the scale is the pre-pass's 1 / den (device), and stats[0] gains B * out[0].
+template <int MODE = XM_PLAIN>
+__device__ __forceinline__ void xent_finish(const XentFin& fin, float* stats, const float* wden = nullptr,
+                                            int B = 0) {
   if (fin.out == nullptr) return;
   __threadfence();
   __syncthreads();
@@ -59,13 +75,54 @@ __device__ __forceinline__ void xent_finish(const XentFin& fin, float* stats) {
   if (!last || threadIdx.x != 0) return;
   __threadfence();
   const float l = atomicExch(fin.acc, 0.f), c = atomicExch(fin.acc + 1, 0.f);
-  fin.out[0] = l * fin.scale;
-  fin.out[1] = c;
-  if (stats) {
-    atomicAdd(stats, l);
-    atomicAdd(stats + 1, c);
+  if constexpr (MODE == XM_W) {
+    const float o = l * wden[1];
+    fin.out[0] = o;
+    fin.out[1] = c;
+    if (stats) {
+      atomicAdd(stats, o * (float)B);
+      atomicAdd(stats + 1, c);
+    }
+  } else {
+    fin.out[0] = l * fin.scale;
+    fin.out[1] = c;
+    if (stats) {
+      atomicAdd(stats, l);
+      atomicAdd(stats + 1, c);
+    }
   }
   atomicExch(fin.cnt, 0u);
+}
+
+// The denominator pre-pass of the weighted loss over labels: ws = {den, den > 0 ? 1 / den : 0,
+// #kept rows}, den = sum over the kept rows of w[label] (w == nullptr: 1).  One workgroup; a
+// thread sums its rows in row order, a wave its lanes by the fixed shuffle tree, thread 0 the
+// four wave sums in wave order: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void xent_wden_kernel(const int64_t* __restrict__ labels,
+                                                        const float* __restrict__ wt, int B, int C,
+                                                        int64_t ignore_index, float* __restrict__ ws) {
+  __shared__ float part[4][2];
+  float den = 0.f, kept = 0.f;
+  for (int r = threadIdx.x; r < B; r += 256) {
+    const int64_t lab = labels[r];
+    if (lab != ignore_index && lab >= 0 && lab < (int64_t)C) {
+      den += wt ? wt[lab] : 1.f;
+      kept += 1.f;
+    }
+  }
+  den = wave_sum(den);
+  kept = wave_sum(kept);
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6][0] = den;
+    part[threadIdx.x >> 6][1] = kept;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float d = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+    ws[0] = d;
+    ws[1] = d > 0.f ? 1.f / d : 0.f;
+    ws[2] = ((part[0][1] + part[1][1]) + part[2][1]) + part[3][1];
+  }
 }
 
 __global__ __launch_bounds__(256) void scale_bf16_kernel(const bf16_t* __restrict__ src, const float* __restrict__ scale,
@@ -88,10 +145,20 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
                                                    float* __restrict__ dbias, int B, int C, int ld,
                                                    float grad_scale, int rows_per_block, XentFin fin,
                                                    float conf, float epsc, const float* __restrict__ q,
-                                                   int ldq) {
-  constexpr bool SMOOTH = MODE == XM_SMOOTH, SOFT = MODE == XM_SOFT;
+                                                   int ldq, const float* __restrict__ wt,
+                                                   const float* __restrict__ wden, int64_t ignore_index) {
+  // QLOAD: the targets are rows of q; SOFT: the loss / gradient take the soft-target form
+  // (t = q', or w (.) q' in the weighted modes, where XM_W builds q' from the label)
+  constexpr bool SMOOTH = MODE == XM_SMOOTH, QLOAD = MODE == XM_SOFT || MODE == XM_WSOFT;
+  constexpr bool WH = MODE == XM_W, WT = WH || MODE == XM_WSOFT, SOFT = QLOAD || WH;
   __shared__ float sdb[4][kMaxColsPerLane * 64];
   __shared__ float sstat[4][2];
+  __shared__ float sw[WT ? kMaxColsPerLane * 64 : 1];  // the class weights (C <= ld <= 1024: 4 KB)
+  if constexpr (WT) {
+    for (int c = threadIdx.x; c < C; c += 256) sw[c] = wt ? wt[c] : 1.f;
+    __syncthreads();
+    if constexpr (WH) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
+  }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int nt = (ld + 63) / 64;
   float dacc[kMaxColsPerLane];
@@ -103,7 +170,21 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   for (int r = blockIdx.x * rows_per_block + w; r < r_end; r += 4) {
     const bf16_t* row = logits + (size_t)r * ld;
     int lab = 0;
-    if constexpr (!SOFT) lab = (int)labels[r];
+    if constexpr (WH) {
+      const int64_t l64 = labels[r];
+      if (l64 == ignore_index || l64 < 0 || l64 >= (int64_t)C) {
+        // ignored (or not a class: never indexes w or the row): a zero gradient row, nothing else
+#pragma unroll
+        for (int t = 0; t < kMaxColsPerLane; ++t) {
+          const int c = lane + 64 * t;
+          if (t < nt && c < ld) dlogits[(size_t)r * ld + c] = 0;
+        }
+        continue;
+      }
+      lab = (int)l64;
+    } else if constexpr (!QLOAD) {
+      lab = (int)labels[r];
+    }
     float xv[kMaxColsPerLane];
     float mx = -INFINITY;
     int amax = 0x7fffffff;
@@ -116,8 +197,16 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
         if (xv[t] > mx) { mx = xv[t]; amax = c; }
       }
     }
-    float qv[SOFT ? kMaxColsPerLane : 1];  // q' = conf q + epsc (0 beyond C)
-    if constexpr (SOFT) {
+    float qv[SOFT ? kMaxColsPerLane : 1];  // q' = conf q + epsc (0 beyond C); weighted: w (.) q'
+    if constexpr (WH) {
+#pragma unroll
+      for (int t = 0; t < kMaxColsPerLane; ++t) {
+        const int c = lane + 64 * t;
+        qv[t] = 0.f;
+        if (t < nt && c < C) qv[t] = sw[c] * (c == lab ? conf + epsc : epsc);
+      }
+    }
+    if constexpr (QLOAD) {
       const float* qrow = q + (size_t)r * ldq;
       float qm = -INFINITY;
       int qa = 0x7fffffff;
@@ -129,6 +218,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
           const float v = qrow[c];
           if (v > qm) { qm = v; qa = c; }
           qv[t] = conf * v + epsc;
+          if constexpr (WT) qv[t] *= sw[c];
         }
       }
       // the targets' first-index argmax stands in for the label
@@ -200,14 +290,20 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   __syncthreads();
   if (threadIdx.x == 0) {
     float* st = fin.out ? fin.acc : stats;
-    atomicAdd(st + 0, sstat[0][0] + sstat[1][0] + sstat[2][0] + sstat[3][0]);
+    if constexpr (WH) {
+      // straight into stats: this block's share of B * (weighted loss sum / den)
+      const float k = fin.out ? 1.f : grad_scale * (float)B;
+      atomicAdd(st + 0, (sstat[0][0] + sstat[1][0] + sstat[2][0] + sstat[3][0]) * k);
+    } else {
+      atomicAdd(st + 0, sstat[0][0] + sstat[1][0] + sstat[2][0] + sstat[3][0]);
+    }
     atomicAdd(st + 1, sstat[0][1] + sstat[1][1] + sstat[2][1] + sstat[3][1]);
   }
   if (dbias) {
     for (int c = threadIdx.x; c < ld; c += blockDim.x)
       atomicAdd(dbias + c, sdb[0][c] + sdb[1][c] + sdb[2][c] + sdb[3][c]);
   }
-  xent_finish(fin, stats);
+  xent_finish<MODE>(fin, stats, wden, B);
 }
 
 
@@ -222,8 +318,17 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
                                                         bf16_t* __restrict__ dlogits, float* __restrict__ stats,
                                                         float* __restrict__ dbias, int B, int C, int ld,
                                                         float grad_scale, XentFin fin, float conf, float epsc,
-                                                        const float* __restrict__ q, int ldq, bool qvec) {
-  constexpr bool SMOOTH = MODE == XM_SMOOTH, SOFT = MODE == XM_SOFT;
+                                                        const float* __restrict__ q, int ldq, bool qvec,
+                                                        const float* __restrict__ wt,
+                                                        const float* __restrict__ wden, int64_t ignore_index) {
+  constexpr bool SMOOTH = MODE == XM_SMOOTH, QLOAD = MODE == XM_SOFT || MODE == XM_WSOFT;
+  constexpr bool WH = MODE == XM_W, WT = WH || MODE == XM_WSOFT, SOFT = QLOAD || WH;
+  __shared__ float sw[WT ? LD : 1];  // the class weights (0 beyond C): every lane reads the same word
+  if constexpr (WT) {
+    if (threadIdx.x < LD) sw[threadIdx.x] = (int)threadIdx.x < C ? (wt ? wt[threadIdx.x] : 1.f) : 0.f;
+    __syncthreads();
+    if constexpr (WH) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
+  }
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool ok = r < B;
   float x[LD];
@@ -240,15 +345,32 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
       for (int j = 0; j < 8; ++j) x[v * 8 + j] = bf2f(q[j]);
     }
     int lab = 0;
-    if constexpr (!SOFT) lab = (int)labels[r];
+    bool keep = true;  // XM_W: false for an ignored label and for one that is no class
+    if constexpr (WH) {
+      const int64_t l64 = labels[r];
+      keep = l64 != ignore_index && l64 >= 0 && l64 < (int64_t)C;
+      lab = keep ? (int)l64 : 0;
+    } else if constexpr (!QLOAD) {
+      lab = (int)labels[r];
+    }
     float mx = -INFINITY;
     int am = 0;
 #pragma unroll
     for (int c = 0; c < LD; ++c)
       if (c < C && x[c] > mx) { mx = x[c]; am = c; }
     float se = 0.f, xl = 0.f, sx = 0.f;
-    float qv[SOFT ? LD : 1];  // q' = conf q + epsc (0 beyond C)
-    if constexpr (SOFT) {
+    float qv[SOFT ? LD : 1];  // q' = conf q + epsc (0 beyond C); weighted: w (.) q'
+    if constexpr (WH) {
+#pragma unroll
+      for (int c = 0; c < LD; ++c) {
+        qv[c] = 0.f;
+        if (c < C) {
+          qv[c] = sw[c] * (c == lab ? conf + epsc : epsc);
+          sx += qv[c];
+          xl += qv[c] * x[c];
+        }
+      }
+    } else if constexpr (QLOAD) {
       const float* qrow = q + (size_t)r * ldq;
 #pragma unroll
       for (int v = 0; v < LD / 4; ++v) {
@@ -269,6 +391,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
         if (c < C) {
           if (qv[c] > qm) { qm = qv[c]; lab = c; }  // first-index argmax of the raw targets
           qv[c] = conf * qv[c] + epsc;
+          if constexpr (WT) qv[c] *= sw[c];
           sx += qv[c];          // s = sum q'
           xl += qv[c] * x[c];   // sum q' x
         }
@@ -290,6 +413,9 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
     else if constexpr (SMOOTH) loss = mx + __logf(se) - conf * xl - epsc * sx;
     else loss = mx + __logf(se) - xl;  // = logsumexp - x_label
     correct = (am == lab) ? 1.f : 0.f;
+    if constexpr (WH) {
+      if (!keep) loss = correct = 0.f;
+    }
     float inv = 1.f / se;
     if constexpr (SOFT) inv *= sx;
     u16x8 out[LD / 8];
@@ -302,6 +428,9 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
         if (c < C) v = (x[c] * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
       } else {
         if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+      }
+      if constexpr (WH) {
+        if (!keep) v = 0.f;  // a zero gradient row
       }
       const uint16_t b = f2bf(v);
       out[c / 8][c % 8] = b;
@@ -331,27 +460,32 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
   __syncthreads();
   const int t = threadIdx.x;
   if (t < LD + 2 && (dbias || t >= LD)) {
-    const float v = part[0][t] + part[1][t] + part[2][t] + part[3][t];
+    float v = part[0][t] + part[1][t] + part[2][t] + part[3][t];
+    if constexpr (WH) {
+      // straight into stats: this block's share of B * (weighted loss sum / den)
+      if (t == LD && !fin.out) v *= grad_scale * (float)B;
+    }
     atomicAdd(t < LD ? dbias + t : (fin.out ? fin.acc : stats) + (t - LD), v);
   }
-  xent_finish(fin, stats);
+  xent_finish<MODE>(fin, stats, wden, B);
 }
 
 template <int MODE>
 hipError_t launch_xent(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats, float* dbias,
                        int B, int C, int ld, float grad_scale, hipStream_t s, const XentFin& fin, float conf,
-                       float epsc, const float* q = nullptr, int ldq = 0) {
-  // 16-B target loads in the rows kernel (XM_SOFT only)
+                       float epsc, const float* q = nullptr, int ldq = 0, const float* wt = nullptr,
+                       const float* wden = nullptr, int64_t ignore_index = -100) {
+  // 16-B target loads in the rows kernel (XM_SOFT / XM_WSOFT only)
   const bool qvec = (ldq % 4 == 0) && (reinterpret_cast<uintptr_t>(q) & 15) == 0;
   const bool vec_ok = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
   if (vec_ok && ld <= 64) {
     const int g = (B + 255) / 256;
     switch (ld) {
 #define XENT_ROWS_CASE(L) \
-      case L: xent_rows_kernel<L, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec); break;
+      case L: xent_rows_kernel<L, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec, wt, wden, ignore_index); break;
       XENT_ROWS_CASE(8) XENT_ROWS_CASE(16) XENT_ROWS_CASE(24) XENT_ROWS_CASE(32) XENT_ROWS_CASE(40) XENT_ROWS_CASE(48) XENT_ROWS_CASE(56)
 #undef XENT_ROWS_CASE
-      default: xent_rows_kernel<64, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec); break;
+      default: xent_rows_kernel<64, MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, fin, conf, epsc, q, ldq, qvec, wt, wden, ignore_index); break;
     }
     return hipGetLastError();
   }
@@ -359,7 +493,7 @@ hipError_t launch_xent(const uint16_t* logits, const int64_t* labels, uint16_t* 
   // instead of 4 waves walking 16 rows each), 16 rows per block beyond
   const int rpb = B <= 4 * 256 ? 4 : kRowsPerBlock;
   const int g = (B + rpb - 1) / rpb;
-  xent_kernel<MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin, conf, epsc, q, ldq);
+  xent_kernel<MODE><<<g, 256, 0, s>>>(logits, labels, dlogits, stats, dbias, B, C, ld, grad_scale, rpb, fin, conf, epsc, q, ldq, wt, wden, ignore_index);
   return hipGetLastError();
 }
 
@@ -391,6 +525,35 @@ hipError_t softmax_xent_soft(const uint16_t* logits, const float* q, int ldq, ui
   if (B <= 0) return hipSuccess;
   return launch_xent<XM_SOFT>(logits, nullptr, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin,
                               1.f - label_smoothing, label_smoothing / (float)C, q, ldq);
+}
+
+hipError_t softmax_xent_w(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
+                          float* dbias, int B, int C, int ld, const float* weight, int64_t ignore_index,
+                          float* wden_ws, hipStream_t s, const XentFin* finp, float label_smoothing) {
+  if (ld > kMaxColsPerLane * 64 || C > ld || C < 1 || wden_ws == nullptr) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return hipErrorInvalidValue;  // (NaN too)
+  const XentFin fin = finp ? *finp : XentFin{};
+  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
+  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  xent_wden_kernel<<<1, 256, 0, s>>>(labels, weight, B, C, ignore_index, wden_ws);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_xent<XM_W>(logits, labels, dlogits, stats, dbias, B, C, ld, 0.f, s, fin, 1.f - label_smoothing,
+                           label_smoothing / (float)C, nullptr, 0, weight, wden_ws, ignore_index);
+}
+
+hipError_t softmax_xent_soft_w(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,
+                               float* dbias, int B, int C, int ld, float grad_scale, const float* weight,
+                               hipStream_t s, const XentFin* finp, float label_smoothing) {
+  if (ld > kMaxColsPerLane * 64 || C > ld || C < 1 || ldq < C || q == nullptr) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return hipErrorInvalidValue;  // (NaN too)
+  const XentFin fin = finp ? *finp : XentFin{};
+  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
+  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  return launch_xent<XM_WSOFT>(logits, nullptr, dlogits, stats, dbias, B, C, ld, grad_scale, s, fin,
+                               1.f - label_smoothing, label_smoothing / (float)C, q, ldq, weight);
 }
 
 hipError_t scale_bf16_dev(const uint16_t* src, const float* scale, uint16_t* out, int64_t n, hipStream_t s) {

@@ -109,21 +109,67 @@ class CrossEntropyLoss(nn.CrossEntropyLoss):
     softmax-xent kernel.  Pass ``stats`` to accumulate loss-sum / #correct on device.
     ``label_smoothing`` is torch's, and so is the dispatch on the target: integer class
     indices [B] or floating class probabilities [B, C] (Mixup / CutMix, distillation).  Class
-    weights, ``ignore_index`` and the sum / none reductions are not implemented and refused."""
+    weights and ``ignore_index`` are refused here as before -- ``WeightedCrossEntropyLoss`` is the
+    criterion that takes them -- and so are the sum / none reductions."""
+
+    _ldnn_weighted = False   # (WeightedCrossEntropyLoss: True)
 
     def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
                  reduction: str = "mean", label_smoothing: float = 0.0):
         super().__init__(weight, size_average, ignore_index, reduce, reduction, label_smoothing)
-        if weight is not None:
-            raise NotImplementedError("ldnn CrossEntropyLoss: class weights are not implemented")
-        if ignore_index != -100:
-            raise NotImplementedError("ldnn CrossEntropyLoss: ignore_index is not implemented")
+        if not self._ldnn_weighted:
+            if weight is not None:
+                raise NotImplementedError("ldnn CrossEntropyLoss: class weights are not implemented here: use "
+                                          "WeightedCrossEntropyLoss(weight=...)")
+            if ignore_index != -100:
+                raise NotImplementedError("ldnn CrossEntropyLoss: ignore_index is not implemented here: use "
+                                          "WeightedCrossEntropyLoss(ignore_index=...)")
         if self.reduction != "mean":
             raise NotImplementedError(f"ldnn CrossEntropyLoss: reduction={self.reduction!r} is not implemented "
                                       "(mean only)")
 
     def forward(self, logits, labels, stats=None):
         return LF.cross_entropy(logits, labels, stats, self.label_smoothing)
+
+
+class WeightedCrossEntropyLoss(CrossEntropyLoss):
+    """``CrossEntropyLoss`` with torch's ``weight`` (one finite value >= 0 per class, kept as the
+    fp32 buffer ``weight``) and ``ignore_index``, on the weighted instances of the fused kernel
+    (a denominator pre-pass + the loss launch).  ``ops.functional.cross_entropy`` names the two
+    departures from torch: an all-ignored batch gives 0, not NaN, and a label that is no class
+    counts as ignored on the GPU.  With ``weight=None, ignore_index=-100`` it is ``CrossEntropyLoss``,
+    launch for launch.  The sum / none reductions are refused as there."""
+
+    _ldnn_weighted = True
+
+    def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
+                 reduction: str = "mean", label_smoothing: float = 0.0):
+        if weight is not None:
+            weight = torch.as_tensor(weight).detach().to(torch.float32).clone()
+            if weight.dim() != 1:
+                raise ValueError("ldnn WeightedCrossEntropyLoss: weight must be one value per class, got "
+                                 f"{tuple(weight.shape)}")
+        super().__init__(weight, size_average, int(ignore_index), reduce, reduction, label_smoothing)
+
+    def set_class_weights(self, values) -> None:
+        """Copy ``values`` (one per class) into the ``weight`` buffer in place: a host write to a
+        persistent address, outside any graph -- a captured step reads the new values at its next
+        replay.  The criterion must have been built with weights (a capture bakes their address in)."""
+        if self.weight is None:
+            raise ValueError("ldnn WeightedCrossEntropyLoss: built without class weights; pass weight= to the "
+                             "constructor")
+        v = torch.as_tensor(values, dtype=torch.float32)
+        if v.shape != self.weight.shape:
+            raise ValueError(f"ldnn WeightedCrossEntropyLoss: {tuple(self.weight.shape)} class weights expected, got "
+                             f"{tuple(v.shape)}")
+        with torch.no_grad():
+            self.weight.copy_(v)
+
+    def forward(self, logits, labels, stats=None):
+        w = self.weight
+        if w is not None and w.device != logits.device:   # (the buffer follows the logits once, then stays)
+            self.weight = w = w.to(logits.device)
+        return LF.cross_entropy(logits, labels, stats, self.label_smoothing, w, self.ignore_index)
 
 
 class Conv2d(nn.Conv2d):

@@ -217,7 +217,7 @@ def sigmoid(x):
 
 class _SoftmaxXentNative(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, stats, label_smoothing=0.0):
+    def forward(ctx, logits, labels, stats, label_smoothing=0.0, weight=None, ignore_index=-100):
         C = _ext.C()
         B, n = logits.shape
         lg = _bf16_rows(logits)
@@ -230,8 +230,17 @@ class _SoftmaxXentNative(torch.autograd.Function):
             q = labels if labels.dtype == torch.float32 else labels.float()
             if q.stride(1) != 1:
                 q = q.contiguous()
-            C.softmax_xent_soft(lg, q, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
-                                label_smoothing=label_smoothing)
+            if weight is not None:   # (ignore_index does not apply to probability targets, as in torch)
+                C.softmax_xent_soft_w(lg, q, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
+                                      label_smoothing=label_smoothing, weight=weight)
+            else:
+                C.softmax_xent_soft(lg, q, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
+                                    label_smoothing=label_smoothing)
+        elif weight is not None or ignore_index != -100:
+            # two launches: the pre-pass sums the kept rows' weights on the device, the loss kernel
+            # divides by that (no host divisor: the batch's weight sum is not known here)
+            C.softmax_xent_w(lg, labels, dfull[:, :n], stats, None, n, loss_out=out, label_smoothing=label_smoothing,
+                             weight=weight, ignore_index=ignore_index)
         else:
             C.softmax_xent(lg, labels, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
                            label_smoothing=label_smoothing)
@@ -245,19 +254,19 @@ class _SoftmaxXentNative(torch.autograd.Function):
         if ctx.in_dtype == torch.bfloat16 and getattr(go, "_ldnn_unit", False):
             # the graphed steps' persistent seed is exactly 1 (train.graphed.unit_seed): the
             # forward's d(mean loss)/d(logits) is the gradient as is, no scaling pass
-            return dfull[:, : ctx.n], None, None, None
+            return dfull[:, : ctx.n], None, None, None, None, None
         if ctx.in_dtype == torch.bfloat16 and go.dtype == torch.float32 and go.is_cuda and dfull.numel() % 8 == 0:
             # d = dlogits * grad_output in one pass over the padded rows (pad stays 0)
             full = torch.empty_like(dfull)
             _ext.C().scale_bf16(dfull, go.reshape(1), full)
-            return full[:, : ctx.n], None, None, None
+            return full[:, : ctx.n], None, None, None, None, None
         d = dfull[:, : ctx.n]
         d = (d.float() * go).to(torch.bfloat16) if ctx.in_dtype == torch.bfloat16 else d.float() * go
         if ctx.in_dtype == torch.bfloat16 and dfull.stride(0) != ctx.n:
             full = torch.zeros_like(dfull)
             full[:, : ctx.n] = d
             d = full[:, : ctx.n]
-        return d, None, None, None
+        return d, None, None, None, None, None
 
 
 def _soft_target(logits, target) -> bool:
@@ -274,7 +283,8 @@ def _soft_target(logits, target) -> bool:
                      f"got a target {tuple(target.shape)} ({target.dtype})")
 
 
-def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoothing: float = 0.0):
+def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoothing: float = 0.0,
+                  weight: torch.Tensor | None = None, ignore_index: int = -100):
     """Mean softmax cross-entropy.  `stats` (device fp32, >= 2) accumulates
     [sum of per-sample loss, #correct] without a host sync.  `label_smoothing` in [0, 1]:
     torch's smoothed targets eps / C + (1 - eps) * onehot (the loss, its gradient and the
@@ -283,19 +293,49 @@ def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoot
     The target is dispatched as torch does: an integer [B] tensor holds class indices, a
     floating [B, C] tensor class probabilities (rows are not normalised; smoothing applies to
     them too).  Under probability targets #correct counts the rows whose logits' argmax is the
-    target row's (first-index) argmax: agreement with the dominant label."""
+    target row's (first-index) argmax: agreement with the dominant label.
+
+    `weight` (fp32 [C], finite and >= 0: the caller's contract) and `ignore_index` are torch's: with
+    k_r = 0 for a row whose label is `ignore_index` (else 1) and q' the smoothed target row,
+    loss = sum_r k_r sum_c w_c q'_rc (lse_r - x_rc) / sum_r k_r w[y_r] over labels, and
+    sum_r sum_c w_c q'_rc (lse_r - x_rc) / B over probability targets (where `ignore_index` does not
+    apply).  `stats[0]` gains B * loss, `stats[1]` #correct over the kept rows.  Two departures from
+    torch: when nothing is kept, or every kept class has weight 0, the loss and its gradient are 0
+    (torch: NaN, which would poison every weight of a replayed step); and on the GPU a label
+    outside [0, C) that is not `ignore_index` counts as ignored (torch: a device assert).  With
+    `weight=None, ignore_index=-100` (the defaults) the call is the unweighted one, launch for launch."""
     label_smoothing = float(label_smoothing)
+    ignore_index = int(ignore_index)
+    if weight is not None and (weight.dim() != 1 or weight.shape[0] != logits.shape[-1]):
+        raise ValueError(f"cross_entropy: weight must hold one value per class [{logits.shape[-1]}], got "
+                         f"{tuple(weight.shape)}")
     if not 0.0 <= label_smoothing <= 1.0:
         raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
     soft = _soft_target(logits, labels)
     if _ext.use_native(logits):
-        return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing)
+        return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing, weight, ignore_index)
     lf = logits.float()
-    loss = F.cross_entropy(lf, labels.float() if soft else labels, label_smoothing=label_smoothing)
+    kept = None
+    if weight is None and (soft or ignore_index == -100):
+        loss = F.cross_entropy(lf, labels.float() if soft else labels, label_smoothing=label_smoothing)
+    elif soft:
+        loss = F.cross_entropy(lf, labels.float(), weight=weight.to(lf.device, lf.dtype),
+                               label_smoothing=label_smoothing)
+    else:
+        # torch's weighted mean is its weighted sum over the kept rows' weight sum; dividing here
+        # gives 0 (not 0 / 0) when that sum is 0, without reading it on the host
+        w = None if weight is None else weight.to(lf.device, lf.dtype)
+        kept = labels != ignore_index
+        safe = torch.where(kept, labels, torch.zeros_like(labels))
+        den = (kept.to(lf.dtype) if w is None else w[safe] * kept).sum()
+        tot = F.cross_entropy(lf, labels, weight=w, ignore_index=ignore_index, reduction="sum",
+                              label_smoothing=label_smoothing)
+        loss = tot / torch.where(den > 0, den, torch.ones_like(den))
     if stats is not None:
         with torch.no_grad():
+            hit = lf.argmax(1) == (labels.argmax(1) if soft else labels)
             stats[0] += loss.detach() * labels.shape[0]
-            stats[1] += (lf.argmax(1) == (labels.argmax(1) if soft else labels)).sum()
+            stats[1] += (hit if kept is None else hit & kept).sum()
     return loss
 
 

@@ -97,6 +97,32 @@ def check_label_smoothing(criterion, captured: float) -> None:
                            "was captured: capture again")
 
 
+def class_weight_key(criterion, device=None):
+    """What a capture bakes in of the criterion's class weights and ``ignore_index``: the weight
+    buffer's address (None: no weights) and the index -- kernel arguments, like the label
+    smoothing.  The VALUES behind the address are read by every replay.  With ``device`` (at
+    capture) a buffer that still lives elsewhere moves there first, so that the address is final."""
+    w = getattr(criterion, "weight", None)
+    if w is not None and device is not None and w.device != torch.device(device):
+        criterion.weight = w = w.to(device)
+    return (None if w is None else w.data_ptr(), int(getattr(criterion, "ignore_index", -100)))
+
+
+def check_class_weights(criterion, captured) -> None:
+    """A replay must find the weight buffer and ``ignore_index`` the capture saw: another tensor
+    (or weights that appeared or went away) would silently train with the captured address.
+    In-place changes of the values (``set_class_weights``) are fine.  Host compares only."""
+    now = class_weight_key(criterion)
+    if now[0] != captured[0]:
+        what = ("appeared" if captured[0] is None else "went away" if now[0] is None
+                else "became a different tensor")
+        raise RuntimeError(f"the criterion's class weights {what} since this step was captured (change the values "
+                           "in place with set_class_weights, or capture again)")
+    if now[1] != captured[1]:
+        raise RuntimeError(f"the criterion's ignore_index changed from {captured[1]} to {now[1]} since this step "
+                           "was captured: capture again")
+
+
 def static_input(model, x_example: torch.Tensor):
     """The graph's static input buffer and its per-step staging function.
 
@@ -162,6 +188,7 @@ class GraphedStep:
             raise ValueError("GraphedStep needs GPU tensors")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
+        self._class_weights = class_weight_key(criterion, x_example.device)   # (so are these)
         self.x, self._stage_x = static_input(model, x_example)
         self.y = y_example.detach().clone()
         self.stats = stats if stats is not None else torch.zeros(2, dtype=torch.float32, device=self.x.device)
@@ -234,6 +261,7 @@ class GraphedStep:
         if x.shape != self.x.shape or y.shape != self.y.shape or y.dtype != self.y.dtype:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
+        check_class_weights(self.criterion, self._class_weights)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         self.graph.replay()
@@ -301,6 +329,7 @@ class GraphedDPStep:
             raise ValueError("GraphedDPStep needs GPU tensors")
         self.dp, self.model, self.criterion, self.optimizer = dp, dp.module, criterion, optimizer
         self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
+        self._class_weights = class_weight_key(criterion, x_example.device)   # (so are these)
         self.bk, self.flat, self.comm = dp.bucketer, dp.flat, dp.comm
         self._SUM = SUM
         self.comm_fn = comm_fn
@@ -548,6 +577,7 @@ class GraphedDPStep:
         if x.shape != self.x.shape or y.shape != self.y.shape or y.dtype != self.y.dtype:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
+        check_class_weights(self.criterion, self._class_weights)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         works = {}

@@ -289,7 +289,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                  check_every: int = 20, progress: bool = True, logger=None, checkpointer=None,
                  start_global_epoch: int = 0, histories=None, dtype=torch.float32, verbose: bool = True,
                  timer: PhaseTimer | None = None, graphs: bool = False, rng_state=None,
-                 ref_samples_per_s: float | None = None):
+                 ref_samples_per_s: float | None = None, class_weights=None):
     """``rng_state`` (resume): the re-partition RNG state saved in the checkpoint's
     ``extra`` -- with it, a resumed run draws the same shards as an uninterrupted one.
 
@@ -297,7 +297,13 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
     by all ranks, whole-job samples/s over the epoch's wall time (training,
     validation, exchange, aggregation, barrier) and, given ``ref_samples_per_s``
     (one GPU's measured rate for the same model / batch), the data-parallel scaling
-    efficiency = samples/s / (N x ref)."""
+    efficiency = samples/s / (N x ref).
+
+    ``class_weights`` (--class_weights): ``"balanced"`` / ``"sqrt"`` recompute the criterion's class
+    weights from THIS rank's training shard at the start of every global epoch and after every
+    re-partition and write them in place (``criterion.set_class_weights``: host writes outside the
+    step graphs, which follow); an array stands for weights the caller wrote once.  Either way the
+    epoch's record gains ``class_weight_min`` / ``class_weight_max`` (host values)."""
     comm = comm or default_comm()
     tm = timer or null_timer()
     N = comm.world_size
@@ -328,6 +334,19 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
         step_aggregator = Aggregator(topology, aggregation_type, "gradients", local_weight, comm, legacy_gossip)
     cutoff = StragglerCutoff(comm, timelimit, check_every, dev)
 
+    def shard_class_weights(idx):
+        """The criterion's weights for the shard ``idx`` (rules: recomputed and written), as host values."""
+        if class_weights is None:
+            return None
+        if not isinstance(class_weights, str):
+            return np.asarray(class_weights, dtype=np.float32)
+        from ..data.class_weights import class_weights_from_labels
+
+        w = class_weights_from_labels(np.asarray(trainset.targets)[np.asarray(idx)], trainset.num_classes,
+                                      class_weights)
+        criterion.set_class_weights(w)
+        return w
+
     for global_epoch in _progress(range(start_global_epoch, num_global_epochs), progress and rank == 0,
                                   "Global Epochs"):
         t_start = time.perf_counter()
@@ -337,6 +356,9 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
         # first epoch (the throughput probe) do not matter.  Host writes, outside the step graphs
         if isinstance(model, torch.nn.Module):
             reseed_dropout(model, loader_seed(seed, rank, global_epoch))
+        # class weights of this rank's current shard, likewise (a resumed run starts from its own shard)
+        cw = shard_class_weights(indices_train)
+        cw_rec = {} if cw is None else {"class_weight_min": float(cw.min()), "class_weight_max": float(cw.max())}
         max_steps = None
         dp_tail = False
         epoch_loader = trainloader   # (re-partitioning replaces it before the epoch's record is written)
@@ -450,6 +472,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                 rng, replace, fixed_classes, fixed_ratio, dtype=dtype,
                 augment=getattr(trainloader, "augment", False), augment_val=bool(getattr(val_loader, "mode", 0)),
                 loader_seed=loader_seed(seed, rank, global_epoch + 1), mix=getattr(trainloader, "mix", None))
+            shard_class_weights(indices_train)   # the new shard's weights (validation after the loop sees them too)
         # batch mixing: the mean lam of this epoch's plans on this rank (host data, no sync)
         lam_mean = getattr(epoch_loader, "pop_mix_lam_mean", lambda: None)()
         mix_rec = {} if lam_mean is None else {"mix_lam_mean": lam_mean}
@@ -490,7 +513,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                        samples_per_s=total_samples / max(duration, 1e-12),
                        train_samples_per_s_per_rank=[s_ / max(duration, 1e-12) for s_ in samples_per_rank],
                        **({"scaling_efficiency": total_samples / max(duration, 1e-12) / (N * ref_samples_per_s)}
-                          if ref_samples_per_s else {}), **clip_rec, **mix_rec)
+                          if ref_samples_per_s else {}), **clip_rec, **mix_rec, **cw_rec)
         if checkpointer is not None:
             checkpointer.save(global_epoch + 1, model, optimizer, scheduler, H,
                               extra=dict(indices_train=np.asarray(indices_train),
