@@ -90,6 +90,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "class, comma-separated, written once.  The same criterion serves validation and the final "
                         "test, so the reported val / test losses are the weighted ones (accuracy is unaffected).  "
                         "metrics.jsonl then logs class_weight_min / class_weight_max per global epoch")
+    p.add_argument("--focal_gamma", type=float, default=0.0, metavar="G",
+                   help="focal loss (Lin et al. 2017) inside the fused loss kernel, against easy samples dominating "
+                        "the gradient on class-skewed shards: a sample's loss is w[y] (1 - p)^G (-log p), p its "
+                        "softmax probability of the true class, over the weight sum of the batch; G finite and >= 0, "
+                        "0 (default) = off, the criterion is the one without it.  w comes from --class_weights (1 "
+                        "without), whose per-epoch recomputation keeps working.  Not defined with --label_smoothing, "
+                        "--mixup or --cutmix: those combinations exit.  The same criterion serves validation and the "
+                        "final test, so the reported val / test losses are the focal ones (accuracy is unaffected)")
     p.add_argument("--dropout", type=float, default=0.0, metavar="P",
                    help="dropout at rate P (0 <= P < 1; 0 (default) = off, no module is built) after every hidden "
                         "layer of the MLPs, after LeNet-5's fc1 and fc2, in front of the classifier of the ResNets and "
@@ -264,6 +272,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "class_weights", "none") != "none":
         # ... and has no weighted form
         why = "--class_weights runs on the autograd path"
+    elif getattr(args, "focal_gamma", 0.0) > 0:
+        # ... nor a focal one
+        why = "--focal_gamma runs on the autograd path"
     elif getattr(args, "ema_decay", 0.0) > 0:
         # the static engine's wgrad-fused optimizer epilogue has no averaging pass behind it
         why = "--ema_decay runs on the autograd path"
@@ -336,6 +347,14 @@ def main(argv=None):
         class_weights = parse_class_weights(args.class_weights)   # (the list's length: once the dataset is known)
     except ValueError as e:
         raise SystemExit(str(e))
+    if not (args.focal_gamma >= 0.0 and math.isfinite(args.focal_gamma)):
+        raise SystemExit(f"--focal_gamma must be finite and >= 0, got {args.focal_gamma}")
+    if args.focal_gamma > 0:
+        for flag, v in (("--label_smoothing", args.label_smoothing), ("--mixup", args.mixup),
+                        ("--cutmix", args.cutmix)):
+            if v > 0:
+                raise SystemExit(f"--focal_gamma with {flag}: there is no agreed focal loss over smoothed or "
+                                 "class-probability targets; drop one of the two")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
     if not 0.0 <= args.dropout < 1.0:
@@ -358,7 +377,7 @@ def main(argv=None):
     from . import prepare
     from .data.loader import get_loaders
     from .data.mix import BatchMix
-    from .models import CrossEntropyLoss, WeightedCrossEntropyLoss, build_model, dataset_for, xavier_init
+    from .models import CrossEntropyLoss, FocalLoss, WeightedCrossEntropyLoss, build_model, dataset_for, xavier_init
     from .optim import StepLR, build_optimizer
     from .parallel.comm import default_comm
     from .parallel.ddp import DataParallel
@@ -447,7 +466,8 @@ def main(argv=None):
     fixed_classes = loaders[7] if len(loaders) > 7 else None
 
     if class_weights is None:
-        criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
+        criterion = (FocalLoss(gamma=args.focal_gamma) if args.focal_gamma > 0
+                     else CrossEntropyLoss(label_smoothing=args.label_smoothing))
     else:
         try:   # (a list: checked against the dataset's own class count)
             w0 = (class_weights_from_labels(trainset.targets[tr_idx], trainset.num_classes, class_weights)
@@ -456,8 +476,9 @@ def main(argv=None):
             raise SystemExit(str(e))
         # the buffer lives on the training device from here on: the step graphs bake its address in,
         # train_global rewrites its values in place (balanced / sqrt) at every global epoch
-        criterion = WeightedCrossEntropyLoss(weight=torch.from_numpy(w0),
-                                             label_smoothing=args.label_smoothing).to(dev)
+        criterion = (FocalLoss(gamma=args.focal_gamma, weight=torch.from_numpy(w0)).to(dev) if args.focal_gamma > 0
+                     else WeightedCrossEntropyLoss(weight=torch.from_numpy(w0),
+                                                   label_smoothing=args.label_smoothing).to(dev))
     if not use_engine:
         lr_schedule = None
         if args.lr_schedule != "none":    # (every rank enters: the default horizon may take a collective)

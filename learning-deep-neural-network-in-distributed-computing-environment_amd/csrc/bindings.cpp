@@ -6,6 +6,7 @@
 #include <torch/extension.h>
 #include <pybind11/stl.h>
 #include <vector>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <mutex>
@@ -503,7 +504,7 @@ void xent_launch(const at::Tensor& logits, const at::Tensor* labels, const at::T
                  const c10::optional<at::Tensor>& dbias, int64_t num_classes, double grad_scale,
                  const c10::optional<at::Tensor>& loss_out, double loss_scale, double label_smoothing,
                  bool weighted = false, const c10::optional<at::Tensor>& weight = c10::nullopt,
-                 int64_t ignore_index = -100) {
+                 int64_t ignore_index = -100, const double* focal_gamma = nullptr) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent: label_smoothing must be in [0, 1], got ",
               label_smoothing);
   // class weights (the *_w entry points): fp32 [num_classes] beside the logits; finite and >= 0 is the
@@ -586,6 +587,14 @@ void xent_launch(const at::Tensor& logits, const at::Tensor* labels, const at::T
   }
   if (weighted) {
     TORCH_CHECK(num_classes >= 1, "xent: no classes");
+    if (focal_gamma) {  // softmax_xent_focal: the weighted launch pair with the focal loss instances
+      check(ldnn::softmax_xent_focal(bf16_ptr(logits), labels->data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
+                                     (int)logits.size(0), (int)num_classes, (int)ld, wt, ignore_index,
+                                     xent_wden_ws(logits).data_ptr<float>(), (float)*focal_gamma, cur_stream(logits),
+                                     loss_out.has_value() ? &fin : nullptr),
+            "softmax_xent_focal");
+      return;
+    }
     check(ldnn::softmax_xent_w(bf16_ptr(logits), labels->data_ptr<int64_t>(), bf16_mut(dlogits), st, db,
                                (int)logits.size(0), (int)num_classes, (int)ld, wt, ignore_index,
                                xent_wden_ws(logits).data_ptr<float>(), cur_stream(logits),
@@ -622,6 +631,18 @@ void softmax_xent_w(const at::Tensor& logits, const at::Tensor& labels, const at
                     const c10::optional<at::Tensor>& weight, int64_t ignore_index) {
   xent_launch(logits, &labels, nullptr, dlogits, stats, dbias, num_classes, 0.0, loss_out, 1.0, label_smoothing,
               true, weight, ignore_index);
+}
+
+// The focal loss over labels on the weighted path: gamma >= 0 and finite (0: softmax_xent_w itself)
+void softmax_xent_focal(const at::Tensor& logits, const at::Tensor& labels, const at::Tensor& dlogits,
+                        const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& dbias,
+                        int64_t num_classes, double gamma, const c10::optional<at::Tensor>& weight,
+                        int64_t ignore_index, const c10::optional<at::Tensor>& loss_out) {
+  // (float)gamma must stay finite too: the kernel takes it in fp32
+  TORCH_CHECK(gamma >= 0.0 && std::isfinite((float)gamma), "softmax_xent_focal: gamma must be finite and >= 0, got ",
+              gamma);
+  xent_launch(logits, &labels, nullptr, dlogits, stats, dbias, num_classes, 0.0, loss_out, 1.0, 0.0, true, weight,
+              ignore_index, &gamma);
 }
 
 void softmax_xent_soft_w(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& dlogits,
@@ -2485,6 +2506,13 @@ PYBIND11_MODULE(_C, m) {
         "loss launch divides by it.  loss_out = [weighted mean loss, #correct over kept rows]; stats gains "
         "[B * mean loss, #correct].  A label outside [0, num_classes) counts as ignored; when nothing is kept "
         "the loss and the gradient are 0 (torch: NaN)");
+  m.def("softmax_xent_focal", &softmax_xent_focal, py::arg("logits"), py::arg("labels"), py::arg("dlogits"),
+        py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("gamma"),
+        py::arg("weight") = py::none(), py::arg("ignore_index") = -100, py::arg("loss_out") = py::none(),
+        "softmax_xent_w with the focal loss (Lin et al. 2017): a kept row's loss is weight[y] (1 - p)^gamma (-log p), "
+        "p = softmax(logits)[y], divided by the kept rows' weight sum like the weighted loss; the same two launches, "
+        "workspace, ignore_index and loss_out / stats conventions.  gamma must be finite and >= 0; 0 is "
+        "softmax_xent_w.  A row whose 1 - p underflows contributes loss 0 and a zero gradient row");
   m.def("softmax_xent_soft_w", &softmax_xent_soft_w, py::arg("logits"), py::arg("target"), py::arg("dlogits"),
         py::arg("stats"), py::arg("dbias") = py::none(), py::arg("num_classes"), py::arg("grad_scale"),
         py::arg("loss_out") = py::none(), py::arg("loss_scale") = 1.0, py::arg("label_smoothing") = 0.0,

@@ -438,6 +438,15 @@ hipError_t softmax_xent_soft(const uint16_t* logits, const float* q, int ldq, ui
 hipError_t softmax_xent_w(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
                           float* dbias, int B, int C, int ld, const float* weight, int64_t ignore_index,
                           float* wden_ws, hipStream_t s, const XentFin* fin = nullptr, float label_smoothing = 0.f);
+// Focal loss over labels (Lin et al. 2017) on softmax_xent_w's machinery: with a = weight[y] (1 without
+// weights), p = softmax(x)[y] and q = 1 - p a kept row has loss a q^gamma (-log p) and the gradient row
+// a f (softmax - onehot) / den, f = q^gamma + gamma p q^(gamma-1) (-log p); den, the pre-pass, wden_ws,
+// ignored rows, den == 0, fin.out and stats exactly as softmax_xent_w.  A row whose q underflows (p rounds
+// to 1) contributes loss 0 and a zero gradient row; nothing stored is ever NaN or inf.  gamma must be finite
+// and >= 0 (hipErrorInvalidValue otherwise); 0 is softmax_xent_w itself.  No label smoothing.
+hipError_t softmax_xent_focal(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
+                              float* dbias, int B, int C, int ld, const float* weight, int64_t ignore_index,
+                              float* wden_ws, float gamma, hipStream_t s, const XentFin* fin = nullptr);
 // Class weights over probability targets: softmax_xent_soft on t = weight (.) q' (one launch; the divisor
 // stays the host's: grad_scale and fin.scale, 1 / B for torch's mean).  weight as above.
 hipError_t softmax_xent_soft_w(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,

@@ -44,6 +44,18 @@
 // dbias.  The finalize writes out[0] = weighted loss sum / den and adds B * out[0] into stats[0]
 // ("loss sum / samples" stays the mean loss).  Under probability targets den = B comes from the
 // host as before.  The PLAIN / SMOOTH / SOFT instances are the code as it was.
+//
+// Focal loss (Lin et al. 2017; XM_FOCAL, labels only, no smoothing): with a = w[y], p = softmax(x)[y],
+// q = 1 - p, nlp = -log p and m = q^gamma a kept row has
+//   loss_r  = a m nlp
+//   dlogits = a f (softmax - onehot) / den,   f = m + gamma p q^(gamma-1) nlp = m (1 + gamma p nlp / q)
+// i.e. the cross-entropy gradient row times one scalar per row, on the XM_W machinery (staged weights, the
+// den pre-pass, ignored rows, the finalize).  q is formed from the other classes' exponentials,
+// sum_{c != y} e_c / sum_c e_c (no cancellation; one more wave_sum in the wave kernel, a register sum in
+// the rows kernel), and nlp as -log1p(-q) where q < 1/2 (lse - x_y cancels there), lse - x_y otherwise.
+// A row whose q is below the smallest normal fp32 (p rounds to 1) takes m = f = 0: loss 0 and a zero gradient
+// row, q^(gamma-1) is never formed at 0 and nothing stored is NaN or inf.  gamma (> 0: the host sends 0 to
+// XM_W) travels in the `conf` argument, which like epsc and the host's grad_scale this mode does not use.
 #include <algorithm>
 
 #include "ldnn_common.h"
@@ -56,13 +68,25 @@ namespace {
 constexpr int kRowsPerBlock = 16;  // 4 rows per wave: B = 4096 -> 256 blocks fill the chip
 constexpr int kMaxColsPerLane = 16;  // C <= 1024
 
-enum XentMode { XM_PLAIN = 0, XM_SMOOTH = 1, XM_SOFT = 2, XM_W = 3, XM_WSOFT = 4 };
+enum XentMode { XM_PLAIN = 0, XM_SMOOTH = 1, XM_SOFT = 2, XM_W = 3, XM_WSOFT = 4, XM_FOCAL = 5 };
+
+// The focal row scalars from q = sum_{c != y} e_c / sum_c e_c, p = e_y / sum_c e_c and lse - x_y:
+// m = q^gamma and f = m (1 + gamma p nlp / q), both 0 once q is below the smallest normal fp32; returns nlp.
+// nlp / q -> 1 as q -> 0 and p nlp <= 1 / e, so no factor overflows for any finite gamma > 0.
+__device__ __forceinline__ float focal_terms(float q, float p, float lse_m_xl, float gamma, float& m, float& f) {
+  m = f = 0.f;
+  if (!(q >= 1.17549435e-38f)) return 0.f;
+  const float nlp = q < 0.5f ? -log1pf(-q) : lse_m_xl;
+  m = __builtin_amdgcn_exp2f(gamma * __builtin_amdgcn_logf(q));  // v_exp_f32 / v_log_f32 are base 2
+  f = m + (gamma * m) * (p * (nlp / q));
+  return nlp;
+}
 
 // Last-block finalize (fin.out set): every block's statistic atomics are made
 // device-visible before its arrival is counted; the last arrival swaps the sums
 // out of the accumulator (leaving it zero), writes [loss_sum * scale, #correct]
 // and adds both into the running stats.
-// XM_W: the scale is the pre-pass's 1 / den (device), and stats[0] gains B * out[0].
+// XM_W / XM_FOCAL: the scale is the pre-pass's 1 / den (device), and stats[0] gains B * out[0].
 template <int MODE = XM_PLAIN>
 __device__ __forceinline__ void xent_finish(const XentFin& fin, float* stats, const float* wden = nullptr,
                                             int B = 0) {
@@ -75,7 +99,7 @@ __device__ __forceinline__ void xent_finish(const XentFin& fin, float* stats, co
   if (!last || threadIdx.x != 0) return;
   __threadfence();
   const float l = atomicExch(fin.acc, 0.f), c = atomicExch(fin.acc + 1, 0.f);
-  if constexpr (MODE == XM_W) {
+  if constexpr (MODE == XM_W || MODE == XM_FOCAL) {
     const float o = l * wden[1];
     fin.out[0] = o;
     fin.out[1] = c;
@@ -150,14 +174,16 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   // QLOAD: the targets are rows of q; SOFT: the loss / gradient take the soft-target form
   // (t = q', or w (.) q' in the weighted modes, where XM_W builds q' from the label)
   constexpr bool SMOOTH = MODE == XM_SMOOTH, QLOAD = MODE == XM_SOFT || MODE == XM_WSOFT;
-  constexpr bool WH = MODE == XM_W, WT = WH || MODE == XM_WSOFT, SOFT = QLOAD || WH;
+  constexpr bool WH = MODE == XM_W, SOFT = QLOAD || WH;
+  // FOCAL shares XM_W's label handling, 1 / den and finalize (WL) and the staged weights (WT)
+  constexpr bool FOCAL = MODE == XM_FOCAL, WL = WH || FOCAL, WT = WL || MODE == XM_WSOFT;
   __shared__ float sdb[4][kMaxColsPerLane * 64];
   __shared__ float sstat[4][2];
   __shared__ float sw[WT ? kMaxColsPerLane * 64 : 1];  // the class weights (C <= ld <= 1024: 4 KB)
   if constexpr (WT) {
     for (int c = threadIdx.x; c < C; c += 256) sw[c] = wt ? wt[c] : 1.f;
     __syncthreads();
-    if constexpr (WH) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
+    if constexpr (WL) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int nt = (ld + 63) / 64;
@@ -170,7 +196,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   for (int r = blockIdx.x * rows_per_block + w; r < r_end; r += 4) {
     const bf16_t* row = logits + (size_t)r * ld;
     int lab = 0;
-    if constexpr (WH) {
+    if constexpr (WL) {
       const int64_t l64 = labels[r];
       if (l64 == ignore_index || l64 < 0 || l64 >= (int64_t)C) {
         // ignored (or not a class: never indexes w or the row): a zero gradient row, nothing else
@@ -237,6 +263,13 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
     for (int t = 0; t < kMaxColsPerLane; ++t) {
       const int c = lane + 64 * t;
       if (t < nt && c < C) {
+        if constexpr (FOCAL) {
+          const float e = __expf(xv[t] - wmx);
+          se += e;
+          if (c == lab) xl = xv[t];
+          else sx += e;  // the other classes' exponentials
+          continue;
+        }
         se += __expf(xv[t] - wmx);
         if constexpr (SOFT) {
           xl += qv[t] * xv[t];  // sum q' x
@@ -249,16 +282,25 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
     }
     se = wave_sum(se);
     xl = wave_sum(xl);
-    if constexpr (SMOOTH || SOFT) sx = wave_sum(sx);
+    if constexpr (SMOOTH || SOFT || FOCAL) sx = wave_sum(sx);
     const float lse = wmx + __logf(se);
     float inv = 1.f / se;
     if constexpr (SOFT) inv *= sx;
+    if constexpr (FOCAL) {
+      // from here on sx is the row's loss a m nlp and xl its gradient factor a f / den
+      float m, f;
+      const float nlp = focal_terms(sx * inv, __expf(xl - wmx) * inv, lse - xl, conf, m, f);
+      sx = sw[lab] * m * nlp;
+      xl = sw[lab] * f * grad_scale;
+    }
 #pragma unroll
     for (int t = 0; t < kMaxColsPerLane; ++t) {
       const int c = lane + 64 * t;
       if (t < nt && c < ld) {
         float g = 0.f;
-        if constexpr (SOFT) {
+        if constexpr (FOCAL) {
+          if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? 1.f : 0.f)) * xl;
+        } else if constexpr (SOFT) {
           if (c < C) g = (__expf(xv[t] - wmx) * inv - qv[t]) * grad_scale;
         } else if constexpr (SMOOTH) {
           if (c < C) g = (__expf(xv[t] - wmx) * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
@@ -271,7 +313,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
       }
     }
     if (lane == 0) {
-      if constexpr (SOFT) loss_sum += sx * lse - xl;
+      if constexpr (FOCAL) loss_sum += sx;
+      else if constexpr (SOFT) loss_sum += sx * lse - xl;
       else if constexpr (SMOOTH) loss_sum += lse - conf * xl - epsc * sx;
       else loss_sum += lse - xl;
       correct += (cand == lab) ? 1.f : 0.f;
@@ -290,7 +333,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const bf16_t* __restrict__ lo
   __syncthreads();
   if (threadIdx.x == 0) {
     float* st = fin.out ? fin.acc : stats;
-    if constexpr (WH) {
+    if constexpr (WL) {
       // straight into stats: this block's share of B * (weighted loss sum / den)
       const float k = fin.out ? 1.f : grad_scale * (float)B;
       atomicAdd(st + 0, (sstat[0][0] + sstat[1][0] + sstat[2][0] + sstat[3][0]) * k);
@@ -322,12 +365,14 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
                                                         const float* __restrict__ wt,
                                                         const float* __restrict__ wden, int64_t ignore_index) {
   constexpr bool SMOOTH = MODE == XM_SMOOTH, QLOAD = MODE == XM_SOFT || MODE == XM_WSOFT;
-  constexpr bool WH = MODE == XM_W, WT = WH || MODE == XM_WSOFT, SOFT = QLOAD || WH;
+  constexpr bool WH = MODE == XM_W, SOFT = QLOAD || WH;
+  // FOCAL shares XM_W's label handling, 1 / den and finalize (WL) and the staged weights (WT)
+  constexpr bool FOCAL = MODE == XM_FOCAL, WL = WH || FOCAL, WT = WL || MODE == XM_WSOFT;
   __shared__ float sw[WT ? LD : 1];  // the class weights (0 beyond C): every lane reads the same word
   if constexpr (WT) {
     if (threadIdx.x < LD) sw[threadIdx.x] = (int)threadIdx.x < C ? (wt ? wt[threadIdx.x] : 1.f) : 0.f;
     __syncthreads();
-    if constexpr (WH) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
+    if constexpr (WL) grad_scale = wden[1];  // 1 / den of the pre-pass (0: nothing kept)
   }
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool ok = r < B;
@@ -345,8 +390,8 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
       for (int j = 0; j < 8; ++j) x[v * 8 + j] = bf2f(q[j]);
     }
     int lab = 0;
-    bool keep = true;  // XM_W: false for an ignored label and for one that is no class
-    if constexpr (WH) {
+    bool keep = true;  // XM_W / XM_FOCAL: false for an ignored label and for one that is no class
+    if constexpr (WL) {
       const int64_t l64 = labels[r];
       keep = l64 != ignore_index && l64 >= 0 && l64 < (int64_t)C;
       lab = keep ? (int)l64 : 0;
@@ -413,7 +458,22 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
     else if constexpr (SMOOTH) loss = mx + __logf(se) - conf * xl - epsc * sx;
     else loss = mx + __logf(se) - xl;  // = logsumexp - x_label
     correct = (am == lab) ? 1.f : 0.f;
-    if constexpr (WH) {
+    if constexpr (FOCAL) {
+      float el = 0.f, so = 0.f;  // the label's exponential and the other classes' sum
+#pragma unroll
+      for (int c = 0; c < LD; ++c) {
+        if (c < C) {
+          if (c == lab) el = x[c];
+          else so += x[c];
+        }
+      }
+      // from here on loss is the row's a m nlp and xl its gradient factor a f / den
+      float m, f;
+      const float nlp = focal_terms(so / se, el / se, loss, conf, m, f);
+      loss = sw[lab] * m * nlp;
+      xl = sw[lab] * f * grad_scale;
+    }
+    if constexpr (WL) {
       if (!keep) loss = correct = 0.f;
     }
     float inv = 1.f / se;
@@ -422,14 +482,16 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int c = 0; c < LD; ++c) {
       float v = 0.f;
-      if constexpr (SOFT) {
+      if constexpr (FOCAL) {
+        if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * xl;
+      } else if constexpr (SOFT) {
         if (c < C) v = (x[c] * inv - qv[c]) * grad_scale;
       } else if constexpr (SMOOTH) {
         if (c < C) v = (x[c] * inv - (c == lab ? conf + epsc : epsc)) * grad_scale;
       } else {
         if (c < C) v = (x[c] * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
       }
-      if constexpr (WH) {
+      if constexpr (WL) {
         if (!keep) v = 0.f;  // a zero gradient row
       }
       const uint16_t b = f2bf(v);
@@ -461,7 +523,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const bf16_t* __restrict
   const int t = threadIdx.x;
   if (t < LD + 2 && (dbias || t >= LD)) {
     float v = part[0][t] + part[1][t] + part[2][t] + part[3][t];
-    if constexpr (WH) {
+    if constexpr (WL) {
       // straight into stats: this block's share of B * (weighted loss sum / den)
       if (t == LD && !fin.out) v *= grad_scale * (float)B;
     }
@@ -541,6 +603,25 @@ hipError_t softmax_xent_w(const uint16_t* logits, const int64_t* labels, uint16_
   if (e != hipSuccess) return e;
   return launch_xent<XM_W>(logits, labels, dlogits, stats, dbias, B, C, ld, 0.f, s, fin, 1.f - label_smoothing,
                            label_smoothing / (float)C, nullptr, 0, weight, wden_ws, ignore_index);
+}
+
+hipError_t softmax_xent_focal(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits, float* stats,
+                              float* dbias, int B, int C, int ld, const float* weight, int64_t ignore_index,
+                              float* wden_ws, float gamma, hipStream_t s, const XentFin* finp) {
+  if (!(gamma >= 0.f && gamma <= 3.402823466e+38f)) return hipErrorInvalidValue;  // negative, NaN, inf
+  if (gamma == 0.f)  // the weighted cross-entropy itself: the focal instances never see 0
+    return softmax_xent_w(logits, labels, dlogits, stats, dbias, B, C, ld, weight, ignore_index, wden_ws, s, finp, 0.f);
+  if (ld > kMaxColsPerLane * 64 || C > ld || C < 1 || wden_ws == nullptr) return hipErrorInvalidValue;
+  const XentFin fin = finp ? *finp : XentFin{};
+  if (fin.out && (fin.acc == nullptr || fin.cnt == nullptr)) return hipErrorInvalidValue;
+  if (!fin.out && stats == nullptr) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  xent_wden_kernel<<<1, 256, 0, s>>>(labels, weight, B, C, ignore_index, wden_ws);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // gamma rides in `conf`; epsc and the host's grad_scale are unused under this mode
+  return launch_xent<XM_FOCAL>(logits, labels, dlogits, stats, dbias, B, C, ld, 0.f, s, fin, gamma, 0.f, nullptr, 0,
+                               weight, wden_ws, ignore_index);
 }
 
 hipError_t softmax_xent_soft_w(const uint16_t* logits, const float* q, int ldq, uint16_t* dlogits, float* stats,

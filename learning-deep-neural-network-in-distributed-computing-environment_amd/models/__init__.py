@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock  # noqa: F401
-from .layers import (NORMS, CrossEntropyLoss, Dropout, GroupNorm, LayerNorm, Linear,  # noqa: F401
+from .layers import (NORMS, CrossEntropyLoss, Dropout, FocalLoss, GroupNorm, LayerNorm, Linear,  # noqa: F401
                      WeightedCrossEntropyLoss, reseed_dropout)
 from .mlp import MLP, mlp2, mlp3  # noqa: F401
 from .resnet import ResNet, resnet18  # noqa: F401

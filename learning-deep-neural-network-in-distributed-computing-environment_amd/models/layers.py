@@ -8,6 +8,7 @@ shadow + flat gradient buffer) by ``ldnn.prepare`` / ``FlatParams(model)``.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -170,6 +171,37 @@ class WeightedCrossEntropyLoss(CrossEntropyLoss):
         if w is not None and w.device != logits.device:   # (the buffer follows the logits once, then stays)
             self.weight = w = w.to(logits.device)
         return LF.cross_entropy(logits, labels, stats, self.label_smoothing, w, self.ignore_index)
+
+
+class FocalLoss(WeightedCrossEntropyLoss):
+    """The focal loss of Lin et al. 2017 over integer labels, on the focal instances of the fused kernel:
+    a kept row's loss is ``weight[y] (1 - p)^gamma (-log p)`` with ``p = softmax(logits)[y]``, divided by the
+    kept rows' weight sum as in ``WeightedCrossEntropyLoss``, whose ``weight``, ``ignore_index``,
+    ``set_class_weights`` and departures from torch it keeps.  ``gamma`` (finite, >= 0) is a plain
+    attribute; 0 is the weighted cross-entropy, launch for launch.  Label smoothing and class-probability
+    targets are refused (no agreed definition), and so are the sum / none reductions."""
+
+    def __init__(self, gamma: float = 2.0, weight=None, ignore_index: int = -100, reduction: str = "mean",
+                 label_smoothing: float = 0.0):
+        if label_smoothing != 0.0:
+            raise ValueError(f"ldnn FocalLoss: label_smoothing={label_smoothing} is not defined for the focal loss")
+        gamma = float(gamma)
+        if not (gamma >= 0.0 and math.isfinite(gamma)):
+            raise ValueError(f"ldnn FocalLoss: gamma must be finite and >= 0, got {gamma}")
+        super().__init__(weight, None, ignore_index, None, reduction, 0.0)
+        self.gamma = gamma
+
+    def extra_repr(self) -> str:
+        return f"gamma={self.gamma}, ignore_index={self.ignore_index}"
+
+    def forward(self, logits, labels, stats=None):
+        if labels.is_floating_point():
+            raise ValueError("ldnn FocalLoss: class-probability targets (Mixup / CutMix) are not defined for the "
+                             f"focal loss, got a {tuple(labels.shape)} {labels.dtype} target")
+        w = self.weight
+        if w is not None and w.device != logits.device:   # (the buffer follows the logits once, then stays)
+            self.weight = w = w.to(logits.device)
+        return LF.cross_entropy(logits, labels, stats, 0.0, w, self.ignore_index, self.gamma)
 
 
 class Conv2d(nn.Conv2d):

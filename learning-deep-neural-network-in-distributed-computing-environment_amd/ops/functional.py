@@ -13,6 +13,7 @@ bookkeeping (K14, K15; BAR/trainer.py:207-216).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -217,7 +218,7 @@ def sigmoid(x):
 
 class _SoftmaxXentNative(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, stats, label_smoothing=0.0, weight=None, ignore_index=-100):
+    def forward(ctx, logits, labels, stats, label_smoothing=0.0, weight=None, ignore_index=-100, focal_gamma=0.0):
         C = _ext.C()
         B, n = logits.shape
         lg = _bf16_rows(logits)
@@ -236,6 +237,10 @@ class _SoftmaxXentNative(torch.autograd.Function):
             else:
                 C.softmax_xent_soft(lg, q, dfull[:, :n], stats, None, n, 1.0 / B, loss_out=out, loss_scale=1.0 / B,
                                     label_smoothing=label_smoothing)
+        elif focal_gamma > 0.0:
+            # the weighted pair of launches with the focal instances (labels, no smoothing: cross_entropy checks)
+            C.softmax_xent_focal(lg, labels, dfull[:, :n], stats, None, n, gamma=focal_gamma, weight=weight,
+                                 ignore_index=ignore_index, loss_out=out)
         elif weight is not None or ignore_index != -100:
             # two launches: the pre-pass sums the kept rows' weights on the device, the loss kernel
             # divides by that (no host divisor: the batch's weight sum is not known here)
@@ -254,19 +259,53 @@ class _SoftmaxXentNative(torch.autograd.Function):
         if ctx.in_dtype == torch.bfloat16 and getattr(go, "_ldnn_unit", False):
             # the graphed steps' persistent seed is exactly 1 (train.graphed.unit_seed): the
             # forward's d(mean loss)/d(logits) is the gradient as is, no scaling pass
-            return dfull[:, : ctx.n], None, None, None, None, None
+            return dfull[:, : ctx.n], None, None, None, None, None, None
         if ctx.in_dtype == torch.bfloat16 and go.dtype == torch.float32 and go.is_cuda and dfull.numel() % 8 == 0:
             # d = dlogits * grad_output in one pass over the padded rows (pad stays 0)
             full = torch.empty_like(dfull)
             _ext.C().scale_bf16(dfull, go.reshape(1), full)
-            return full[:, : ctx.n], None, None, None, None, None
+            return full[:, : ctx.n], None, None, None, None, None, None
         d = dfull[:, : ctx.n]
         d = (d.float() * go).to(torch.bfloat16) if ctx.in_dtype == torch.bfloat16 else d.float() * go
         if ctx.in_dtype == torch.bfloat16 and dfull.stride(0) != ctx.n:
             full = torch.zeros_like(dfull)
             full[:, : ctx.n] = d
             d = full[:, : ctx.n]
-        return d, None, None, None, None, None
+        return d, None, None, None, None, None, None
+
+
+class _FocalFallback(torch.autograd.Function):
+    """The focal loss of cross_entropy(focal_gamma > 0) in fp32 torch ops, with the closed-form gradient
+    the kernels use: autograd through (1 - p) ** gamma gives NaN at p == 1 for gamma < 1."""
+
+    @staticmethod
+    def forward(ctx, lf, labels, weight, ignore_index, gamma):
+        ncls = lf.shape[1]
+        kept = (labels != ignore_index) & (labels >= 0) & (labels < ncls)
+        safe = torch.where(kept, labels, torch.zeros_like(labels))
+        hot = F.one_hot(safe, ncls).bool()
+        lse = torch.logsumexp(lf, 1)
+        xl = lf.gather(1, safe[:, None])[:, 0]
+        # q = 1 - p from the other classes' exponentials (no cancellation); a single class has q = 0
+        q = (torch.exp(torch.logsumexp(lf.masked_fill(hot, float("-inf")), 1) - lse) if ncls > 1
+             else torch.zeros_like(lse))
+        p = torch.exp(xl - lse)
+        pos = q >= torch.finfo(lf.dtype).tiny   # below: p rounds to 1, the row contributes nothing
+        qs = torch.where(pos, q, torch.ones_like(q))
+        nlp = torch.where(q < 0.5, -torch.log1p(-q), lse - xl)
+        m = torch.where(pos, qs ** gamma, torch.zeros_like(q))
+        f = m + (gamma * m) * (p * (nlp / qs))
+        a = kept.to(lf.dtype) if weight is None else weight[safe] * kept
+        den = a.sum()
+        inv = torch.where(den > 0, 1.0 / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        ctx.save_for_backward((a * f * inv)[:, None] * (torch.softmax(lf, 1) - hot.to(lf.dtype)))
+        ctx.mark_non_differentiable(kept)
+        return (a * m * nlp).sum() * inv, kept
+
+    @staticmethod
+    def backward(ctx, go, _):
+        (d,) = ctx.saved_tensors
+        return d * go, None, None, None, None
 
 
 def _soft_target(logits, target) -> bool:
@@ -284,7 +323,7 @@ def _soft_target(logits, target) -> bool:
 
 
 def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoothing: float = 0.0,
-                  weight: torch.Tensor | None = None, ignore_index: int = -100):
+                  weight: torch.Tensor | None = None, ignore_index: int = -100, focal_gamma: float = 0.0):
     """Mean softmax cross-entropy.  `stats` (device fp32, >= 2) accumulates
     [sum of per-sample loss, #correct] without a host sync.  `label_smoothing` in [0, 1]:
     torch's smoothed targets eps / C + (1 - eps) * onehot (the loss, its gradient and the
@@ -303,20 +342,39 @@ def cross_entropy(logits, labels, stats: torch.Tensor | None = None, label_smoot
     torch: when nothing is kept, or every kept class has weight 0, the loss and its gradient are 0
     (torch: NaN, which would poison every weight of a replayed step); and on the GPU a label
     outside [0, C) that is not `ignore_index` counts as ignored (torch: a device assert).  With
-    `weight=None, ignore_index=-100` (the defaults) the call is the unweighted one, launch for launch."""
+    `weight=None, ignore_index=-100` (the defaults) the call is the unweighted one, launch for launch.
+
+    `focal_gamma` (finite, >= 0; integer labels only, no label smoothing: ValueError otherwise) turns the
+    loss into the focal loss of Lin et al. 2017 on the weighted path: with p = softmax(x_r)[y_r],
+    loss = sum_r k_r w[y_r] (1 - p)^gamma (-log p) / sum_r k_r w[y_r], everything else (`weight`,
+    `ignore_index`, the divisor, `stats`, the two departures) as above.  A row whose 1 - p underflows
+    contributes 0 and gets a zero gradient row.  0 (the default) is the call without it, launch for launch."""
     label_smoothing = float(label_smoothing)
     ignore_index = int(ignore_index)
+    focal_gamma = float(focal_gamma)
+    if not (focal_gamma >= 0.0 and math.isfinite(focal_gamma)):
+        raise ValueError(f"cross_entropy: focal_gamma must be finite and >= 0, got {focal_gamma}")
     if weight is not None and (weight.dim() != 1 or weight.shape[0] != logits.shape[-1]):
         raise ValueError(f"cross_entropy: weight must hold one value per class [{logits.shape[-1]}], got "
                          f"{tuple(weight.shape)}")
     if not 0.0 <= label_smoothing <= 1.0:
         raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
     soft = _soft_target(logits, labels)
+    if focal_gamma > 0.0 and (soft or label_smoothing > 0.0):
+        raise ValueError("cross_entropy: focal_gamma > 0 takes integer labels and label_smoothing == 0 (there is no "
+                         "agreed focal loss over class-probability targets or smoothed ones), got "
+                         + (f"a {tuple(labels.shape)} {labels.dtype} target" if soft
+                            else f"label_smoothing={label_smoothing}"))
     if _ext.use_native(logits):
+        if focal_gamma > 0.0:
+            return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing, weight, ignore_index, focal_gamma)
         return _SoftmaxXentNative.apply(logits, labels, stats, label_smoothing, weight, ignore_index)
     lf = logits.float()
     kept = None
-    if weight is None and (soft or ignore_index == -100):
+    if focal_gamma > 0.0:
+        loss, kept = _FocalFallback.apply(lf, labels, None if weight is None else weight.to(lf.device, lf.dtype),
+                                          ignore_index, focal_gamma)
+    elif weight is None and (soft or ignore_index == -100):
         loss = F.cross_entropy(lf, labels.float() if soft else labels, label_smoothing=label_smoothing)
     elif soft:
         loss = F.cross_entropy(lf, labels.float(), weight=weight.to(lf.device, lf.dtype),

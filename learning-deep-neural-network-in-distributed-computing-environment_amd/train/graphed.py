@@ -97,6 +97,15 @@ def check_label_smoothing(criterion, captured: float) -> None:
                            "was captured: capture again")
 
 
+def check_focal_gamma(criterion, captured: float) -> None:
+    """The focal criterion's ``gamma`` is a kernel argument of the captured loss launch too (0: the
+    criterion has none): a replay under another value would silently train with the captured one."""
+    now = float(getattr(criterion, "gamma", 0.0))
+    if now != captured:
+        raise RuntimeError(f"the criterion's gamma changed from {captured} to {now} since this step was captured: "
+                           "capture again")
+
+
 def class_weight_key(criterion, device=None):
     """What a capture bakes in of the criterion's class weights and ``ignore_index``: the weight
     buffer's address (None: no weights) and the index -- kernel arguments, like the label
@@ -189,6 +198,7 @@ class GraphedStep:
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
         self._class_weights = class_weight_key(criterion, x_example.device)   # (so are these)
+        self._focal_gamma = float(getattr(criterion, "gamma", 0.0))   # (and the focal loss's exponent)
         self.x, self._stage_x = static_input(model, x_example)
         self.y = y_example.detach().clone()
         self.stats = stats if stats is not None else torch.zeros(2, dtype=torch.float32, device=self.x.device)
@@ -262,6 +272,7 @@ class GraphedStep:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
         check_class_weights(self.criterion, self._class_weights)
+        check_focal_gamma(self.criterion, self._focal_gamma)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         self.graph.replay()
@@ -330,6 +341,7 @@ class GraphedDPStep:
         self.dp, self.model, self.criterion, self.optimizer = dp, dp.module, criterion, optimizer
         self._label_smoothing = float(getattr(criterion, "label_smoothing", 0.0))   # baked into the capture
         self._class_weights = class_weight_key(criterion, x_example.device)   # (so are these)
+        self._focal_gamma = float(getattr(criterion, "gamma", 0.0))   # (and the focal loss's exponent)
         self.bk, self.flat, self.comm = dp.bucketer, dp.flat, dp.comm
         self._SUM = SUM
         self.comm_fn = comm_fn
@@ -578,6 +590,7 @@ class GraphedDPStep:
             return self._eager_step(x, y)
         check_label_smoothing(self.criterion, self._label_smoothing)
         check_class_weights(self.criterion, self._class_weights)
+        check_focal_gamma(self.criterion, self._focal_gamma)
         self._stage_x(x, y, self.y)
         self._sync_lr()
         works = {}

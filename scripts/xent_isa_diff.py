@@ -6,8 +6,9 @@
 
 Pairs every plain xent kernel of old.s with the plain instance of new.s that has the same leading
 template arguments (the mode is a trailing `bool SMOOTH` in older trees, an `int MODE` -- 0 plain,
-1 smoothed, 2 soft targets -- since the soft-target instances; with a smoothed old.s the smoothed
-instances are paired too), and compares their instruction streams: comments dropped, the
+1 smoothed, 2 soft targets, 3 weighted labels, 4 weighted soft targets -- since the soft-target
+instances; the instances of modes 1 to 4 are paired too where old.s has them, any other mode of
+new.s, such as 5, focal, is ignored), and compares their instruction streams: comments dropped, the
 function number of local labels (.LBB<fn>_<n>) and the kernels' own symbol names normalised.
 Two scalar loads that differ only in their constant offset are counted apart: appended kernel
 arguments move the hidden ones (block / grid size) behind them in the kernel-argument segment.
@@ -71,14 +72,22 @@ def main():
     bad += compare(by_mode(old, (None, 0)), plain, smooth, soft, "SMOOTH=false")
     if by_mode(old, (1,)):
         bad += compare(by_mode(old, (1,)), smooth, {}, {}, "SMOOTH=true")
+    # the later modes, each against its own instance where old.s has it; a mode that is not in this
+    # table (5, focal, has no counterpart in a tree before it) is left out of the comparison
+    for mode, what in LATER_MODES.items():
+        if by_mode(old, (mode,)):
+            bad += compare(by_mode(old, (mode,)), by_mode(new, (mode,)), {}, {}, what)
     return 1 if bad else 0
+
+
+LATER_MODES = {2: "soft", 3: "weighted", 4: "weighted_soft"}
 
 
 def compare(olds, plain, smooth, soft, what):
     bad = 0
     for k in sorted(olds):
         a, b = olds[k], plain.get(k)
-        tag = "_".join(str(v) for v in k) + ("" if what == "SMOOTH=false" else "_smooth")
+        tag = "_".join(str(v) for v in k) + {"SMOOTH=false": "", "SMOOTH=true": "_smooth"}.get(what, "_" + what)
         if b is None:
             print(f"{tag}: missing from {sys.argv[2]}")
             bad += 1
