@@ -135,6 +135,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ema_no_warmup", action="store_true",
                    help="--ema_decay: use d from the first step on instead of d_t = min(d, (1 + c) / (10 + c)) after "
                         "c updates")
+    p.add_argument("--fedprox_mu", type=float, default=0.0, metavar="MU",
+                   help="FedProx (Li et al. 2020) against client drift between two aggregations: every rank "
+                        "minimises its loss + MU / 2 * |w - w_round|^2, w_round its weights at the start of the global "
+                        "epoch (behind the aggregation).  MU * (w - w_round) joins the gradient inside the fused "
+                        "optimizer update, where weight decay does (the clip norm of --clip_grad_norm does not see "
+                        "it); 0 = off.  For --partition skewed with several --epochs_local; not with --optimizer "
+                        "lars | lamb, autograd path only.  metrics.jsonl then logs prox_mu / prox_drift_norm "
+                        "(|w - w_round| before the aggregation) per global epoch")
     p.add_argument("--lr_schedule", type=str, default="none", choices=["none", "constant", "linear", "poly", "cosine"],
                    help="per-step learning-rate schedule inside the fused optimizer: a linear warm-up over "
                         "--warmup_steps, then constant, polynomial (linear: power 1) or cosine decay to "
@@ -278,6 +286,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "ema_decay", 0.0) > 0:
         # the static engine's wgrad-fused optimizer epilogue has no averaging pass behind it
         why = "--ema_decay runs on the autograd path"
+    elif getattr(args, "fedprox_mu", 0.0) > 0:
+        # ... and streams no anchor
+        why = "--fedprox_mu runs on the autograd path"
     elif getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0:
         # the static engine's head kernels take hard labels
         why = "--mixup / --cutmix runs on the autograd path"
@@ -357,6 +368,15 @@ def main(argv=None):
                                  "class-probability targets; drop one of the two")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema_decay must be in [0, 1), got {args.ema_decay}")
+    if not (args.fedprox_mu >= 0.0 and math.isfinite(args.fedprox_mu)):
+        raise SystemExit(f"--fedprox_mu must be finite and >= 0, got {args.fedprox_mu}")
+    if args.fedprox_mu > 0:
+        if args.optimizer in ("lars", "lamb"):
+            raise SystemExit(f"--fedprox_mu with --optimizer {args.optimizer}: the trust ratios are defined on "
+                             "g + weight_decay * w, there is no agreed form with a proximal term; use sgd, adam, "
+                             "adamw or lion")
+        if args.engine == "static":
+            raise SystemExit("--engine static: --fedprox_mu runs on the autograd path")
     if not 0.0 <= args.dropout < 1.0:
         raise SystemExit(f"--dropout must be in [0, 1), got {args.dropout}")
     for flag, v in (("--mixup", args.mixup), ("--cutmix", args.cutmix)):
@@ -489,6 +509,7 @@ def main(argv=None):
                                     max_grad_norm=args.clip_grad_norm if args.clip_grad_norm > 0 else None,
                                     ema_decay=args.ema_decay if args.ema_decay > 0 else None,
                                     ema_warmup=not args.ema_no_warmup, lr_schedule=lr_schedule,
+                                    prox_mu=args.fedprox_mu if args.fedprox_mu > 0 else None,
                                     **(dict(lars_trust=args.lars_trust, lars_eps=args.lars_eps,
                                             lars_exclude_1d=not args.lars_adapt_1d)
                                        if args.optimizer == "lars" else

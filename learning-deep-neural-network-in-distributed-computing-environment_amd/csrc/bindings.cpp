@@ -794,6 +794,25 @@ const float* hp_ptr(const char* fn, const at::Tensor& hp, const at::Tensor& like
   return hp.data_ptr<float>();
 }
 
+// prox = (anchor, hdr), the FedProx operands of an update (both nullptr without): the anchor fp32, on
+// the parameters' device, as long as `param` and aligned like it (the float4 body indexes both alike);
+// hdr fp32 there too, hdr[0] = mu
+using Prox = c10::optional<std::pair<at::Tensor, at::Tensor>>;
+std::pair<const float*, const float*> prox_ptrs(const char* fn, const Prox& prox, const at::Tensor& param) {
+  if (!prox.has_value()) return {nullptr, nullptr};
+  const at::Tensor &anchor = prox->first, &hdr = prox->second;
+  check_dev(anchor, at::kFloat, "prox anchor");
+  check_dev(hdr, at::kFloat, "prox hdr");
+  TORCH_CHECK(anchor.is_contiguous() && anchor.numel() == param.numel() && anchor.device() == param.device(), fn,
+              ": the prox anchor must be a contiguous fp32 buffer as long as param (", param.numel(),
+              " elements) on its device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(anchor.data_ptr()) & 15) == (reinterpret_cast<uintptr_t>(param.data_ptr()) & 15),
+              fn, ": the prox anchor must have param's 16-byte alignment");
+  TORCH_CHECK(hdr.is_contiguous() && hdr.numel() >= 1 && hdr.device() == param.device(), fn,
+              ": the prox hdr must hold [mu] on the parameters' device");
+  return {anchor.data_ptr<float>(), hdr.data_ptr<float>()};
+}
+
 // a dense int32 [rows][4] table; returns rows
 int64_t int4_table(const char* fn, const at::Tensor& t, const char* name, const char* rows) {
   check_dev(t, at::kInt, name);
@@ -925,9 +944,12 @@ void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor&
               const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double momentum,
               double dampening, double weight_decay, bool nesterov, bool first_step, const Ranges& zero_ranges,
               int64_t t_begin, const c10::optional<at::Tensor>& t_out, const c10::optional<at::Tensor>& clip,
-              const c10::optional<std::pair<at::Tensor, at::Tensor>>& lars) {
+              const c10::optional<std::pair<at::Tensor, at::Tensor>>& lars, const Prox& prox) {
   check_dev(hp, at::kFloat, "hp");
   const int64_t n = f32_bufs("sgd", {{param, "param"}, {grad, "grad"}}, false, false);
+  TORCH_CHECK(!prox.has_value() || (!lars.has_value() && !t_out.has_value()),
+              "sgd: prox= does not go with lars= (no agreed form) or t_out= (the transposed-shadow form has none)");
+  const auto px = prox_ptrs("sgd", prox, param);
   float* mp = nullptr;
   if (momentum != 0.0) {
     f32_bufs("sgd", {{param, "param"}, {mom, "mom"}}, false, false);
@@ -958,37 +980,41 @@ void sgd_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor&
   check(ldnn::sgd_step(param.data_ptr<float>(), grad.data_ptr<float>(), mp, sh, hp.data_ptr<float>(),
                        (float)grad_scale, sp, n, cur_stream(param), t_out.has_value() ? &tr : nullptr,
                        clip_ptr(clip, param), lars.has_value() ? lars->first.data_ptr<float>() : nullptr,
-                       lars.has_value() ? lars->second.data_ptr<uint16_t>() : nullptr),
+                       lars.has_value() ? lars->second.data_ptr<uint16_t>() : nullptr, px.first, px.second),
         "sgd_step");
 }
 
 void adam_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double beta1,
                double beta2, double eps, double weight_decay, bool decoupled, const Ranges& zero_ranges,
-               const c10::optional<at::Tensor>& clip) {
+               const c10::optional<at::Tensor>& clip, const Prox& prox) {
   check_dev(hp, at::kFloat, "hp");
   const int64_t n =
       f32_bufs("adam", {{param, "param"}, {grad, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}}, false, false);
+  const auto px = prox_ptrs("adam", prox, param);
   uint16_t* sh = shadow_ptr("adam", shadow, param, false);
   ldnn::AdamParams ap{(float)beta1, (float)beta2, (float)eps, (float)weight_decay, decoupled ? 1 : 0,
                       grad_zero(zero_ranges, n)};
   check(ldnn::adam_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                        sh, hp.data_ptr<float>(), (float)grad_scale, ap, n, cur_stream(param), clip_ptr(clip, param)),
+                        sh, hp.data_ptr<float>(), (float)grad_scale, ap, n, cur_stream(param), clip_ptr(clip, param),
+                        px.first, px.second),
         "adam_step");
 }
 
 // (every check comes before the launch: a refused call leaves the buffers untouched)
 void lion_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& m,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& hp, double grad_scale, double beta1,
-               double beta2, double weight_decay, const Ranges& zero_ranges, const c10::optional<at::Tensor>& clip) {
+               double beta2, double weight_decay, const Ranges& zero_ranges, const c10::optional<at::Tensor>& clip,
+               const Prox& prox) {
   const int64_t n = f32_bufs("lion", {{param, "param"}, {grad, "grad"}, {m, "exp_avg"}}, true, true);
+  const auto px = prox_ptrs("lion", prox, param);
   const float* hpp = hp_ptr("lion", hp, param);
   uint16_t* sh = shadow_ptr("lion", shadow, param, true);
   const float* cp = clip_ptr(clip, param);
   ldnn::LionParams lp{(float)beta1, (float)beta2, (float)weight_decay, grad_zero(zero_ranges, n)};
   c10::hip::HIPGuardMasqueradingAsCUDA g(param.device());
   check(ldnn::lion_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), sh, hpp,
-                        (float)grad_scale, lp, n, cur_stream(param), cp),
+                        (float)grad_scale, lp, n, cur_stream(param), cp, px.first, px.second),
         "lion_step");
 }
 
@@ -2564,7 +2590,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("hp"), py::arg("grad_scale"), py::arg("momentum"), py::arg("dampening"),
         py::arg("weight_decay"), py::arg("nesterov"), py::arg("first_step"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("t_begin") = 0,
-        py::arg("t_out") = py::none(), py::arg("clip") = py::none(), py::arg("lars") = py::none());
+        py::arg("t_out") = py::none(), py::arg("clip") = py::none(), py::arg("lars") = py::none(),
+        py::arg("prox") = py::none());
   m.def("seg_sumsq", &seg_sumsq, "per-chunk sums of squares of master and grad (partials[2c], partials[2c + 1]) over a "
         "device chunk table cut from 64-aligned `ranges` of segments at `seg_offsets`; returns the chunk count",
         py::arg("master"), py::arg("grad"), py::arg("chunks"), py::arg("partials"), py::arg("ranges"),
@@ -2592,12 +2619,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("adam_step", &adam_step, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"),
-        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
+        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none(),
+        py::arg("prox") = py::none());
   m.def("lion_step", &lion_step, "Lion: w = w (1 - lr wd) - lr sign(beta1 m + (1 - beta1) g), m = beta2 m + "
         "(1 - beta2) g (+ bf16 shadow, gradient zero ranges); lr = hp[0]", py::arg("param"), py::arg("grad"),
         py::arg("exp_avg"), py::arg("shadow"), py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"),
         py::arg("beta2"), py::arg("weight_decay"),
-        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none());
+        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none(),
+        py::arg("prox") = py::none());
   m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
   m.def("lr_sched", &lr_sched, "learning-rate schedule, once per step: hp[0] = base * s(t + 1), the factor and the "
         "step count into hdr (nothing on a skipped step)", py::arg("hdr"), py::arg("hp"), py::arg("clip") = py::none());

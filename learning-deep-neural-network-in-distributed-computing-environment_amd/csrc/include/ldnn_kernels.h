@@ -503,17 +503,25 @@ struct ShadowT {
 // lars_ratio / lars_map (optional, both or neither): the LARS trust ratios trust_finalize wrote and,
 // per 64-element block of THIS range, the index of its ratio (alignment gaps point at a slot that
 // holds 1).  The update becomes ratio * (g + weight_decay * p); together with `tr` it is refused.
+// prox_anchor / prox_hdr (optional, both or neither; sgd_step, adam_step, lion_step): FedProx.  The
+// anchor is n fp32 elements laid out like `param` (the weights the round started from), prox_hdr[0] = mu
+// is WRITTEN BY THE HOST like hp[0] = lr.  mu * (p0 - anchor), p0 the weight as loaded, is added to
+// the scaled and clipped gradient where weight decay is added (behind it; AdamW and Lion: to g, the
+// decay stays decoupled), so it enters the momentum / the moments.  The clip norm does not see it; a
+// skipped step touches nothing.  sgd_step refuses it together with lars_* or `tr`.
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
                     float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr = nullptr,
                     const float* clip = nullptr, const float* lars_ratio = nullptr,
-                    const uint16_t* lars_map = nullptr);
+                    const uint16_t* lars_map = nullptr, const float* prox_anchor = nullptr,
+                    const float* prox_hdr = nullptr);
 struct AdamParams {
   float beta1, beta2, eps, weight_decay;
   int decoupled;  // AdamW
   GradZero zero;
 };
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
-                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip = nullptr);
+                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip = nullptr,
+                     const float* prox_anchor = nullptr, const float* prox_hdr = nullptr);
 // Lion: c = beta1 m + (1 - beta1) g, w = w (1 - lr weight_decay) - lr sign(c), m = beta2 m + (1 - beta2) g.
 // hp[0] = lr; hp[1] is not read (no bias correction, no bump_step).  clip / zero as in adam_step.
 struct LionParams {
@@ -521,7 +529,8 @@ struct LionParams {
   GradZero zero;
 };
 hipError_t lion_step(float* param, float* grad, float* m, uint16_t* shadow, const float* hp, float grad_scale,
-                     LionParams lp, int64_t n, hipStream_t s, const float* clip = nullptr);
+                     LionParams lp, int64_t n, hipStream_t s, const float* clip = nullptr,
+                     const float* prox_anchor = nullptr, const float* prox_hdr = nullptr);
 // hp[1] += 1 (graph-capturable step counter); with clip: not on a skipped step
 hipError_t bump_step(float* hp, hipStream_t s, const float* clip = nullptr);
 

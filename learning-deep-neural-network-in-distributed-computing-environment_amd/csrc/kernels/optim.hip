@@ -76,6 +76,22 @@ struct LarsArg {
 template <>
 struct LarsArg<false> {};
 
+// PROX: the kernel also takes the FedProx anchor (the weights the round started from, fp32, laid out
+// like the range's master) and a header whose first element is mu: mu * (p0 - anchor) joins the
+// gradient where weight decay does, p0 the weight as loaded.  mu is read on the device, so a captured
+// step follows a changed mu as it follows the lr.  The PROX = false instances carry an empty
+// argument and compile to the code without it.
+template <bool PROX>
+struct ProxArg {
+  static constexpr bool on = PROX;
+  const float* anchor;
+  const float* hdr;
+};
+template <>
+struct ProxArg<false> {
+  static constexpr bool on = false;
+};
+
 // a skipped (non-finite norm) step: only the requested gradient zero ranges are cleared
 __device__ __forceinline__ void clear_only(const GradZero& z, float* grad, int64_t n) {
   if (z.ze[0] <= z.zb[0] && z.ze[1] <= z.zb[1]) return;
@@ -90,14 +106,15 @@ __device__ __forceinline__ void clear_only(const GradZero& z, float* grad, int64
 // one float4 of the SGD(-momentum) update: master, momentum, gradient clear; returns the
 // new bf16 shadow values.  LARS: (g + weight_decay * p) is scaled by the trust ratio of the
 // 64-element block the float4 lies in (segments start on 64-element boundaries).
-template <bool NT, bool LARS>
+template <bool NT, bool LARS, bool PROX>
 __device__ __forceinline__ u16x4 sgd4(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mom,
                                       float lr, float grad_scale, const SgdParams& sp, int64_t i,
-                                      const LarsArg<LARS>& lars) {
+                                      const LarsArg<LARS>& lars, const ProxArg<PROX>& prox, float mu) {
   floatx4 p = ld4<NT>(param, i);
   floatx4 g = ld4<NT>(grad, i) * grad_scale;
   clear4(sp.zero, grad, i);
   if (sp.weight_decay != 0.f) g += sp.weight_decay * p;
+  if constexpr (PROX) g += mu * (p - ld4<NT>(prox.anchor, i));
   if constexpr (LARS) g *= lars.ratio[lars.map[i >> 4]];
   if (sp.momentum != 0.f) {
     floatx4 b;
@@ -117,11 +134,13 @@ __device__ __forceinline__ u16x4 sgd4(float* __restrict__ param, float* __restri
 // that matrix one 64 x 64 tile each and write the transposed tile through LDS; the rest
 // stride over the remaining elements -- one launch instead of the update plus a
 // transpose pass that re-reads the 32 MB shadow.
-template <bool NT, bool TR, bool CLIP, bool LARS>
+template <bool NT, bool TR, bool CLIP, bool LARS, bool PROX>
 __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mom,
                            bf16_t* __restrict__ shadow, const float* __restrict__ hp, float grad_scale,
-                           SgdParams sp, int64_t n, ShadowT tr, ClipArg<CLIP> clip, LarsArg<LARS> lars) {
+                           SgdParams sp, int64_t n, ShadowT tr, ClipArg<CLIP> clip, LarsArg<LARS> lars,
+                           ProxArg<PROX> prox) {
   static_assert(!(TR && LARS), "the transposed-shadow form has no LARS instance");
+  static_assert(!(PROX && (TR || LARS)), "the proximal term has no transposed-shadow and no LARS instance");
   if constexpr (CLIP) {
     if (clip.st[kClipSkip] != 0.f) {
       clear_only(sp.zero, grad, n);
@@ -130,6 +149,8 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
     grad_scale *= clip.st[kClipCoef];
   }
   const float lr = hp[0];
+  float mu = 0.f;
+  if constexpr (PROX) mu = prox.hdr[0];
   const int64_t nv = n / 4;
   int64_t bid = blockIdx.x, nblk = gridDim.x, skip_b = 0, skip_n = 0;
   if constexpr (TR) {
@@ -143,7 +164,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
       for (int k = 0; k < 4; ++k) {
         const int r = rg * 4 + k;
         const int64_t i = (tr.begin + (int64_t)(r0 + r) * tr.cols + c0 + c4 * 4) >> 2;
-        const u16x4 b = sgd4<NT, LARS>(param, grad, mom, lr, grad_scale, sp, i, lars);
+        const u16x4 b = sgd4<NT, LARS, PROX>(param, grad, mom, lr, grad_scale, sp, i, lars, prox, mu);
         if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = b;
 #pragma unroll
         for (int q = 0; q < 4; ++q) t[r][c4 * 4 + q] = b[q];
@@ -168,7 +189,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
   const int64_t stride = nblk * blockDim.x;
   for (int64_t j = bid * (int64_t)blockDim.x + threadIdx.x; j < nv - skip_n; j += stride) {
     const int64_t i = (TR && j >= skip_b) ? j + skip_n : j;
-    const u16x4 b = sgd4<NT, LARS>(param, grad, mom, lr, grad_scale, sp, i, lars);
+    const u16x4 b = sgd4<NT, LARS, PROX>(param, grad, mom, lr, grad_scale, sp, i, lars, prox, mu);
     if (shadow) reinterpret_cast<u16x4*>(shadow)[i] = b;
   }
   for (int64_t i = nv * 4 + bid * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -176,6 +197,7 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
     float g = grad[i] * grad_scale;
     if (in_zero(sp.zero, i)) grad[i] = 0.f;
     if (sp.weight_decay != 0.f) g += sp.weight_decay * p;
+    if constexpr (PROX) g += mu * (p - prox.anchor[i]);
     if constexpr (LARS) g *= lars.ratio[lars.map[i >> 6]];
     if (sp.momentum != 0.f) {
       const float b = sp.first_step ? g : sp.momentum * mom[i] + (1.f - sp.dampening) * g;
@@ -188,22 +210,25 @@ __global__ void sgd_kernel(float* __restrict__ param, float* __restrict__ grad, 
   }
 }
 
+// PROX: px = mu * (p0 - anchor), added behind the coupled weight decay
+template <bool PROX>
 __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, float lr, float bc1,
-                                           float bc2s, const AdamParams& ap) {
+                                           float bc2s, const AdamParams& ap, float px) {
   if (ap.weight_decay != 0.f) {
     if (ap.decoupled) p *= (1.f - lr * ap.weight_decay);
     else g += ap.weight_decay * p;
   }
+  if constexpr (PROX) g += px;
   m = ap.beta1 * m + (1.f - ap.beta1) * g;
   v = ap.beta2 * v + (1.f - ap.beta2) * g * g;
   const float denom = sqrtf(v) / bc2s + ap.eps;
   return p - (lr / bc1) * m / denom;
 }
 
-template <bool NT, bool CLIP>
+template <bool NT, bool CLIP, bool PROX>
 __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mm,
                             float* __restrict__ vv, bf16_t* __restrict__ shadow, const float* __restrict__ hp,
-                            float grad_scale, AdamParams ap, int64_t n, ClipArg<CLIP> clip) {
+                            float grad_scale, AdamParams ap, int64_t n, ClipArg<CLIP> clip, ProxArg<PROX> prox) {
   if constexpr (CLIP) {
     if (clip.st[kClipSkip] != 0.f) {
       clear_only(ap.zero, grad, n);
@@ -213,6 +238,8 @@ __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
   }
   const float lr = hp[0];
   const float t = hp[1];
+  float mu = 0.f;
+  if constexpr (PROX) mu = prox.hdr[0];
   const float bc1 = 1.f - powf(ap.beta1, t);
   const float bc2s = sqrtf(1.f - powf(ap.beta2, t));
   const int64_t nv = n / 4;
@@ -223,10 +250,12 @@ __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
     clear4(ap.zero, grad, i);
     floatx4 m = ld4<NT>(mm, i);
     floatx4 v = ld4<NT>(vv, i);
+    floatx4 px = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (PROX) px = mu * (p - ld4<NT>(prox.anchor, i));
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float mj = m[j], vj = v[j];
-      p[j] = adam_elem(p[j], g[j], mj, vj, lr, bc1, bc2s, ap);
+      p[j] = adam_elem<PROX>(p[j], g[j], mj, vj, lr, bc1, bc2s, ap, px[j]);
       m[j] = mj;
       v[j] = vj;
     }
@@ -237,7 +266,10 @@ __global__ void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
   }
   for (int64_t i = nv * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
     float m = mm[i], v = vv[i];
-    const float p = adam_elem(param[i], grad[i] * grad_scale, m, v, lr, bc1, bc2s, ap);
+    const float p0 = param[i];
+    float px = 0.f;
+    if constexpr (PROX) px = mu * (p0 - prox.anchor[i]);
+    const float p = adam_elem<PROX>(p0, grad[i] * grad_scale, m, v, lr, bc1, bc2s, ap, px);
     if (in_zero(ap.zero, i)) grad[i] = 0.f;
     param[i] = p;
     mm[i] = m;
@@ -258,10 +290,10 @@ __device__ __forceinline__ float lion_elem(float p, float g, float& m, float lr,
   return p - lr * s;
 }
 
-template <bool NT, bool CLIP>
+template <bool NT, bool CLIP, bool PROX>
 __global__ void lion_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ mm,
                             bf16_t* __restrict__ shadow, const float* __restrict__ hp, float grad_scale,
-                            LionParams lp, int64_t n, ClipArg<CLIP> clip) {
+                            LionParams lp, int64_t n, ClipArg<CLIP> clip, ProxArg<PROX> prox) {
   if constexpr (CLIP) {
     if (clip.st[kClipSkip] != 0.f) {
       clear_only(lp.zero, grad, n);
@@ -270,13 +302,16 @@ __global__ void lion_kernel(float* __restrict__ param, float* __restrict__ grad,
     grad_scale *= clip.st[kClipCoef];
   }
   const float lr = hp[0];
+  float mu = 0.f;
+  if constexpr (PROX) mu = prox.hdr[0];
   const int64_t nv = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += stride) {
     floatx4 p = ld4<NT>(param, i);
-    const floatx4 g = ld4<NT>(grad, i) * grad_scale;
+    floatx4 g = ld4<NT>(grad, i) * grad_scale;
     clear4(lp.zero, grad, i);
     floatx4 m = ld4<NT>(mm, i);
+    if constexpr (PROX) g += mu * (p - ld4<NT>(prox.anchor, i));
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float mj = m[j];
@@ -289,7 +324,10 @@ __global__ void lion_kernel(float* __restrict__ param, float* __restrict__ grad,
   }
   for (int64_t i = nv * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
     float m = mm[i];
-    const float p = lion_elem(param[i], grad[i] * grad_scale, m, lr, lp);
+    const float p0 = param[i];
+    float g = grad[i] * grad_scale;
+    if constexpr (PROX) g += mu * (p0 - prox.anchor[i]);
+    const float p = lion_elem(p0, g, m, lr, lp);
     if (in_zero(lp.zero, i)) grad[i] = 0.f;
     param[i] = p;
     mm[i] = m;
@@ -699,13 +737,20 @@ void with_clip(const float* clip, Launch launch) {
   else launch(ClipArg<false>{});
 }
 
-template <bool TR, bool LARS>
+// launch(ProxArg<..>): the PROX instance when an anchor is given, else the one without the term
+template <class Launch>
+void with_prox(const float* anchor, const float* hdr, Launch launch) {
+  if (anchor != nullptr) launch(ProxArg<true>{anchor, hdr});
+  else launch(ProxArg<false>{});
+}
+
+template <bool TR, bool LARS, bool PROX = false>
 void launch_sgd(int grid, float* param, float* grad, float* mom, uint16_t* shadow, const float* hp, float grad_scale,
                 const SgdParams& sp, int64_t n, hipStream_t s, const ShadowT& tr, const float* clip,
-                LarsArg<LARS> la) {
+                LarsArg<LARS> la, ProxArg<PROX> pa = {}) {
   with_clip(clip, [&](auto ca) {
-    sgd_kernel<true, TR, ca.on, LARS><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, tr, ca,
-                                                              la);
+    sgd_kernel<true, TR, ca.on, LARS, PROX><<<grid, kBlock, 0, s>>>(param, grad, mom, shadow, hp, grad_scale, sp, n, tr,
+                                                                    ca, la, pa);
   });
 }
 
@@ -715,10 +760,15 @@ void set_opt_max_blocks(int n) { g_opt_max_blocks = n > 0 ? n : 2048; }
 
 hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, const float* hp,
                     float grad_scale, SgdParams sp, int64_t n, hipStream_t s, const ShadowT* tr, const float* clip,
-                    const float* lars_ratio, const uint16_t* lars_map) {
+                    const float* lars_ratio, const uint16_t* lars_map, const float* prox_anchor,
+                    const float* prox_hdr) {
   if (n <= 0) return hipSuccess;
   const bool lars = lars_ratio != nullptr;
   if (lars != (lars_map != nullptr)) return hipErrorInvalidValue;
+  const bool prox = prox_anchor != nullptr;
+  if (prox != (prox_hdr != nullptr)) return hipErrorInvalidValue;
+  // (no agreed LARS form with a proximal term; only the static engine transposes, and it has neither)
+  if (prox && (lars || (tr != nullptr && tr->out != nullptr))) return hipErrorInvalidValue;
   if (tr != nullptr && tr->out != nullptr) {
     if (lars) return hipErrorInvalidValue;  // (only the static engine transposes; it has no LARS)
     // (the tile path needs whole 64 x 64 tiles and 16-B aligned transposed rows)
@@ -735,26 +785,38 @@ hipError_t sgd_step(float* param, float* grad, float* mom, uint16_t* shadow, con
   if (lars)
     launch_sgd<false, true>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, ShadowT{}, clip,
                             {lars_ratio, lars_map});
+  else if (prox)
+    launch_sgd<false, false, true>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, ShadowT{}, clip, {},
+                                   {prox_anchor, prox_hdr});
   else
     launch_sgd<false, false>(grid, param, grad, mom, shadow, hp, grad_scale, sp, n, s, ShadowT{}, clip, {});
   return hipGetLastError();
 }
 
 hipError_t adam_step(float* param, float* grad, float* m, float* v, uint16_t* shadow, const float* hp,
-                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip) {
+                     float grad_scale, AdamParams ap, int64_t n, hipStream_t s, const float* clip,
+                     const float* prox_anchor, const float* prox_hdr) {
   if (n <= 0) return hipSuccess;
+  if ((prox_anchor != nullptr) != (prox_hdr != nullptr)) return hipErrorInvalidValue;
   with_clip(clip, [&](auto ca) {
-    adam_kernel<true, ca.on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, v, shadow, hp, grad_scale, ap, n,
-                                                                      ca);
+    with_prox(prox_anchor, prox_hdr, [&](auto pa) {
+      adam_kernel<true, decltype(ca)::on, decltype(pa)::on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(
+          param, grad, m, v, shadow, hp, grad_scale, ap, n, ca, pa);
+    });
   });
   return hipGetLastError();
 }
 
 hipError_t lion_step(float* param, float* grad, float* m, uint16_t* shadow, const float* hp, float grad_scale,
-                     LionParams lp, int64_t n, hipStream_t s, const float* clip) {
+                     LionParams lp, int64_t n, hipStream_t s, const float* clip, const float* prox_anchor,
+                     const float* prox_hdr) {
   if (n <= 0) return hipSuccess;
+  if ((prox_anchor != nullptr) != (prox_hdr != nullptr)) return hipErrorInvalidValue;
   with_clip(clip, [&](auto ca) {
-    lion_kernel<true, ca.on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(param, grad, m, shadow, hp, grad_scale, lp, n, ca);
+    with_prox(prox_anchor, prox_hdr, [&](auto pa) {
+      lion_kernel<true, decltype(ca)::on, decltype(pa)::on><<<grid_for((n + 3) / 4), kBlock, 0, s>>>(
+          param, grad, m, shadow, hp, grad_scale, lp, n, ca, pa);
+    });
   });
   return hipGetLastError();
 }

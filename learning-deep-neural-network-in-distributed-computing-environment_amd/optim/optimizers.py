@@ -90,6 +90,31 @@ it starts at 0), ``lr_schedule_stats()`` reports count, factor and rate.  The co
 scalar (exact to 2**24; longer horizons are refused).  A graph captured with the schedule off never
 schedules until it is captured again; one captured with it on keeps its ``lr_sched`` (with the last
 constants written, still following the base) after ``lr_schedule`` is set to None.
+
+``prox_mu`` (default None = off, as is 0; SGD, Adam, AdamW and Lion, ``build_optimizer(prox_mu=)``) is FedProx
+(Li et al., MLSys 2020): each rank minimises ``F_k(w) + mu / 2 * |w - a|^2`` with the anchor ``a`` the
+weights its round started from, so ``mu * (p0 - a)`` -- ``p0`` the weight as loaded, before any decoupled
+decay -- is added to the reduced, scaled and clipped gradient where weight decay is added (behind it):
+SGD ``g += wd p0; g += mu (p0 - a)``, then the momentum chain; Adam the same before both moments; AdamW
+and Lion add it to ``g`` and keep their decay decoupled.  The anchor is ``_ls()["prox_anchor"]``, a flat
+fp32 buffer shaped like the master (loose tensors: ``state[p]["prox_anchor"]``); ``set_prox_anchor()``
+copies the master into it in place (``train_global`` does at the start of every global epoch, behind the
+aggregation), and without a call the first eager step with ``prox_mu > 0`` anchors at the master before
+its update.  ``mu`` lives in a small device header (``prox_hdr``) the host writes like the lr, and the
+anchor is one more streamed operand of the fused update (``sgd_step`` / ``adam_step`` / ``lion_step``
+``prox=``, 4 B per element), cut by the same range as the master: the eager, range, sharded and graphed
+steps all apply the term, a captured step follows ``sync_hyperparams()`` and ``set_prox_anchor()`` (a
+device copy into the same address, outside the graph), and no collective is added.  Clipping: the global
+norm is taken of the loss gradient alone -- the term is a regulariser the optimizer adds, treated
+exactly as L2 weight decay is, so the norm, the coefficient and the non-finite guard do not see it, and
+a skipped step changes no master, moment, shadow or anchor.  This departs from "penalty in the loss +
+``clip_grad_norm_``", where the penalty's gradient is clipped with the rest.  LARS and LAMB refuse
+``prox_mu > 0`` (their ratios are defined on ``g + wd w``; there is no agreed form with a proximal term).
+Neither anchor nor header is saved (``state_dict()`` keys are unchanged): checkpoints are written at the
+end of a global epoch, behind the aggregation, and the next one re-anchors.  ``prox_stats()`` reports
+``mu`` and ``|w - a|_2``.  A graph captured with ``prox_mu`` off never applies the term until it is
+captured again; one captured with it on runs with ``mu = 0`` after ``prox_mu`` is set to None or 0; a
+capture with ``prox_mu > 0`` and no anchor yet asks for an eager step first.
 """
 from __future__ import annotations
 
@@ -119,7 +144,9 @@ def _refuse_partial_sharded(params):
 _CLIP_MAX, _CLIP_COEF, _CLIP_SKIP, _CLIP_NORM, _CLIP_STEPS, _CLIP_CLIPPED, _CLIP_SKIPPED, _CLIP_LEN = 0, 1, 2, 3, 4, 5, 6, 8
 # device-only entries of _ls(): rebuilt by an eager step, never saved
 _TRANSIENT = ("hp", "clip", "clip_scratch", "clip_local", "lars", "lamb", "ema_hdr", "sched_hdr", "sched_written",
-              "sched_last")
+              "sched_last", "prox_anchor", "prox_hdr")
+# the FedProx header: [mu, -, -, -]
+_PROX_MU, _PROX_LEN = 0, 4
 # slots of the weight EMA's header (csrc/include/ldnn_kernels.h EmaSlot)
 _EMA_DECAY, _EMA_WARMUP, _EMA_UPDATES, _EMA_ALPHA, _EMA_LEN = 0, 1, 2, 3, 4
 # slots of the learning-rate schedule's header (csrc/include/ldnn_kernels.h SchedSlot): the first six
@@ -132,7 +159,8 @@ _SCHED_KEYS = ("kind", "total_steps", "warmup_steps", "warmup_start", "min_ratio
 _LARS_SLOTS, _LARS_GAP = 65536, 65535
 _CAPTURE_MSG = "run an eager optimizer step before capturing it into a graph"
 # lengths of the fp32 device vectors of _ls() (clip_scratch: as many slots as the ranges need)
-_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1, "ema_hdr": _EMA_LEN, "sched_hdr": _SCHED_LEN}
+_STATE_LEN = {"hp": 2, "clip": _CLIP_LEN, "clip_local": 1, "ema_hdr": _EMA_LEN, "sched_hdr": _SCHED_LEN,
+              "prox_hdr": _PROX_LEN}
 
 
 def _graph_state(store: dict, key, capturing: bool, make):
@@ -326,6 +354,16 @@ def _ema_update_torch(e, w, hdr):
     e.add_((w - e).mul_(hdr[_EMA_ALPHA].to(e.device)))
 
 
+def check_prox_mu(mu):
+    """``prox_mu`` as the optimizers take it: None (off) or a finite real number >= 0 (0: off too);
+    anything else is a ValueError.  Returns None when off, else the float."""
+    if mu is None:
+        return None
+    if isinstance(mu, bool) or not isinstance(mu, numbers.Real) or not 0.0 <= float(mu) < float("inf"):
+        raise ValueError(f"prox_mu must be None (off) or a finite number >= 0; got {mu!r}")
+    return float(mu) or None
+
+
 def _whole(what, v):
     """``v`` as an int when it is a whole, finite number (no bool, no string); else a ValueError."""
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or v in (float("inf"), -float("inf")) \
@@ -433,6 +471,9 @@ class _FlatStep:
     becomes ``group["lr"] * s`` in Python floats.  ``sched``: the factor of a schedule stepped
     outside (several groups / loose tensors), already in ``lr``.
 
+    FedProx (``prox``: ``(anchor, header)``; ``prox_mu``: the host's value for the torch paths) adds no
+    stage: ``update(lo, hi)`` hands the optimizer's launch the anchor cut like the master.
+
     The stages hand their results on in the object, so the order is a precondition: when the
     step takes a norm (``normed``: its own clipping, or LARS), ``norm`` comes before ``finalize``;
     ``finalize`` comes before any ``update``.  With neither, ``norm`` may be left out."""
@@ -440,7 +481,7 @@ class _FlatStep:
     # what a plain step (no clipping, no LARS) never sets
     own_clip = normed = False
     cl = skip = L = M = hp = local = local2 = tab = mtab = sumsq = ctx = ema = ema_hdr = None
-    sched_hdr = sched_host = None
+    sched_hdr = sched_host = prox = prox_mu = None
     ranges, counted, nparts = (), (), 0
 
     def __init__(self, opt, f, group, clip=None, sharded=False, sched=None):
@@ -458,6 +499,9 @@ class _FlatStep:
             self.local2 = self.M.local if sharded else None
         if opt._ema_conf() is not None:
             self.ema, self.ema_hdr = opt._ema_state(f)
+        self.prox_mu = opt._prox_conf()
+        if self.prox_mu is not None:
+            self.prox = opt._prox_state(f)
         if native:
             hp = st.get("hp")
             self.hp = hp if hp is not None and hp.device == dev else opt._state("hp", dev)
@@ -483,6 +527,15 @@ class _FlatStep:
         self.normed = self.own_clip or self.L is not None
         if sharded and self.normed:
             self.local = self.L.local if self.L is not None else opt._state("clip_local", dev)
+
+    def prox_arg(self, sl):
+        """``prox=`` of a native update over the flat slice ``sl``: the anchor cut like the master."""
+        return None if self.prox is None else (_cut(sl, self.prox[0])[0], self.prox[1])
+
+    def prox_term(self, sl, p):
+        """The torch paths' ``mu * (p0 - a)`` over the flat slice ``sl`` (None when off); ``p``: the
+        master's slice, before the update touches it."""
+        return None if self.prox is None else (p - _cut(sl, self.prox[0])[0]).mul_(self.prox_mu)
 
     def _seg_sums(self):
         L, f = self.L, self.f
@@ -670,6 +723,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._sched_conf()    # (a schedule given per param group: checked, and the same in all)
+        self._prox_conf()     # (prox_mu likewise)
 
     def _ls(self) -> dict:
         """Fused (flat-buffer) optimizer state: momentum / moments / step / hp (+ the
@@ -691,6 +745,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
             # ... and the schedule's count of non-skipped steps (the host paths keep it in ``ls``)
             flat["sched_steps"] = int(ls["sched_hdr"][_SCHED_STEPS].item())
         sd["ldnn_flat_state"] = flat
+        if any("prox_anchor" in v for v in sd["state"].values()):
+            # (loose tensors: the anchors are not saved either; the dicts are the live ones, so copy)
+            sd["state"] = {k: {n: t for n, t in v.items() if n != "prox_anchor"} for k, v in sd["state"].items()}
         return sd
 
     # ---- device state an eager step allocates and a captured graph reads ---------------
@@ -702,7 +759,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         step count], ``clip`` [max_norm, coef, skip, last_norm, steps, clipped, skipped, -],
         ``clip_scratch`` (grad_sumsq's partial slots), ``clip_local`` (the 1-element local sum),
         ``ema_hdr`` [decay, warm-up flag, EMA updates, last a_t], ``sched_hdr`` [kind, W, ws, T, m,
-        q, base, steps, last factor]."""
+        q, base, steps, last factor], ``prox_hdr`` [mu, -, -, -]."""
         st = self._ls()
         t = st.get(key)
         n = n or _STATE_LEN[key]
@@ -746,8 +803,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 "adapted": list(T.adapt)}
 
     def _write_hyperparams(self, lr=None, conf=None):
-        """Write the learning rate, the clipping threshold, LARS's trust coefficient and eps and the
-        EMA's decay and warm-up flag into whichever of their device tensors exist; with a schedule's
+        """Write the learning rate, the clipping threshold, LARS's trust coefficient and eps, the
+        EMA's decay and warm-up flag and FedProx's mu into whichever of their device tensors exist; with a schedule's
         header the rate goes there as the base (``lr_sched`` writes ``hp[0]``).  ``conf``:
         ``(_clip_threshold(), _lars_conf())`` where the caller has them already."""
         st = self._ls()
@@ -773,6 +830,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
             if ema is not None:    # (switched off after a capture: the captured kernels keep the last decay)
                 eh[_EMA_DECAY].fill_(ema[0])
                 eh[_EMA_WARMUP].fill_(float(ema[1]))
+        ph = st.get("prox_hdr")
+        if ph is not None:
+            # (switched off after a capture: the captured kernels run with mu = 0, the term vanishes)
+            ph[_PROX_MU].fill_(self._prox_conf() or 0.0)
         if cl is None and L is None:
             return
         mx, lars = conf if conf is not None else (self._clip_threshold(), self._lars_conf())
@@ -787,7 +848,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def sync_hyperparams(self):
         """Write the current learning rate (and clipping threshold, LARS trust coefficient and
-        eps, EMA decay and warm-up flag, the schedule's constants and base rate) into the device
+        eps, EMA decay and warm-up flag, the schedule's constants and base rate, FedProx's mu) into the device
         hyper-parameter tensors."""
         self._write_hyperparams()
 
@@ -926,12 +987,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _ema_flat(self):
         """The one flat buffer the EMA covers (None: loose tensors); anything between is refused."""
-        flats = [self._flat_for_group(g) for g in self.param_groups]
-        if all(f is None for f in flats):
-            return None
-        if len(flats) != 1:
-            raise ValueError("ema_decay needs ONE param group holding one flat buffer, or loose tensors only")
-        return flats[0]
+        return self._one_flat("ema_decay")
 
     def _loose_ema_begin(self):
         """Loose tensors, before the step's updates: every parameter's average (created as a copy of
@@ -1008,6 +1064,92 @@ class _FlatOptimizer(torch.optim.Optimizer):
         finally:
             self._ldnn_in_ema = False
             swap()
+
+    # ---- FedProx: the proximal term toward the round's start weights ----------------------
+    _prox_ok = True    # (Lamb: False)
+
+    def _prox_conf(self):
+        """``mu`` > 0, or None when the term is off.  One value for the whole optimizer; the key is
+        read with .get, so state saved before it existed loads.  LARS and LAMB refuse it."""
+        mu = self._same_in_groups(lambda g: check_prox_mu(g.get("prox_mu")),
+                                  "prox_mu must be the same in every param group")
+        if mu is not None and (not self._prox_ok or self._lars_conf() is not None):
+            raise ValueError("prox_mu: LARS and LAMB take no proximal term (their trust ratios are defined on "
+                             "g + weight_decay * w; there is no agreed form with one)")
+        return mu
+
+    def _one_flat(self, what):
+        """The one flat buffer ``what`` covers (None: loose tensors); anything between is refused."""
+        flats = [self._flat_for_group(g) for g in self.param_groups]
+        if all(f is None for f in flats):
+            return None
+        if len(flats) != 1:
+            raise ValueError(f"{what} needs ONE param group holding one flat buffer, or loose tensors only")
+        return flats[0]
+
+    def _prox_state(self, f):
+        """``(anchor, header)`` of the flat buffer ``f``; without a ``set_prox_anchor()`` before it the
+        anchor starts as a copy of the master (the first eager step calls this before its update)."""
+        st = self._ls()
+        a = st.get("prox_anchor")
+        if a is None or a.shape != f.master.shape or a.device != f.master.device:
+            a = _graph_state(st, "prox_anchor", self._ldnn_capturing, lambda: f.master.detach().clone())
+        return a, self._state("prox_hdr", f.master.device)
+
+    def _loose_prox(self, p, mu):
+        """Loose tensors: ``mu * (p - a)`` of the parameter ``p`` (None when off); the anchor is created
+        as a copy of ``p`` by the first step that needs it."""
+        if mu is None:
+            return None
+        ps = self.state.setdefault(p, {})
+        if "prox_anchor" not in ps:
+            ps["prox_anchor"] = p.detach().clone()
+        return (p.data - ps["prox_anchor"]).mul_(mu)
+
+    @torch.no_grad()
+    def set_prox_anchor(self):
+        """Anchor FedProx at the current weights: copy the master into the anchor, in place -- the
+        address stands, so captured steps follow (the copy itself runs outside any graph).  The first
+        call allocates the anchor.  Of a sharded buffer the master must be whole (``gather_master``)."""
+        self._refuse_inside_ema("set_prox_anchor()")
+        if self._ldnn_capturing:
+            raise RuntimeError("set_prox_anchor() during a graph capture: the copy would not be recorded as a "
+                               "host-side call; anchor before the capture or between replays")
+        if self._prox_conf() is None:
+            raise RuntimeError("set_prox_anchor(): the proximal term is off (prox_mu is None or 0)")
+        f = self._one_flat("prox_mu")
+        if f is None:
+            for g in self.param_groups:
+                for p in g["params"]:
+                    ps = self.state.setdefault(p, {})
+                    if "prox_anchor" in ps:
+                        ps["prox_anchor"].copy_(p.data)
+                    else:
+                        ps["prox_anchor"] = p.detach().clone()
+            return
+        st = self._ls()
+        a = st.get("prox_anchor")
+        if a is None or a.shape != f.master.shape or a.device != f.master.device:
+            st["prox_anchor"] = f.master.detach().clone()
+        else:
+            a.copy_(f.master)
+
+    def prox_stats(self):
+        """``{"mu": float, "drift_norm": float or None}``: ``mu`` (0.0 when off) and ``|w - a|_2`` over
+        the flat master (loose tensors: over all of them) in fp64 torch ops, None before any anchor
+        exists.  One host sync; meant for once per global epoch."""
+        mu = self._prox_conf()
+        f = self._one_flat("prox_mu") if mu is not None else None
+        sq = None
+        if f is not None:
+            a = self._ls().get("prox_anchor")
+            if a is not None and a.shape == f.master.shape and a.device == f.master.device:
+                sq = (f.master.double() - a.double()).square().sum()
+        elif mu is not None:
+            pairs = [(p, self.state.get(p, {}).get("prox_anchor")) for g in self.param_groups for p in g["params"]]
+            if pairs and all(a is not None for _, a in pairs):
+                sq = sum((p.detach().double() - a.double()).square().sum().cpu() for p, a in pairs)
+        return {"mu": mu or 0.0, "drift_norm": None if sq is None else float(sq.sqrt())}
 
     # ---- per-step learning-rate schedule -------------------------------------------------
     _check_schedule = staticmethod(check_lr_schedule)
@@ -1094,6 +1236,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         loose_ema = None     # the EMA over loose tensors (a flat buffer's rides on its _FlatStep)
         if self._ema_conf() is not None and self._ema_flat() is None:
             loose_ema = self._loose_ema_begin()
+        if self._prox_conf() is not None:
+            self._one_flat("prox_mu")     # (one anchor: one flat buffer, or loose tensors only)
         if len(flats) != 1 or flats[0] is None:
             # several groups / loose tensors: one norm over all of them in torch ops; and one LARS
             # setting for every group, or a ValueError, before any update
@@ -1232,14 +1376,16 @@ class SGD(_FlatOptimizer):
 
     def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
                  max_grad_norm=None, lars_trust=None, lars_eps=1e-8, lars_exclude_1d=True, ema_decay=None,
-                 ema_warmup=True, lr_schedule=None):
+                 ema_warmup=True, lr_schedule=None, prox_mu=None):
         if lars_trust is not None and lars_trust <= 0:
             raise ValueError(f"lars_trust must be positive (None: LARS off); got {lars_trust}")
         self._check_ema_decay(ema_decay)
+        check_prox_mu(prox_mu)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, max_grad_norm=max_grad_norm, lars_trust=lars_trust,
                                       lars_eps=lars_eps, lars_exclude_1d=lars_exclude_1d, ema_decay=ema_decay,
-                                      ema_warmup=ema_warmup, lr_schedule=self._check_schedule(lr_schedule)))
+                                      ema_warmup=ema_warmup, lr_schedule=self._check_schedule(lr_schedule),
+                                      prox_mu=prox_mu))
 
     def _begin_ranges(self, s):
         # (``first`` is host-driven: the very first step seeds the momentum)
@@ -1253,17 +1399,17 @@ class SGD(_FlatOptimizer):
         if L is not None:
             lars = (L.ratio, L.segmap if sl is None else L.segmap[sl.start // 64: sl.stop // 64])
         _ext.C().sgd_step(p, grad, mom, shadow, s.hp, f.grad_scale, g["momentum"], g["dampening"], g["weight_decay"],
-                          g["nesterov"], first, zero_ranges=zero, clip=s.cl, lars=lars)
+                          g["nesterov"], first, zero_ranges=zero, clip=s.cl, lars=lars, prox=s.prox_arg(sl))
 
     def _update_torch(self, s, sl, p, g_, ratio):
         g, mu = s.group, s.group["momentum"]
         first, mom = s.ctx
         self._sgd_torch(p, g_, _cut(sl, mom)[0] if mu != 0 else None, s.lr, mu, g["dampening"],
-                        g["weight_decay"], g["nesterov"], first, ratio=ratio)
+                        g["weight_decay"], g["nesterov"], first, ratio=ratio, prox=s.prox_term(sl, p))
 
     def _loose_update(self, group, cl, loose):
         lr, mu, damp, wd, nest = (group[k] for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"))
-        lars = self._lars_conf()
+        lars, prox_mu = self._lars_conf(), self._prox_conf()
         if lars is not None and not loose:
             # LARS over tensors outside a flat buffer: the next parameter's index, rows of (ratio, wn, gn)
             ps_all = [p for g_ in self.param_groups for p in g_["params"]]
@@ -1289,12 +1435,15 @@ class SGD(_FlatOptimizer):
                 if L.adapt[k] and wn > 0 and gn > 0:
                     ratio = lars[0] * wn / (gn + wd * wn + lars[1])
                 L.ratio[k], L.w_norm[k], L.g_norm[k] = ratio, wn, gn
-            self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first, ratio=ratio)
+            self._sgd_torch(p.data, p.grad, ps.get("momentum_buffer"), lr, mu, damp, wd, nest, first, ratio=ratio,
+                            prox=self._loose_prox(p, prox_mu))
 
     @staticmethod
-    def _sgd_torch(p, g, buf, lr, mu, damp, wd, nest, first, ratio=None):
+    def _sgd_torch(p, g, buf, lr, mu, damp, wd, nest, first, ratio=None, prox=None):
         if wd != 0:
             g = g + wd * p
+        if prox is not None:      # mu * (p0 - a)
+            g = g + prox
         if ratio is not None:
             g = g * ratio
         if mu != 0:
@@ -1316,11 +1465,12 @@ class Adam(_FlatOptimizer):
     _bumps_step = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 ema_decay=None, ema_warmup=True, lr_schedule=None):
+                 ema_decay=None, ema_warmup=True, lr_schedule=None, prox_mu=None):
         self._check_ema_decay(ema_decay)
+        check_prox_mu(prox_mu)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                                      lr_schedule=self._check_schedule(lr_schedule)))
+                                      lr_schedule=self._check_schedule(lr_schedule), prox_mu=prox_mu))
 
     def _begin_ranges(self, s):
         if s.native:
@@ -1332,12 +1482,13 @@ class Adam(_FlatOptimizer):
         f, g = s.f, s.group
         p, grad, m, v, shadow = _cut(sl, f.master, f.grad, s.ctx[0], s.ctx[1], f.shadow)
         _ext.C().adam_step(p, grad, m, v, shadow, s.hp, f.grad_scale, *g["betas"], g["eps"], g["weight_decay"],
-                           self.decoupled, zero_ranges=zero, clip=s.cl)
+                           self.decoupled, zero_ranges=zero, clip=s.cl, prox=s.prox_arg(sl))
 
     def _update_torch(self, s, sl, p, g_, ratio):
         g = s.group
         m, v = _cut(sl, s.ctx[0], s.ctx[1])
-        self._adam_torch(p, g_, m, v, s.ctx[2], s.lr, *g["betas"], g["eps"], g["weight_decay"])
+        self._adam_torch(p, g_, m, v, s.ctx[2], s.lr, *g["betas"], g["eps"], g["weight_decay"],
+                         prox=s.prox_term(sl, p))
 
     def _loose_state(self, p, cl):
         """The per-tensor step of a loose ``p`` begins: its gradient clipped, its state (exp_avg,
@@ -1354,17 +1505,22 @@ class Adam(_FlatOptimizer):
 
     def _loose_update(self, group, cl, loose):
         lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        prox_mu = self._prox_conf()
         for p in group["params"]:
             if p.grad is not None:
                 ps = self._loose_state(p, cl)
-                self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps, wd)
+                self._adam_torch(p.data, p.grad, ps["exp_avg"], ps["exp_avg_sq"], ps["step"], lr, b1, b2, eps, wd,
+                                 prox=self._loose_prox(p, prox_mu))
 
-    def _adam_torch(self, p, g, m, v, t, lr, b1, b2, eps, wd):
+    def _adam_torch(self, p, g, m, v, t, lr, b1, b2, eps, wd, prox=None):
+        """``prox``: mu * (p0 - a), formed by the caller before the decoupled decay below touches p."""
         if wd != 0:
             if self.decoupled:
                 p.mul_(1 - lr * wd)
             else:
                 g = g + wd * p
+        if prox is not None:
+            g = g + prox
         _adam_moments(m, v, g, b1, b2)
         bc1 = 1 - b1 ** t
         bc2 = 1 - b2 ** t
@@ -1376,8 +1532,9 @@ class AdamW(Adam):
     decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 ema_decay=None, ema_warmup=True, lr_schedule=None):
-        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup, lr_schedule)
+                 ema_decay=None, ema_warmup=True, lr_schedule=None, prox_mu=None):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup, lr_schedule,
+                         prox_mu)
 
 
 class Lamb(_FlatOptimizer):
@@ -1399,14 +1556,17 @@ class Lamb(_FlatOptimizer):
     Adam's (``exp_avg``, ``exp_avg_sq``, ``step``); ``lamb_stats()`` reports the last ratios."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_grad_norm=None,
-                 lamb_exclude_1d=True, ema_decay=None, ema_warmup=True, lr_schedule=None):
+                 lamb_exclude_1d=True, ema_decay=None, ema_warmup=True, lr_schedule=None, prox_mu=None):
         self._check_ema_decay(ema_decay)
+        if check_prox_mu(prox_mu) is not None:
+            raise ValueError("Lamb takes no prox_mu: its trust ratio is defined on the Adam direction of g + "
+                             "weight_decay * w; there is no agreed form with a proximal term")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm, lamb_exclude_1d=lamb_exclude_1d,
                                       ema_decay=ema_decay, ema_warmup=ema_warmup,
                                       lr_schedule=self._check_schedule(lr_schedule)))
 
-    _begin_ranges, _loose_state, _bumps_step = Adam._begin_ranges, Adam._loose_state, True
+    _begin_ranges, _loose_state, _bumps_step, _prox_ok = Adam._begin_ranges, Adam._loose_state, True, False
 
     def _update_native(self, s, sl, zero):
         f, g, M = s.f, s.group, s.M
@@ -1469,13 +1629,14 @@ class Lion(_FlatOptimizer):
     (fp32, shaped like the master, zero at first) and the host's ``step``; there is no ``exp_avg_sq``."""
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, max_grad_norm=None, ema_decay=None,
-                 ema_warmup=True, lr_schedule=None):
+                 ema_warmup=True, lr_schedule=None, prox_mu=None):
         if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
             raise ValueError(f"Lion: betas must be two numbers in [0, 1); got {betas!r}")
         self._check_ema_decay(ema_decay)
+        check_prox_mu(prox_mu)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                                      lr_schedule=self._check_schedule(lr_schedule)))
+                                      lr_schedule=self._check_schedule(lr_schedule), prox_mu=prox_mu))
 
     def _begin_ranges(self, s):
         return self._buf("exp_avg", s.f.master)     # (no launch: nothing counts steps on the device)
@@ -1484,14 +1645,15 @@ class Lion(_FlatOptimizer):
         f, g = s.f, s.group
         p, grad, m, shadow = _cut(sl, f.master, f.grad, s.ctx, f.shadow)
         _ext.C().lion_step(p, grad, m, shadow, s.hp, f.grad_scale, *g["betas"], g["weight_decay"], zero_ranges=zero,
-                           clip=s.cl)
+                           clip=s.cl, prox=s.prox_arg(sl))
 
     def _update_torch(self, s, sl, p, g_, ratio):
         g = s.group
-        self._lion_torch(p, g_, _cut(sl, s.ctx)[0], s.lr, *g["betas"], g["weight_decay"])
+        self._lion_torch(p, g_, _cut(sl, s.ctx)[0], s.lr, *g["betas"], g["weight_decay"], prox=s.prox_term(sl, p))
 
     def _loose_update(self, group, cl, loose):
         lr, (b1, b2), wd = group["lr"], group["betas"], group["weight_decay"]
+        prox_mu = self._prox_conf()
         for p in group["params"]:
             if p.grad is None:
                 continue
@@ -1500,10 +1662,12 @@ class Lion(_FlatOptimizer):
             ps = self.state.setdefault(p, {})
             if "exp_avg" not in ps:
                 ps["exp_avg"] = torch.zeros_like(p)
-            self._lion_torch(p.data, p.grad, ps["exp_avg"], lr, b1, b2, wd)
+            self._lion_torch(p.data, p.grad, ps["exp_avg"], lr, b1, b2, wd, prox=self._loose_prox(p, prox_mu))
 
     @staticmethod
-    def _lion_torch(p, g, m, lr, b1, b2, wd):
+    def _lion_torch(p, g, m, lr, b1, b2, wd, prox=None):
+        if prox is not None:      # mu * (p0 - a): into c and m alike
+            g = g + prox
         c = m * b1 + g * (1 - b1)
         s = torch.where(c != c, c, c.sign())      # (torch.sign(NaN) is 0; the kernel's is NaN)
         if wd != 0:
@@ -1514,10 +1678,11 @@ class Lion(_FlatOptimizer):
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     max_grad_norm: float | None = None, ema_decay: float | None = None, ema_warmup: bool = True,
-                    lr_schedule: dict | None = None, **lars):
+                    lr_schedule: dict | None = None, prox_mu: float | None = None, **lars):
     """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  ema_decay / ema_warmup: the
     weight EMA of every optimizer (None: off).  lr_schedule: the per-step schedule of every optimizer
-    (a dict, see the module docstring; None: off).  "lars": SGD with
+    (a dict, see the module docstring; None: off).  prox_mu: FedProx's mu (None or 0: off; "lars" and
+    "lamb" refuse a positive one with a ValueError).  "lars": SGD with
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
     "sgd" takes them too); Adam, AdamW and Lion refuse them.  "lamb": Lamb, which takes
     ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords.  "lion": Lion at its
@@ -1530,7 +1695,7 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     bad = set(lars) - allowed
     if bad:
         raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
-    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup, lr_schedule=lr_schedule)
+    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup, lr_schedule=lr_schedule, prox_mu=prox_mu)
     if name == "lamb":
         return Lamb(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema, **lars)
     if name == "lars":

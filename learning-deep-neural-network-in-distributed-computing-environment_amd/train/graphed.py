@@ -27,6 +27,11 @@ What makes the ldnn step capturable:
   ``hp[0]`` on every replay; the host writes the header only when the base rate (StepLR) or
   the schedule dict changed -- a graph captured with ``lr_schedule=None`` never schedules
   until it is captured again;
+* FedProx (``prox_mu``) travels like the lr too: ``mu`` is a device scalar refreshed before a replay
+  when ``param_groups[..]['prox_mu']`` changed, and ``optimizer.set_prox_anchor()`` copies into the
+  anchor the captured updates read, so replays follow both -- a graph captured with ``prox_mu`` off
+  never applies the term until it is captured again, and a capture with ``prox_mu > 0`` needs an
+  eager step first, so that the anchor and its header exist;
 * the criterion's label smoothing is a kernel argument of the loss launch, so it IS
   captured: a replay raises when the criterion's value differs from the captured one;
 * dropout (models.layers.Dropout) needs no check: seed, module index, call count and rate live
@@ -250,7 +255,8 @@ class GraphedStep:
         # (the clipping threshold, LARS's trust coefficient / eps, the EMA's decay / warm-up flag and
         # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
-                g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
+                g.get("ema_warmup"), dict(g.get("lr_schedule") or {}), g.get("prox_mu"))
+               for g in self.optimizer.param_groups]
         for m in self._dropouts:   # (a changed module.p: written like a changed lr)
             m.sync_rate()
         if force or lrs != self._lrs:
@@ -560,7 +566,8 @@ class GraphedDPStep:
         # (the clipping threshold, LARS's trust coefficient / eps, the EMA's decay / warm-up flag and
         # the schedule's constants travel like the lr: device scalars the captured kernels read)
         lrs = [(g["lr"], g.get("max_grad_norm"), g.get("lars_trust"), g.get("lars_eps"), g.get("ema_decay"),
-                g.get("ema_warmup"), dict(g.get("lr_schedule") or {})) for g in self.optimizer.param_groups]
+                g.get("ema_warmup"), dict(g.get("lr_schedule") or {}), g.get("prox_mu"))
+               for g in self.optimizer.param_groups]
         for m in self._dropouts:   # (a changed module.p: written like a changed lr)
             m.sync_rate()
         if force or lrs != self._lrs:

@@ -359,6 +359,12 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
         # class weights of this rank's current shard, likewise (a resumed run starts from its own shard)
         cw = shard_class_weights(indices_train)
         cw_rec = {} if cw is None else {"class_weight_min": float(cw.min()), "class_weight_max": float(cw.max())}
+        # FedProx: this round's anchor is the weights it starts from (behind the last aggregation; under
+        # sharded DP the master is whole here, gather_master ran at the last epoch's end).  A device copy
+        # into the anchor's standing address, likewise outside the step graphs
+        prox_on = getattr(optimizer, "prox_stats", lambda: {"mu": 0.0})()["mu"] > 0
+        if prox_on:
+            optimizer.set_prox_anchor()
         max_steps = None
         dp_tail = False
         epoch_loader = trainloader   # (re-partitioning replaces it before the epoch's record is written)
@@ -396,6 +402,12 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
         cutoff.finish()
         if dp is not None and getattr(dp, "sharded", False):
             dp.gather_master(optimizer)   # sharded DP: whole master for aggregation / checkpoint / eval
+        # FedProx: how far the local epochs moved this replica from its anchor, before the aggregation
+        # moves it again (one host sync per global epoch)
+        prox_rec = {}
+        if prox_on:
+            ps = optimizer.prox_stats()
+            prox_rec = {"prox_mu": ps["mu"], "prox_drift_norm": ps["drift_norm"]}
 
         # ---- one metric exchange per global epoch (replaces C3-C6 per local epoch)
         lt = torch.tensor([float(max([len(b) for b in batch_losses] + [0]))], device=dev)
@@ -513,7 +525,7 @@ def train_global(model, trainloader, val_loader, trainset, valset, indices_train
                        samples_per_s=total_samples / max(duration, 1e-12),
                        train_samples_per_s_per_rank=[s_ / max(duration, 1e-12) for s_ in samples_per_rank],
                        **({"scaling_efficiency": total_samples / max(duration, 1e-12) / (N * ref_samples_per_s)}
-                          if ref_samples_per_s else {}), **clip_rec, **mix_rec, **cw_rec)
+                          if ref_samples_per_s else {}), **clip_rec, **mix_rec, **cw_rec, **prox_rec)
         if checkpointer is not None:
             checkpointer.save(global_epoch + 1, model, optimizer, scheduler, H,
                               extra=dict(indices_train=np.asarray(indices_train),
