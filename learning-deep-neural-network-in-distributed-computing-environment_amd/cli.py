@@ -56,12 +56,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n_train", type=int, default=None)
     p.add_argument("--n_test", type=int, default=None)
     p.add_argument("--data_root", type=str, default="data")
-    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars", "lamb", "lion"],
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd", "lars", "lamb", "lion", "adam8bit", "adamw8bit"],
                    help="lars: SGD-momentum with layer-wise adaptive rate scaling (per-tensor trust ratios); "
                         "lamb: Adam's direction with per-tensor trust ratios |w| / |u| (metrics.jsonl then logs "
                         "lamb_ratio_min / _median / _max per global epoch); lion: the sign of an interpolated "
                         "momentum with one moment buffer, betas (0.9, 0.99) and decoupled --weight_decay (use a "
-                        "3-10x smaller --lr and a 3-10x larger --weight_decay than for adamw)")
+                        "3-10x smaller --lr and a 3-10x larger --weight_decay than for adamw); adam8bit / adamw8bit: "
+                        "Adam / AdamW with both moments as block-scaled fp8 codes (a quarter of the state, "
+                        "18.25 B instead of 30 B per element and step; the rounding stream is seeded by --seed)")
     p.add_argument("--lamb_adapt_1d", action="store_true",
                    help="--optimizer lamb: also adapt tensors with dim() < 2 (biases, BatchNorm affine)")
     p.add_argument("--lars_trust", type=float, default=0.001,
@@ -274,6 +276,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
     elif getattr(args, "optimizer", None) == "lion":
         # the static engine's wgrad-fused optimizer epilogue has SGD and Adam forms only
         why = "--optimizer lion runs on the autograd path"
+    elif getattr(args, "optimizer", None) in ("adam8bit", "adamw8bit"):
+        # ... and keeps its moments in fp32
+        why = f"--optimizer {args.optimizer} runs on the autograd path"
     elif getattr(args, "label_smoothing", 0.0) > 0:
         # the static engine's head kernels compute the plain loss
         why = "--label_smoothing runs on the autograd path"
@@ -514,7 +519,8 @@ def main(argv=None):
                                             lars_exclude_1d=not args.lars_adapt_1d)
                                        if args.optimizer == "lars" else
                                        dict(lamb_exclude_1d=not args.lamb_adapt_1d)
-                                       if args.optimizer == "lamb" else {}))
+                                       if args.optimizer == "lamb" else
+                                       dict(seed=args.seed) if args.optimizer in ("adam8bit", "adamw8bit") else {}))
     scheduler = StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
 
     os.makedirs(args.out_dir, exist_ok=True)

@@ -1018,6 +1018,39 @@ void lion_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor
         "lion_step");
 }
 
+// Adam8bit: codes uint8 [n], scales fp32 [n / 64]; whole 64-element blocks only (no block is ever cut)
+void adam8_step(const at::Tensor& param, const at::Tensor& grad, const at::Tensor& mq, const at::Tensor& sq,
+                const at::Tensor& mscale, const at::Tensor& sscale, const c10::optional<at::Tensor>& shadow,
+                const at::Tensor& hp, double grad_scale, double beta1, double beta2, double eps, double weight_decay,
+                bool decoupled, int64_t seed, int64_t base, const Ranges& zero_ranges,
+                const c10::optional<at::Tensor>& clip, const Prox& prox, bool wide) {
+  const int64_t n = f32_bufs("adam8", {{param, "param"}, {grad, "grad"}}, true, true);
+  TORCH_CHECK(n % 64 == 0 && base % 64 == 0 && base >= 0, "adam8: the range must be 64-element aligned (", n,
+              " elements at offset ", base, ")");
+  for (const Named& x : {Named{mq, "exp_avg_q"}, Named{sq, "exp_avg_sq_q"}}) {
+    check_dev(x.t, at::kByte, x.name);
+    TORCH_CHECK(x.t.is_contiguous() && x.t.numel() == n && x.t.device() == param.device() &&
+                    (reinterpret_cast<uintptr_t>(x.t.data_ptr()) & 7) == 0,
+                "adam8: ", x.name, " must hold ", n, " contiguous uint8 codes on the parameters' device, 8-byte aligned");
+  }
+  for (const Named& x : {Named{mscale, "exp_avg_scale"}, Named{sscale, "exp_avg_sq_scale"}}) {
+    check_dev(x.t, at::kFloat, x.name);
+    TORCH_CHECK(x.t.is_contiguous() && x.t.numel() == n / 64 && x.t.device() == param.device(), "adam8: ", x.name,
+                " must hold ", n / 64, " contiguous fp32 scales on the parameters' device");
+  }
+  const auto px = prox_ptrs("adam8", prox, param);
+  const float* hpp = hp_ptr("adam8", hp, param);
+  uint16_t* sh = shadow_ptr("adam8", shadow, param, true);
+  const float* cp = clip_ptr(clip, param);
+  const ldnn::Adam8Params ap = ldnn::adam8_params(beta1, beta2, eps, weight_decay, decoupled, grad_zero(zero_ranges, n));
+  c10::hip::HIPGuardMasqueradingAsCUDA g(param.device());
+  check(ldnn::adam8_step(param.data_ptr<float>(), grad.data_ptr<float>(), mq.data_ptr<uint8_t>(),
+                         sq.data_ptr<uint8_t>(), mscale.data_ptr<float>(), sscale.data_ptr<float>(), sh, hpp,
+                         (float)grad_scale, ap, n, (uint64_t)seed, base, cur_stream(param), cp, px.first, px.second,
+                         wide),
+        "adam8_step");
+}
+
 void head_fwd_xent(const at::Tensor& h, const at::Tensor& W, const at::Tensor& bias, const at::Tensor& labels,
                    const c10::optional<at::Tensor>& logits, const at::Tensor& dlogits, const at::Tensor& stats,
                    int64_t num_classes, double grad_scale, const c10::optional<at::Tensor>& dh,
@@ -2627,6 +2660,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("beta2"), py::arg("weight_decay"),
         py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none(),
         py::arg("prox") = py::none());
+  m.def("adam8_step", &adam8_step, "Adam with block-scaled e4m3 moments (64-element blocks, stochastic rounding "
+        "hashed from seed, hp[1] and the absolute element index base + i); lr = hp[0]", py::arg("param"),
+        py::arg("grad"), py::arg("mq"), py::arg("sq"), py::arg("mscale"), py::arg("sscale"), py::arg("shadow"),
+        py::arg("hp"), py::arg("grad_scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("weight_decay"), py::arg("decoupled"), py::arg("seed"), py::arg("base"),
+        py::arg("zero_ranges") = std::vector<std::pair<int64_t, int64_t>>{}, py::arg("clip") = py::none(),
+        py::arg("prox") = py::none(), py::arg("wide") = false);
   m.def("bump_step", &bump_step, py::arg("hp"), py::arg("clip") = py::none());
   m.def("lr_sched", &lr_sched, "learning-rate schedule, once per step: hp[0] = base * s(t + 1), the factor and the "
         "step count into hdr (nothing on a skipped step)", py::arg("hdr"), py::arg("hp"), py::arg("clip") = py::none());

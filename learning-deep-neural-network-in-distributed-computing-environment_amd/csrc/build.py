@@ -101,6 +101,9 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
     inc, lib, abi = _torch_paths()
     common = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(HERE, 'include')}", "-Wno-unused-result"]
     kern_flags = common + [f"--offload-arch={ARCH}", "-munsafe-fp-atomics"]
+    # per-file additions.  optim_q.hip: no packed fp32 arithmetic (v_pk_mul_f32 / v_pk_fma_f32), so its
+    # float4 expressions lower to the scalar forms the torch twin rounds like
+    extra_flags = {"optim_q.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
     py_inc = sysconfig.get_paths()["include"]
     import pybind11
 
@@ -119,7 +122,8 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
     jobs_list = []
     for src in sorted(glob.glob(os.path.join(HERE, "kernels", "*.hip"))):
         obj = os.path.join(BUILD_DIR, os.path.basename(src) + ".o")
-        jobs_list.append((src, obj, [HIPCC] + kern_flags + ["-c", src, "-o", obj]))
+        flags = kern_flags + extra_flags.get(os.path.basename(src), [])
+        jobs_list.append((src, obj, [HIPCC] + flags + ["-c", src, "-o", obj]))
     bsrc = os.path.join(HERE, "bindings.cpp")
     bobj = os.path.join(BUILD_DIR, "bindings.o")
     jobs_list.append((bsrc, bobj, [HIPCC] + bind_flags + ["-c", bsrc, "-o", bobj]))

@@ -531,6 +531,29 @@ struct LionParams {
 hipError_t lion_step(float* param, float* grad, float* m, uint16_t* shadow, const float* hp, float grad_scale,
                      LionParams lp, int64_t n, hipStream_t s, const float* clip = nullptr,
                      const float* prox_anchor = nullptr, const float* prox_hdr = nullptr);
+// Adam8bit (optim_q.hip): Adam with both moments as block-scaled e4m3fn codes.  A block is 64 consecutive
+// elements: mq / sq hold n codes of m and of s = sqrt(v), mscale / sscale n / 64 fp32 scales; the math of
+// one block is written out at the top of optim_q.hip.  n % 64 == 0 and base % 64 == 0 (hipErrorInvalidValue
+// otherwise); base is the range's element offset in the flat buffer, which the counter-hashed rounding bits
+// are indexed by (with `seed` and the step count hp[1]).  hp, clip, prox and ap.zero as in adam_step.
+// wide: eight elements per lane and eight lanes per block instead of four and sixteen (same results).
+// The hyper-parameters: 1 - beta and the floor's factor are formed in double and rounded once (1.f - 0.999f
+// is off by 1.3e-5 of itself, which the block scales would carry).
+struct Adam8Params {
+  float beta1, beta2, omb1, omb2, vfloor, eps, weight_decay;
+  int decoupled;  // AdamW8bit
+  GradZero zero;
+};
+inline Adam8Params adam8_params(double beta1, double beta2, double eps, double weight_decay, bool decoupled,
+                                const GradZero& zero) {
+  return {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+          beta1 <= beta2 ? (float)((1.0 - beta2) / (1.0 - beta1)) : 0.f, (float)eps, (float)weight_decay,
+          decoupled ? 1 : 0, zero};
+}
+hipError_t adam8_step(float* param, float* grad, uint8_t* mq, uint8_t* sq, float* mscale, float* sscale,
+                      uint16_t* shadow, const float* hp, float grad_scale, Adam8Params ap, int64_t n, uint64_t seed,
+                      int64_t base, hipStream_t s, const float* clip = nullptr, const float* prox_anchor = nullptr,
+                      const float* prox_hdr = nullptr, bool wide = false);
 // hp[1] += 1 (graph-capturable step counter); with clip: not on a skipped step
 hipError_t bump_step(float* hp, hipStream_t s, const float* clip = nullptr);
 

@@ -734,9 +734,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         sd = super().state_dict()
         ls = self._ls()
         flat = {k: v for k, v in ls.items() if k not in _TRANSIENT}
-        if self._bumps_step and self._clip_threshold() is not None and "hp" in ls and "exp_avg" in ls:
+        if self._bumps_step and self._clip_threshold() is not None and "hp" in ls and \
+                ("exp_avg" in ls or "exp_avg_q" in ls):
             # the fused Adam's step count lives on the device: skipped steps did not advance it
-            # (Adam / AdamW / Lamb; Lion never bumps hp[1], its count is the host's)
+            # (Adam / AdamW / Lamb / Adam8bit; Lion never bumps hp[1], its count is the host's)
             flat["step"] = int(ls["hp"][1].item())
         if "ema_hdr" in ls:
             # ... and so does the EMA's update count (load_state_dict hands it to the next header)
@@ -1537,6 +1538,199 @@ class AdamW(Adam):
                          prox_mu)
 
 
+# ---- Adam8bit: block-scaled e4m3 moments (csrc/kernels/optim_q.hip) -------------------------------
+_Q_BLOCK, _Q_MAX, _Q_GROUP_MUL = 64, 448.0, 0xD1B54A32D192ED03
+
+
+def _q8_decode(codes, scale):
+    """[nb * 64] uint8 e4m3fn codes and [nb] scales -> fp32 [nb, 64]."""
+    return codes.view(torch.float8_e4m3fn).float().view(-1, _Q_BLOCK) * scale.view(-1, 1)
+
+
+def _q8_bits(seed, t, lo, hi, device):
+    """The kernel's 16 rounding bits of the flat elements [lo, hi) at step count ``t`` as two int32
+    [(hi - lo) / 64, 64] tensors (first moment, root of the second), formed on the host."""
+    import numpy as np
+
+    from ..data.autoaugment import smix, smix_np
+
+    u, m64 = np.uint64, (1 << 64) - 1
+    key = smix(smix(int(seed) & m64) ^ (int(t) & m64))
+    with np.errstate(over="ignore"):
+        hm = smix_np(u(key) ^ (np.arange(lo // 4, hi // 4, dtype=np.uint64) * u(_Q_GROUP_MUL)))
+    shifts = np.arange(4, dtype=np.uint64) * u(16)
+
+    def bits(h):
+        b = ((h[:, None] >> shifts) & u(0xFFFF)).astype(np.int32)
+        return torch.from_numpy(b.reshape(-1, _Q_BLOCK)).to(device)
+
+    return bits(hm), bits(smix_np(hm))
+
+
+def _q8_encode(x, r):
+    """fp32 [nb, 64] and the rounding bits -> (uint8 codes [nb * 64], fp32 scales [nb]): scale absmax / 448,
+    stochastic rounding to 3 mantissa bits in the fp32 bit pattern, then the (exact there) e4m3fn cast."""
+    a = x.abs().amax(1, keepdim=True)
+    inv = torch.where(a > 0, (_Q_MAX / a).clamp(max=torch.finfo(torch.float32).max), torch.zeros_like(a))
+    y = (x * inv).clamp(-_Q_MAX, _Q_MAX).contiguous()
+    y = ((y.view(torch.int32) + (r << 4)) & ~0xFFFFF).view(torch.float32)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8).reshape(-1), (a / _Q_MAX).reshape(-1)
+
+
+class Adam8bit(_FlatOptimizer):
+    """Adam whose two moments are kept as block-scaled OCP fp8 (e4m3fn) codes: block-wise quantised
+    optimizer state (Dettmers et al. 2022; Peng et al. 2023, FP8-LM).  A block is 64 consecutive flat
+    elements; per block the state is 64 codes of ``m``, 64 codes of ``s = sqrt(v)`` and one fp32 scale
+    each -- a quarter of Adam's state, and the fused update (``adam8_step``) moves 18.25 B per element
+    where ``adam_step`` moves 30.  One step of one block:
+
+        m0 = dec(cm) * sm,  s0 = dec(cs) * ss,  v0 = s0^2;  g as Adam forms it (scaled, clipped, + coupled
+        decay, + the proximal term; AdamW's decay goes to p)
+        m = b1 m0 + (1 - b1) g,  v = b2 v0 + (1 - b2) g^2,  and when b1 <= b2: v = max(v, m^2 (1 - b2) / (1 - b1))
+        s = sqrt(v),  p -= (lr / bc1) * m / (s / bc2s + eps)      (the fp32 m and s, not their codes)
+        for x in (m, s): a = max_block |x|, scale = a / 448, y = x * min(448 / a, FLT_MAX) (0 when a == 0),
+        clamped to +-448, rounded STOCHASTICALLY to the e4m3 grid, stored as codes
+
+    The floor on ``v`` is a no-op for exact Adam (Cauchy-Schwarz); with quantised state it bounds the step of
+    an element whose second moment rounded to 0 under a surviving first moment by
+    ``sqrt((1 - b1) / (1 - b2)) * lr``.  Stochastic rounding is what lets the second moment move at all:
+    with ``b2 = 0.999`` a step changes ``s`` by 0.05 %, an e4m3 step is 6-12 %.  It adds ``r << 4`` (``r``:
+    16 random bits) to the fp32 bit pattern and drops the 20 mantissa bits e4m3 does not have; below
+    ``2^-6`` of the block maximum / 448 -- the e4m3 subnormals -- the cast's round-to-nearest applies on top,
+    the one place where the rounding is not stochastic.  The bits are hashed from ``seed``, the step count
+    and the ABSOLUTE flat element index (``key = smix(smix(seed) ^ t)``; the four elements at index ``4q``
+    share ``h_m = smix(key ^ q * 0xD1B54A32D192ED03)``, ``h_s = smix(h_m)``, 16 bits each), so eager,
+    range, sharded and replayed steps write the same codes, a replay advances the stream and a skipped
+    step draws nothing.
+
+    State (``_ls()``, none of it transient, created by an eager step): ``exp_avg_q`` / ``exp_avg_sq_q``
+    (uint8 [n]), ``exp_avg_scale`` / ``exp_avg_sq_scale`` (fp32 [n / 64]); ``state_dict()`` saves them with
+    ``seed`` and the step count, ``gather_master(optimizer)`` makes them whole.  Every range of a range or
+    sharded step must be 64-element aligned: no block is ever cut.  Clipping, the non-finite guard, the
+    EMA, ``lr_schedule`` and ``prox_mu`` ride on the step as for ``Adam``.  Non-finite gradients: without
+    ``max_grad_norm`` a non-finite element makes its block's scale non-finite, so the block's 64 moments
+    decode to NaN from the next step on -- the 8-bit form of "a NaN gradient reaches its moment and
+    weight"; with it the step is skipped and no code, scale, master or shadow changes.  On the CPU, for
+    loose tensors (each blocked over its flattened, zero-padded self, indices from 0) and with several
+    param groups the same steps run in fp32 torch ops (``_adam8_torch``)."""
+
+    decoupled = False
+    _bumps_step = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True, lr_schedule=None, prox_mu=None, seed: int = 0):
+        self._check_ema_decay(ema_decay)
+        check_prox_mu(prox_mu)
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 2 ** 63:
+            raise ValueError(f"seed must be a whole number in [0, 2**63); got {seed!r}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                      lr_schedule=self._check_schedule(lr_schedule), prox_mu=prox_mu, seed=int(seed)))
+
+    @staticmethod
+    def _q_zeros(n, device):
+        return {"exp_avg_q": torch.zeros(n, dtype=torch.uint8, device=device),
+                "exp_avg_sq_q": torch.zeros(n, dtype=torch.uint8, device=device),
+                "exp_avg_scale": torch.zeros(n // _Q_BLOCK, dtype=torch.float32, device=device),
+                "exp_avg_sq_scale": torch.zeros(n // _Q_BLOCK, dtype=torch.float32, device=device)}
+
+    def _begin_ranges(self, s):
+        if s.native:
+            _ext.C().bump_step(s.hp, clip=s.cl)   # once per step, before any range reads the step count
+        st, m = s.st, s.f.master
+        q = st.get("exp_avg_q")
+        if q is None or q.numel() != m.numel() or q.device != m.device:
+            if m.numel() % _Q_BLOCK:
+                raise ValueError(f"Adam8bit: the flat buffer's {m.numel()} elements are no multiple of {_Q_BLOCK}")
+            if self._ldnn_capturing:     # (as _graph_state: a capture allocates no state)
+                raise RuntimeError(_CAPTURE_MSG)
+            st.update(self._q_zeros(m.numel(), m.device))
+        st["seed"] = s.group["seed"]
+        return (st["exp_avg_q"], st["exp_avg_sq_q"], st["exp_avg_scale"], st["exp_avg_sq_scale"],
+                st.get("step", 0) + 1)
+
+    @staticmethod
+    def _q_cut(s, sl):
+        """The four state tensors over the flat slice ``sl`` (codes by elements, scales by blocks) and its offset."""
+        mq, sq, ms, ss = s.ctx[:4]
+        if sl is None:
+            return mq, sq, ms, ss, 0
+        _aligned64("Adam8bit", "update", [(sl.start, sl.stop)])
+        b = slice(sl.start // _Q_BLOCK, sl.stop // _Q_BLOCK)
+        return mq[sl], sq[sl], ms[b], ss[b], sl.start
+
+    def _update_native(self, s, sl, zero):
+        f, g = s.f, s.group
+        mq, sq, ms, ss, base = self._q_cut(s, sl)
+        p, grad, shadow = _cut(sl, f.master, f.grad, f.shadow)
+        _ext.C().adam8_step(p, grad, mq, sq, ms, ss, shadow, s.hp, f.grad_scale, *g["betas"], g["eps"],
+                            g["weight_decay"], self.decoupled, g["seed"], base, zero_ranges=zero, clip=s.cl,
+                            prox=s.prox_arg(sl))
+
+    def _update_torch(self, s, sl, p, g_, ratio):
+        g = s.group
+        mq, sq, ms, ss, base = self._q_cut(s, sl)
+        self._adam8_torch(p, g_, mq, sq, ms, ss, s.ctx[4], s.lr, *g["betas"], g["eps"], g["weight_decay"], g["seed"],
+                          base, prox=s.prox_term(sl, p))
+
+    def _loose_update(self, group, cl, loose):
+        lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        prox_mu = self._prox_conf()
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if cl is not None:
+                p.grad.mul_(cl[_CLIP_COEF].to(p.grad.device))
+            n = p.numel()
+            npad = (n + _Q_BLOCK - 1) // _Q_BLOCK * _Q_BLOCK
+            ps = self.state.setdefault(p, {})
+            if "exp_avg_q" not in ps:
+                ps.update(self._q_zeros(npad, p.device), step=0)
+            ps["step"] += 1
+            prox = self._loose_prox(p, prox_mu)
+            # (the tensor's flattened, zero-padded self: padding has zero gradient and stays zero)
+            w, g, x = (torch.zeros(npad, dtype=torch.float32, device=p.device) for _ in range(3))
+            w[:n], g[:n] = p.data.reshape(-1), p.grad.reshape(-1)
+            if prox is not None:
+                x[:n] = prox.reshape(-1)
+            self._adam8_torch(w, g, ps["exp_avg_q"], ps["exp_avg_sq_q"], ps["exp_avg_scale"], ps["exp_avg_sq_scale"],
+                              ps["step"], lr, b1, b2, eps, wd, group["seed"], 0, prox=x if prox is not None else None)
+            p.data.copy_(w[:n].view_as(p))
+
+    def _adam8_torch(self, p, g, mq, sq, ms, ss, t, lr, b1, b2, eps, wd, seed, base, prox=None):
+        """adam8_step in fp32 torch ops over the 64-aligned flat range at element offset ``base``; ``prox``:
+        mu * (p0 - a), formed by the caller before the decoupled decay below touches p."""
+        m0, s0 = _q8_decode(mq, ms), _q8_decode(sq, ss)
+        g = g.view(-1, _Q_BLOCK)
+        if wd != 0:
+            if self.decoupled:
+                p.mul_(1 - lr * wd)
+            else:
+                g = g + wd * p.view(-1, _Q_BLOCK)
+        if prox is not None:
+            g = g + prox.view(-1, _Q_BLOCK)
+        m = b1 * m0 + (1 - b1) * g
+        v = b2 * (s0 * s0) + (1 - b2) * g * g
+        if b1 <= b2:
+            v = torch.maximum(v, m * m * ((1 - b2) / (1 - b1)))
+        s = v.sqrt()
+        p.view(-1, _Q_BLOCK).addcdiv_(m, (s / math.sqrt(1 - b2 ** t)).add_(eps), value=-lr / (1 - b1 ** t))
+        rm, rs = _q8_bits(seed, t, base, base + p.numel(), p.device)
+        for x, r, codes, scale in ((m, rm, mq, ms), (s, rs, sq, ss)):
+            c, a = _q8_encode(x, r)
+            codes.copy_(c)
+            scale.copy_(a)
+
+
+class AdamW8bit(Adam8bit):
+    decoupled = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True, lr_schedule=None, prox_mu=None, seed: int = 0):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, ema_warmup, lr_schedule,
+                         prox_mu, seed)
+
+
 class Lamb(_FlatOptimizer):
     """LAMB (You et al. 2020): Adam's direction with a per-tensor trust ratio,
 
@@ -1678,7 +1872,7 @@ class Lion(_FlatOptimizer):
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     max_grad_norm: float | None = None, ema_decay: float | None = None, ema_warmup: bool = True,
-                    lr_schedule: dict | None = None, prox_mu: float | None = None, **lars):
+                    lr_schedule: dict | None = None, prox_mu: float | None = None, seed: int = 0, **lars):
     """max_grad_norm: clip by the global L2 norm (None or <= 0: off).  ema_decay / ema_warmup: the
     weight EMA of every optimizer (None: off).  lr_schedule: the per-step schedule of every optimizer
     (a dict, see the module docstring; None: off).  prox_mu: FedProx's mu (None or 0: off; "lars" and
@@ -1686,12 +1880,13 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
     ``lars_trust=0.001``; ``lars_trust`` / ``lars_eps`` / ``lars_exclude_1d`` go to SGD (and
     "sgd" takes them too); Adam, AdamW and Lion refuse them.  "lamb": Lamb, which takes
     ``lamb_exclude_1d`` (nobody else does) and refuses the ``lars_*`` keywords.  "lion": Lion at its
-    default betas (0.9, 0.99); ``momentum`` is ignored, as for Adam."""
+    default betas (0.9, 0.99); ``momentum`` is ignored, as for Adam.  "adam8bit" / "adamw8bit": Adam8bit /
+    AdamW8bit (block-scaled fp8 moments), the only ones that read ``seed`` (the rounding stream's)."""
     name = name.lower()
     if max_grad_norm is not None and max_grad_norm <= 0:
         max_grad_norm = None
     allowed = {"lamb_exclude_1d"} if name == "lamb" else \
-        set() if name in ("adam", "adamw", "lion") else {"lars_trust", "lars_eps", "lars_exclude_1d"}
+        set() if name in ("adam", "adamw", "lion", "adam8bit", "adamw8bit") else {"lars_trust", "lars_eps", "lars_exclude_1d"}
     bad = set(lars) - allowed
     if bad:
         raise TypeError(f"build_optimizer({name!r}) got unexpected keyword arguments {sorted(bad)}")
@@ -1709,6 +1904,9 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
         return Adam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     if name == "adamw":
         return AdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
+    if name in ("adam8bit", "adamw8bit"):
+        cls = Adam8bit if name == "adam8bit" else AdamW8bit
+        return cls(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, seed=seed, **ema)
     if name == "lion":
         return Lion(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, **ema)
     raise ValueError(f"unknown optimizer {name!r}")

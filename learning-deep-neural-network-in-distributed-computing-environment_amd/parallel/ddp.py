@@ -382,14 +382,19 @@ class GradBucketer:
         self.wait_gathers()
         if not self.shard or self.master_whole:
             return
-        bufs = [self.flat.master]
+        bufs, scales = [self.flat.master], []
         if optimizer is not None:
             bufs += [v for k, v in optimizer._ls().items() if torch.is_tensor(v) and v.shape == self.flat.master.shape]
+            # (Adam8bit: one scale per 64-element block; shards and buckets lie on block boundaries)
+            scales = [v for k, v in optimizer._ls().items() if torch.is_tensor(v) and k.endswith("_scale")
+                      and v.numel() * 64 == self.flat.master.numel()]
         for i, b in enumerate(self.buckets):
             if b["sharded"]:
                 lo, hi = self.shard_range(i)
                 for t in bufs:
                     self.comm.all_gather_into(t[b["begin"]: b["end"]], t[lo:hi])
+                for t in scales:
+                    self.comm.all_gather_into(t[b["begin"] // 64: b["end"] // 64], t[lo // 64: hi // 64])
         self.master_whole = True
         if self.flat.shadow is not None:
             self.flat.refresh_shadow()
