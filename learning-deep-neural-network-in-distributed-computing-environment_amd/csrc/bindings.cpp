@@ -1936,6 +1936,64 @@ void gn_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, con
         "gn_backward");
 }
 
+// ---- depthwise 3x3 conv, padding 1: x / dx [N][H][W][Cp], y / dy [N][P][Q][Cp] dense NHWC bf16; w / dw the
+// bf16 / fp32 KRSC storage [Cp][3][3][8] of a [C,1,3,3] parameter
+void dw_check(const at::Tensor& x, const at::Tensor& y, int64_t stride, const char* who) {
+  check_dev(x, at::kBFloat16, "x");
+  check_dev(y, at::kBFloat16, "y");
+  TORCH_CHECK(stride == 1 || stride == 2, who, ": stride must be 1 or 2, got ", stride);
+  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.is_contiguous() && y.is_contiguous() && x.numel() > 0,
+              who, ": activations must be dense NHWC [N][H][W][Cp]");
+  TORCH_CHECK(x.size(3) % 8 == 0, who, ": Cp must be a multiple of 8, got ", x.size(3));
+  TORCH_CHECK(y.size(0) == x.size(0) && y.size(3) == x.size(3) && y.size(1) == (x.size(1) - 1) / stride + 1 &&
+                  y.size(2) == (x.size(2) - 1) / stride + 1,
+              who, ": a 3x3 / pad 1 / stride ", stride, " conv of ", x.sizes(), " does not give ", y.sizes());
+  TORCH_CHECK(aligned16(x.data_ptr()) && aligned16(y.data_ptr()), who, ": activations must be 16-byte aligned");
+  TORCH_CHECK(x.device() == y.device() && x.data_ptr() != y.data_ptr(), who, ": one device, no in-place");
+  TORCH_CHECK(ldnn::dwconv_workspace_floats(x.size(0), x.size(1), x.size(2), x.size(3), (int)stride) > 0, who,
+              ": shape too large for the kernels' 32-bit row and tile counts");
+}
+
+void dw_check_w(const at::Tensor& w, at::ScalarType dt, const at::Tensor& x, const char* who) {
+  check_dev(w, dt, "w");
+  TORCH_CHECK(w.dim() == 4 && w.is_contiguous() && w.size(0) == x.size(3) && w.size(1) == 3 && w.size(2) == 3 &&
+                  w.size(3) == 8,
+              who, ": the weight storage of a depthwise 3x3 kernel over ", x.size(3), " channels is [Cp][3][3][8], got ",
+              w.sizes());
+  TORCH_CHECK(w.device() == x.device() && aligned16(w.data_ptr()), who, ": w on x's device, 16-byte aligned");
+}
+
+void dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& y, int64_t stride,
+                const c10::optional<at::Tensor>& bias, bool relu) {
+  dw_check(x, y, stride, "dwconv_fwd");
+  dw_check_w(w, at::kBFloat16, x, "dwconv_fwd");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::dwconv_forward(bf16_ptr(x), bf16_ptr(w), fptr_opt(bias, x.size(3), "bias", &x), relu, bf16_mut(y),
+                             x.size(0), x.size(1), x.size(2), x.size(3), (int)stride, cur_stream(x)),
+        "dwconv_forward");
+}
+
+void dwconv_dgrad(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& dx, int64_t stride) {
+  dw_check(dx, dy, stride, "dwconv_dgrad");
+  dw_check_w(w, at::kBFloat16, dx, "dwconv_dgrad");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dx.device());
+  check(ldnn::dwconv_dgrad(bf16_ptr(dy), bf16_ptr(w), bf16_mut(dx), dx.size(0), dx.size(1), dx.size(2), dx.size(3),
+                           (int)stride, cur_stream(dx)),
+        "dwconv_dgrad");
+}
+
+void dwconv_wgrad(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& ws, const at::Tensor& dw, int64_t C,
+                  bool accumulate, int64_t stride) {
+  dw_check(x, dy, stride, "dwconv_wgrad");
+  dw_check_w(dw, at::kFloat, x, "dwconv_wgrad");
+  TORCH_CHECK(C >= 1 && C <= x.size(3), "dwconv_wgrad: ", C, " channels in a storage of ", x.size(3));
+  const int64_t need = ldnn::dwconv_workspace_floats(x.size(0), x.size(1), x.size(2), x.size(3), (int)stride);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::dwconv_wgrad(bf16_ptr(x), bf16_ptr(dy), fptr_opt(ws, need, "ws", &x, true), dw.data_ptr<float>(), C,
+                           accumulate, x.size(0), x.size(1), x.size(2), x.size(3), (int)stride, cur_stream(x)),
+        "dwconv_wgrad");
+}
+
 // ---- LayerNorm: x, y, dy, dx logical [B][N] bf16 matrices with unit column stride, row strides that are
 // multiples of 8 and 16-byte aligned bases (a dense matrix with N % 8 == 0, or the [B][N] view of a padded
 // [B][ld] buffer); gamma, beta, dgamma, dbeta fp32 of at least N rounded up to 8 elements (the FlatParams
@@ -2726,6 +2784,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("N"), py::arg("P"), py::arg("C"), py::arg("G"));
   m.def("gn_slabs", &ldnn::gn_slabs, "pixel slabs per sample of the GroupNorm statistics passes", py::arg("N"),
         py::arg("P"), py::arg("C"), py::arg("G"));
+  m.def("dwconv_fwd", &dwconv_fwd, "depthwise 3x3 / pad 1 conv over dense NHWC bf16: y = relu?(x * w (+ bias))",
+        py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stride"), py::arg("bias") = py::none(),
+        py::arg("relu") = false);
+  m.def("dwconv_dgrad", &dwconv_dgrad, "input gradient of dwconv_fwd (a gather, also at stride 2)", py::arg("dy"),
+        py::arg("w"), py::arg("dx"), py::arg("stride"));
+  m.def("dwconv_wgrad", &dwconv_wgrad, "weight gradient of dwconv_fwd into the fp32 KRSC storage: stored, or added "
+        "onto the tap positions (accumulate); fixed summation order", py::arg("x"), py::arg("dy"), py::arg("ws"),
+        py::arg("dw"), py::arg("channels"), py::arg("accumulate"), py::arg("stride"));
+  m.def("dwconv_workspace_floats", &ldnn::dwconv_workspace_floats, "fp32 scratch of one dwconv_wgrad call",
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("stride"));
   m.def("ln_fwd", &ln_fwd, "y = act(layer_norm(x)) over the rows of a [B][N] bf16 matrix; writes mean / rstd [B]",
         py::arg("x"), py::arg("y"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"),
         py::arg("eps"), py::arg("act"));

@@ -299,6 +299,21 @@ hipError_t pool2d_bwd(const uint16_t* dy, const uint8_t* argmax, uint16_t* dx, i
 hipError_t global_avgpool_fwd(const uint16_t* x, uint16_t* y, int N, int HW, int C, hipStream_t s);
 hipError_t global_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int HW, int C, hipStream_t s);
 
+// ---- Depthwise 3x3 convolution, padding 1, stride 1 or 2 (dwconv.hip): groups == channels, multiplier 1
+// x, dx [N][H][W][Cp] and y, dy [N][P][Q][Cp] dense NHWC bf16 (P = (H - 1) / stride + 1), Cp % 8 == 0,
+// 16-byte aligned; w: the bf16 KRSC storage of a [C,1,3,3] parameter, [Cp][3][3][8] with the tap in
+// element 0; fp32 accumulation.  bias (nullable, fp32 [Cp]) and relu: the forward epilogue.
+hipError_t dwconv_forward(const uint16_t* x, const uint16_t* w, const float* bias, bool relu, uint16_t* y, int64_t N,
+                          int64_t H, int64_t W, int64_t Cp, int stride, hipStream_t s);
+hipError_t dwconv_dgrad(const uint16_t* dy, const uint16_t* w, uint16_t* dx, int64_t N, int64_t H, int64_t W,
+                        int64_t Cp, int stride, hipStream_t s);
+// dw: the fp32 gradient storage [Cp][3][3][8]; stored whole (zeros beside the taps and for the channels
+// C .. Cp-1) unless `accumulate`, which adds onto the tap positions only.  ws: dwconv_workspace_floats
+// fp32 of scratch (nothing to zero or keep).  No atomics: a shape has one summation order.
+hipError_t dwconv_wgrad(const uint16_t* x, const uint16_t* dy, float* ws, float* dw, int64_t C, bool accumulate,
+                        int64_t N, int64_t H, int64_t W, int64_t Cp, int stride, hipStream_t s);
+int64_t dwconv_workspace_floats(int64_t N, int64_t H, int64_t W, int64_t Cp, int stride);   // -1: unsupported shape
+
 // ---- GroupNorm on dense NHWC bf16 [N][P][C] (group_norm.hip), C % 8 == 0, C % G == 0
 // Statistics per (sample, group of C / G neighbouring channels), biased variance; residual add and
 // ReLU fused into the apply pass.  No atomics: a shape has one summation order.

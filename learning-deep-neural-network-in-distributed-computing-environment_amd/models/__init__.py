@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock  # noqa: F401
+from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock, SeparableConv2d  # noqa: F401
 from .layers import (NORMS, CrossEntropyLoss, Dropout, FocalLoss, GroupNorm, LayerNorm, Linear,  # noqa: F401
                      WeightedCrossEntropyLoss, reseed_dropout)
 from .mlp import MLP, mlp2, mlp3  # noqa: F401
@@ -12,8 +12,8 @@ from .resnet import ResNet, resnet18  # noqa: F401
 
 # name -> (constructor, input kind for the synthetic dataset)
 REGISTRY = {
-    "enhanced_cnn": (lambda nc=10, dropout=0.0, **norm: EnhancedCNNModel(nc, dropout=dropout, **norm), "cifar10"),
-    "enhanced_cnn_small": (lambda nc=10, dropout=0.0, **norm: EnhancedCNNSmall(nc, dropout=dropout, **norm), "cifar10"),
+    "enhanced_cnn": (lambda nc=10, dropout=0.0, **kw: EnhancedCNNModel(nc, dropout=dropout, **kw), "cifar10"),
+    "enhanced_cnn_small": (lambda nc=10, dropout=0.0, **kw: EnhancedCNNSmall(nc, dropout=dropout, **kw), "cifar10"),
     "lenet5": (lambda nc=10, dropout=0.0: LeNet5(nc, dropout=dropout), "mnist"),
     "mlp2": (lambda nc=10, dropout=0.0, **norm: mlp2(784, 1024, nc, dropout=dropout, **norm), "mnist"),
     "mlp3": (lambda nc=10, dropout=0.0, **norm: mlp3(784, 4096, nc, dropout=dropout, **norm), "mnist"),
@@ -27,10 +27,12 @@ REGISTRY = {
 NORM_MODELS = ("enhanced_cnn", "enhanced_cnn_small", "resnet18", "resnet18_cifar")
 # the models that take a LayerNorm after every hidden Linear (norm="layer")
 LAYER_NORM_MODELS = ("mlp2", "mlp3", "mlp3_small")
+# the models that have a depthwise-separable variant (separable=True)
+SEPARABLE_MODELS = ("enhanced_cnn", "enhanced_cnn_small")
 
 
 def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0, norm: str = "batch",
-                gn_groups: int = 32) -> nn.Module:
+                gn_groups: int = 32, separable: bool = False) -> nn.Module:
     """``dropout``: the rate of the model's Dropout modules (MLPs: after every hidden layer; LeNet-5:
     after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist.
     ``norm``: "batch" (BatchNorm2d, the default) or "group" (GroupNorm with ``gn_groups`` groups under
@@ -38,7 +40,9 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
     no buffers); the MLPs and LeNet-5 have no normalisation layer and refuse "group".  "layer": the
     MLPs only -- a LayerNorm over the width after every hidden Linear, carrying the activation
     (``norms.{i}.weight`` / ``norms.{i}.bias`` beside the default's keys, no buffers); every other
-    model refuses it."""
+    model refuses it.
+    ``separable``: the EnhancedCNNs with every residual-block 3x3 convolution as a depthwise 3x3 followed
+    by a 1x1 (``conv1.dw.weight`` / ``conv1.pw.weight``); every other model refuses it."""
     ctor, _ = REGISTRY[name]
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
@@ -52,6 +56,11 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
             raise ValueError(f"norm='layer': LayerNorm is built for the MLPs ({', '.join(LAYER_NORM_MODELS)}), "
                              f"not for {name}")
         kw.update(norm=norm)
+    if separable:
+        if name not in SEPARABLE_MODELS:
+            raise ValueError(f"separable=True: the depthwise-separable variant is built for "
+                             f"{', '.join(SEPARABLE_MODELS)}, not for {name}")
+        kw.update(separable=True)
     return ctor(**kw) if num_classes is None else ctor(num_classes, **kw)
 
 

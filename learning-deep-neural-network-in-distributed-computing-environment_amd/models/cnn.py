@@ -31,16 +31,40 @@ class ConvBNReLU(nn.Sequential):
         return self[1].act(self[0](x), relu=True)
 
 
+class SeparableConv2d(nn.Module):
+    """A depthwise-separable 3x3 convolution: ``dw``, a per-channel 3x3 (stride, padding 1; the native
+    dwconv.hip kernels on the GPU), then ``pw``, a 1x1 to ``out_channels`` (the implicit-GEMM kernels);
+    no norm or activation between them, no biases.  in * 9 + in * out weights instead of in * out * 9."""
+
+    def __init__(self, in_channels, out_channels, stride=1):
+        super().__init__()
+        self.dw = Conv2d(in_channels, in_channels, kernel_size=3, stride=stride, padding=1, groups=in_channels,
+                         bias=False)
+        self.pw = Conv2d(in_channels, out_channels, kernel_size=1, bias=False)
+
+    def forward(self, x):
+        return self.pw(self.dw(x))
+
+
 class ResBlock(nn.Module):
     """conv3x3(stride)-BN-ReLU-conv3x3-BN + shortcut (1x1 conv + BN when the shape
     changes) -> add -> ReLU; convs without bias (BAR/model.py:52-72).  ``norm="group"``: a
-    GroupNorm under every BN's attribute name (bn1, bn2, shortcut.1)."""
+    GroupNorm under every BN's attribute name (bn1, bn2, shortcut.1).  ``separable``: conv1 and conv2
+    are ``SeparableConv2d`` (keys conv1.dw.weight / conv1.pw.weight); the shortcut conv then runs as
+    its own launch."""
 
-    def __init__(self, in_channels, out_channels, stride=1, norm: str = "batch", gn_groups: int = 32):
+    def __init__(self, in_channels, out_channels, stride=1, norm: str = "batch", gn_groups: int = 32,
+                 separable: bool = False):
         super().__init__()
-        self.conv1 = Conv2d(in_channels, out_channels, kernel_size=3, stride=stride, padding=1, bias=False)
+        if separable:
+            self.conv1 = SeparableConv2d(in_channels, out_channels, stride)
+        else:
+            self.conv1 = Conv2d(in_channels, out_channels, kernel_size=3, stride=stride, padding=1, bias=False)
         self.bn1 = make_norm(norm, out_channels, gn_groups)
-        self.conv2 = Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False)
+        if separable:
+            self.conv2 = SeparableConv2d(out_channels, out_channels)
+        else:
+            self.conv2 = Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False)
         self.bn2 = make_norm(norm, out_channels, gn_groups)
         self.shortcut = nn.Sequential()
         if stride != 1 or in_channels != out_channels:
@@ -50,18 +74,25 @@ class ResBlock(nn.Module):
             )
         self.relu = ReLU()
         self.group_norm = norm == "group"
+        self.separable = separable
         if not self.group_norm:
-            pair_conv_bn(self.conv1, self.bn1)
-            pair_conv_bn(self.conv2, self.bn2)
+            pair_conv_bn(self.conv1.pw if separable else self.conv1, self.bn1)
+            pair_conv_bn(self.conv2.pw if separable else self.conv2, self.bn2)
             if len(self.shortcut):
                 pair_conv_bn(self.shortcut[0], self.shortcut[1])
+
+    def _conv1_shortcut(self, x):
+        """(conv1(x), shortcut conv of x's twin): one launch for the dense pair, two for a separable conv1."""
+        if self.separable:
+            return self.conv1(x), self.shortcut[0](LF.shortcut_input(x))
+        return LF.conv2d_pair(x, LF.shortcut_input(x), self.conv1, self.shortcut[0])
 
     def forward(self, x):
         if self.group_norm:
             # conv -> gn(+ReLU), conv -> gn(+ residual + ReLU); the shortcut's GroupNorm output is
             # the residual of the main branch's pass.  No twins: autograd sums x's two gradients
             if len(self.shortcut):
-                c1, sc = LF.conv2d_pair(x, LF.shortcut_input(x), self.conv1, self.shortcut[0])
+                c1, sc = self._conv1_shortcut(x)
                 res = self.shortcut[1].act(sc)
             else:
                 c1, res = self.conv1(x), LF.shortcut_input(x)
@@ -72,7 +103,7 @@ class ResBlock(nn.Module):
         if len(self.shortcut):
             # the 3x3 and the 1x1 shortcut conv of x in one launch, then conv2 and both BNs, the add
             # and the ReLU in one pass
-            c1, sc = LF.conv2d_pair(x, LF.shortcut_input(x), self.conv1, self.shortcut[0])
+            c1, sc = self._conv1_shortcut(x)
             out = self.bn1.act(c1, relu=True)
             return LF.batch_norm_dual_act(self.conv2(out), self.bn2, sc, self.shortcut[1])
         out = self.bn1.act(self.conv1(x), relu=True)
@@ -90,9 +121,9 @@ def _head(x, pool, fc, drop=None):
 
 class EnhancedCNNModel(nn.Module):
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32):
+                 gn_groups: int = 32, separable: bool = False):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),
@@ -120,9 +151,9 @@ class EnhancedCNNSmall(nn.Module):
     """The reference's commented-out smaller model (BAR/model.py:4-50)."""
 
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32):
+                 gn_groups: int = 32, separable: bool = False):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),

@@ -706,18 +706,78 @@ def _layers_fuse_bn_stats() -> bool:
     return layers.FUSE_BN_STATS
 
 
+class _DwConv2dNative(torch.autograd.Function):
+    """Depthwise 3x3 / pad 1 / stride 1 or 2 convolution (groups == channels) on the dwconv.hip kernels,
+    with _Conv2dNative's contract: NHWC bf16 in and out, pad channels exactly 0, the weight gradient's
+    first write honouring flat.grad_beta, bias gradient through the colsum launches."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, flat, relu, mod):
+        C = _ext.C()
+        K = weight.shape[0]
+        w = flat.shadow_storage(weight)   # [Cp][3][3][8], the tap in element 0
+        cp = w.shape[0]
+        xb = as_nhwc(x, cp)
+        N, H, W, _ = xb.shape
+        y = torch.empty(N, (H - 1) // stride + 1, (W - 1) // stride + 1, cp, dtype=torch.bfloat16, device=x.device)
+        C.dwconv_fwd(xb, w, y, stride, flat.master_storage(bias) if bias is not None else None, relu)
+        ctx.save_for_backward(xb, y)
+        ctx.meta = (stride, flat, weight, bias, relu, K, x.dtype, mod)
+        return nchw_view(y, K)
+
+    @staticmethod
+    def backward(ctx, gy):
+        C = _ext.C()
+        xb, y = ctx.saved_tensors
+        stride, flat, weight, bias, relu, K, in_dtype, mod = ctx.meta
+        cp = y.shape[3]
+        g = as_nhwc(_to_bf16(gy), cp)
+        if relu:
+            gz = torch.empty_like(y)
+            if bias is not None:
+                C.act_bwd_colsum(g.contiguous().view(-1, cp), y.view(-1, cp), gz.view(-1, cp),
+                                 flat.grad_storage(bias), 0, flat.grad_beta(bias) != 0.0,
+                                 ws=_colsum_ws(flat, bias, cp, y.device))
+            else:
+                C.act_bwd(g.contiguous(), y, gz, 0)
+            g = gz
+        elif bias is not None:
+            C.colsum(g.contiguous().view(-1, cp), flat.grad_storage(bias), flat.grad_beta(bias) != 0.0,
+                     ws=_colsum_ws(flat, bias, cp, g.device))
+        g = g.contiguous()
+        N, H, W, _ = xb.shape
+        ws = _module_ws(mod, "_ldnn_dw_ws", C.dwconv_workspace_floats(N, H, W, cp, stride), xb.device)
+        C.dwconv_wgrad(xb, g, ws, flat.grad_storage(weight), K, flat.grad_beta(weight) != 0.0, stride)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxb = torch.empty_like(xb)
+            C.dwconv_dgrad(g, flat.shadow_storage(weight), dxb, stride)
+            dx = _from_bf16(_zpad(nchw_view(dxb, K)), in_dtype)   # (weight pad channels are zero)
+        flat.notify(weight, bias)
+        return dx, None, None, None, None, None, None
+
+
+def _depthwise3x3(mod) -> bool:
+    return (mod.groups == mod.in_channels == mod.out_channels and mod.kernel_size == (3, 3)
+            and mod.padding == (1, 1) and mod.stride in ((1, 1), (2, 2)) and mod.dilation == (1, 1))
+
+
 def conv2d(x, mod, relu: bool = False, bn=None):
     """Convolution of module `mod` (nn.Conv2d parameters).  GPU: native implicit-GEMM
-    kernels on NHWC bf16 activations and KRSC bf16 weights (groups=1, dilation=1);
+    kernels on NHWC bf16 activations and KRSC bf16 weights (groups=1, dilation=1), or the
+    depthwise 3x3 kernels (groups == channels, padding 1, stride 1 or 2);
     CPU: the fp32 reference."""
     if _ext.use_native(x):
         flat = getattr(mod, "_ldnn_flat", None)
+        if flat is not None and flat.shadow is not None and mod.groups != 1 and _depthwise3x3(mod):
+            return _zpad(_DwConv2dNative.apply(x, mod.weight, mod.bias, mod.stride[0], flat, relu, mod))
         ok = (flat is not None and flat.shadow is not None and mod.groups == 1 and mod.dilation == (1, 1)
               and mod.stride[0] == mod.stride[1] and mod.padding[0] == mod.padding[1]
               and isinstance(mod.padding, tuple))
         if not ok:
-            raise RuntimeError("native conv needs groups=1, dilation=1, square stride/padding and "
-                               "the model attached to FlatParams (ldnn.prepare(model))")
+            raise RuntimeError("native conv needs groups=1, dilation=1, square stride/padding -- or a depthwise "
+                               "3x3 (groups == in_channels == out_channels, padding 1, stride 1 or 2, "
+                               "dilation 1) -- and the model attached to FlatParams (ldnn.prepare(model))")
         # output pad channels: zero weight rows and bias entries -> exactly 0 (also after ReLU)
         return _zpad(_Conv2dNative.apply(x, mod.weight, mod.bias, mod.stride[0], mod.padding[0], flat, relu, bn))
     y = F.conv2d(x.float(), mod.weight, mod.bias, mod.stride, mod.padding, mod.dilation, mod.groups)
