@@ -121,6 +121,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "(native bandwidth kernels, dwconv.hip) followed by a 1x1 (the implicit-GEMM kernels): 7.9x "
                         "fewer parameters to aggregate, keep optimizer state for and checkpoint (enhanced_cnn "
                         "44,595,786 -> 5,662,346); every other model refuses it")
+    p.add_argument("--linear_dtype", choices=["bf16", "fp8"], default="bf16",
+                   help="fp8: the MLPs' hidden Linear layers run their three GEMMs (forward, dgrad, wgrad) on the "
+                        "gfx950 fp8 matrix instruction (gemm_f8.hip): e4m3 activations and weights, e5m2 gradients, "
+                        "per-tensor power-of-two scales taken from the current tensor on the device, fp32 accumulation; "
+                        "the backward keeps one byte per input element instead of two.  The output layer stays bf16; "
+                        "autograd path only; every other model refuses it")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
                    help="Mixup of every training batch with a permutation of itself, lam ~ Beta(ALPHA, ALPHA), one "
                         "draw per batch, in one native pass (mix.hip) that also writes the class-probability targets "
@@ -313,6 +319,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
         why = "--norm group runs on the autograd path"
     elif getattr(args, "norm", "batch") == "layer":
         why = "--norm layer runs on the autograd path"
+    elif getattr(args, "linear_dtype", "bf16") == "fp8":
+        # the static engine's layer chain is built on the bf16 kernels and their saved activations
+        why = "--linear_dtype fp8 runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -395,7 +404,10 @@ def main(argv=None):
     for flag, v in (("--mix_prob", args.mix_prob), ("--mix_switch_prob", args.mix_switch_prob)):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} must be in [0, 1], got {v}")
-    from .models import LAYER_NORM_MODELS, NORM_MODELS, SEPARABLE_MODELS
+    from .models import FP8_LINEAR_MODELS, LAYER_NORM_MODELS, NORM_MODELS, SEPARABLE_MODELS
+    if args.linear_dtype == "fp8" and args.model not in FP8_LINEAR_MODELS:
+        raise SystemExit(f"--linear_dtype fp8: the fp8 Linear is built for the hidden layers of the MLPs "
+                         f"({', '.join(FP8_LINEAR_MODELS)}), not for --model {args.model}")
     if args.separable and args.model not in SEPARABLE_MODELS:
         raise SystemExit(f"--separable: the depthwise-separable variant is built for {', '.join(SEPARABLE_MODELS)}, "
                          f"not for --model {args.model}")
@@ -436,7 +448,7 @@ def main(argv=None):
             raise SystemExit(str(e))
     try:
         model = build_model(args.model, dropout=args.dropout, norm=args.norm, gn_groups=args.gn_groups,
-                            separable=args.separable)
+                            separable=args.separable, linear_dtype=args.linear_dtype)
     except ValueError as e:   # (a --gn_groups that does not divide a width)
         raise SystemExit(str(e))
     xavier_init(model)

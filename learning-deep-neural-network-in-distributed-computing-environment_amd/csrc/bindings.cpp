@@ -1994,6 +1994,113 @@ void dwconv_wgrad(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& w
         "dwconv_wgrad");
 }
 
+// ---- fp8 Linear: src bf16 [R][C] with a unit column stride, C and the row stride multiples of 8, 16-byte
+// aligned; words fp32 [4] = {amax bits, s, 1 / s, counter}; codes dense uint8 with extents multiples of 128
+void f8_check_src(const at::Tensor& src, const at::Tensor& words, int64_t fmt, const char* who) {
+  check_dev(src, at::kBFloat16, "src");
+  check_dev(words, at::kFloat, "words");
+  const int64_t ld = ld_of(src, "src");
+  TORCH_CHECK(src.size(0) >= 1 && src.size(1) >= 8 && src.size(1) % 8 == 0 && ld % 8 == 0 && ld >= src.size(1) &&
+                  aligned16(src.data_ptr()),
+              who, ": src must be [R][C] bf16 with C and the row stride multiples of 8, 16-byte aligned, got ",
+              src.sizes(), " stride ", ld);
+  TORCH_CHECK(src.size(0) < (1ll << 31) - 128 && src.size(1) < (1ll << 31) - 128, who, ": extents must fit 32 bits");
+  TORCH_CHECK(words.is_contiguous() && words.numel() >= 4 && words.device() == src.device(), who,
+              ": words must hold 4 fp32 on src's device");
+  TORCH_CHECK(fmt == 0 || fmt == 1, who, ": fmt must be 0 (e4m3) or 1 (e5m2), got ", fmt);
+}
+
+void f8_amax(const at::Tensor& src, const at::Tensor& words, int64_t fmt) {
+  f8_check_src(src, words, fmt, "f8_amax");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
+  check(ldnn::f8_amax(bf16_ptr(src), (int)src.size(0), (int)src.size(1), src.stride(0), (int)fmt,
+                      words.data_ptr<float>(), cur_stream(src)),
+        "f8_amax");
+}
+
+int64_t f8_up128(int64_t v) { return (v + 127) / 128 * 128; }
+
+void f8_cast_transpose(const at::Tensor& src, const at::Tensor& words, int64_t fmt, const at::Tensor& out,
+                       const at::Tensor& out_t) {
+  f8_check_src(src, words, fmt, "f8_cast_transpose");
+  const int64_t R = src.size(0), C = src.size(1), Rp = f8_up128(R), Cp = f8_up128(C);
+  const bool has = out.numel() > 0, has_t = out_t.numel() > 0;
+  TORCH_CHECK(has || has_t, "f8_cast_transpose: both outputs are empty");
+  if (has) {
+    check_dev(out, at::kByte, "out");
+    TORCH_CHECK(out.dim() == 2 && out.is_contiguous() && out.size(0) == Rp && out.size(1) == Cp &&
+                    aligned16(out.data_ptr()) && out.device() == src.device(),
+                "f8_cast_transpose: out must be a dense [", Rp, "][", Cp, "] uint8 tensor, got ", out.sizes());
+  }
+  if (has_t) {
+    check_dev(out_t, at::kByte, "out_t");
+    TORCH_CHECK(out_t.dim() == 2 && out_t.is_contiguous() && out_t.size(0) == Cp && out_t.size(1) == Rp &&
+                    aligned16(out_t.data_ptr()) && out_t.device() == src.device(),
+                "f8_cast_transpose: out_t must be a dense [", Cp, "][", Rp, "] uint8 tensor, got ", out_t.sizes());
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
+  check(ldnn::f8_cast_transpose(bf16_ptr(src), (int)R, (int)C, src.stride(0), words.data_ptr<float>(), (int)fmt,
+                                has ? out.data_ptr<uint8_t>() : nullptr, has_t ? out_t.data_ptr<uint8_t>() : nullptr,
+                                (int)Rp, (int)Cp, cur_stream(src)),
+        "f8_cast_transpose");
+}
+
+// out[M][N] = epi(alpha * a8 . b8^T): a8 [>= M rows][K], b8 [>= N rows][K] padded fp8 codes (f8_cast_transpose)
+void gemm_f8(const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& out, const at::Tensor& a_words,
+             const at::Tensor& b_words, int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias,
+             double beta) {
+  check_dev(a8, at::kByte, "a8");
+  check_dev(b8, at::kByte, "b8");
+  check_dev(a_words, at::kFloat, "a_words");
+  check_dev(b_words, at::kFloat, "b_words");
+  TORCH_CHECK(out.is_cuda() && (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat),
+              "gemm_f8: out must be a bf16 or fp32 GPU tensor");
+  const bool out_f32 = out.scalar_type() == at::kFloat;
+  for (const at::Tensor* t : {&a8, &b8})
+    TORCH_CHECK(t->dim() == 2 && t->is_contiguous() && t->numel() > 0 && t->size(0) % 128 == 0 &&
+                    t->size(1) % 128 == 0 && aligned16(t->data_ptr()) && t->size(0) < (1ll << 31) &&
+                    t->size(1) < (1ll << 31),
+                "gemm_f8: operands must be dense uint8 [rows][K] with both extents multiples of 128, got ", t->sizes());
+  TORCH_CHECK(a8.size(1) == b8.size(1), "gemm_f8: inner dims differ (", a8.size(1), " vs ", b8.size(1), ")");
+  const int64_t ldc = ld_of(out, "out"), M = out.size(0), N = out.size(1);
+  TORCH_CHECK(M >= 1 && N >= 8 && M <= a8.size(0) && N <= b8.size(0), "gemm_f8: out ", out.sizes(), " exceeds the ",
+              a8.size(0), " x ", b8.size(0), " rows of the operands");
+  TORCH_CHECK(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && ldc < (1ll << 31) && aligned16(out.data_ptr()),
+              "gemm_f8: N and the row stride of out must be multiples of 8, out 16-byte aligned");
+  TORCH_CHECK(a_words.is_contiguous() && a_words.numel() >= 4 && b_words.is_contiguous() && b_words.numel() >= 4,
+              "gemm_f8: scale words hold 4 fp32 each");
+  TORCH_CHECK(a_fmt == 0 || a_fmt == 1, "gemm_f8: a_fmt must be 0 (e4m3) or 1 (e5m2), got ", a_fmt);
+  TORCH_CHECK(a8.device() == out.device() && b8.device() == out.device() && a_words.device() == out.device() &&
+                  b_words.device() == out.device(),
+              "gemm_f8: one device");
+  ldnn::GemmF8Params p{};
+  const bool bias_epi = epi == ldnn::EPI_BIAS || epi == ldnn::EPI_BIAS_RELU || epi == ldnn::EPI_BIAS_SIGMOID;
+  TORCH_CHECK(out_f32 ? epi == ldnn::EPI_NONE : (bias_epi || epi == ldnn::EPI_NONE),
+              "gemm_f8: bf16 out takes EPI_NONE / EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID, fp32 out EPI_NONE");
+  TORCH_CHECK(out_f32 || beta == 0.0, "gemm_f8: beta goes with an fp32 out");
+  if (bias_epi) {
+    TORCH_CHECK(bias.has_value(), "gemm_f8: bias epilogue needs a bias tensor");
+    check_dev(*bias, at::kFloat, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() >= N && aligned16(bias->data_ptr()) &&
+                    bias->device() == out.device(),
+                "gemm_f8: bad bias");
+    p.bias = bias->data_ptr<float>();
+  }
+  p.A = a8.data_ptr<uint8_t>();
+  p.B = b8.data_ptr<uint8_t>();
+  p.C = out.data_ptr();
+  p.a_words = a_words.data_ptr<float>();
+  p.b_words = b_words.data_ptr<float>();
+  p.M = (int)M;
+  p.N = (int)N;
+  p.K = (int)a8.size(1);
+  p.lda = p.ldb = p.K;
+  p.ldc = (int)ldc;
+  p.beta = (float)beta;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  check(ldnn::gemm_f8(p, (int)a_fmt, (int)epi, out_f32, cur_stream(out)), "gemm_f8");
+}
+
 // ---- LayerNorm: x, y, dy, dx logical [B][N] bf16 matrices with unit column stride, row strides that are
 // multiples of 8 and 16-byte aligned bases (a dense matrix with N % 8 == 0, or the [B][N] view of a padded
 // [B][ld] buffer); gamma, beta, dgamma, dbeta fp32 of at least N rounded up to 8 elements (the FlatParams
@@ -2794,6 +2901,14 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dw"), py::arg("channels"), py::arg("accumulate"), py::arg("stride"));
   m.def("dwconv_workspace_floats", &ldnn::dwconv_workspace_floats, "fp32 scratch of one dwconv_wgrad call",
         py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("stride"));
+  m.def("f8_amax", &f8_amax, "words = {amax bits, s, 1 / s} of a bf16 [R][C] matrix for fp8 format fmt (0 e4m3, 1 e5m2)",
+        py::arg("src"), py::arg("words"), py::arg("fmt"));
+  m.def("f8_cast_transpose", &f8_cast_transpose, "fp8 codes of src * words[1], row-major [Rp][Cp] and transposed "
+        "[Cp][Rp] (extents rounded up to 128, pad code 0; an empty tensor skips that output)", py::arg("src"),
+        py::arg("words"), py::arg("fmt"), py::arg("out"), py::arg("out_t"));
+  m.def("gemm_f8", &gemm_f8, "fp8 MFMA GEMM out = epi(a8 . b8^T / (s_a s_b)) over padded K-contiguous codes",
+        py::arg("a8"), py::arg("b8"), py::arg("out"), py::arg("a_words"), py::arg("b_words"), py::arg("a_fmt") = 0,
+        py::arg("epi") = 0, py::arg("bias") = py::none(), py::arg("beta") = 0.0);
   m.def("ln_fwd", &ln_fwd, "y = act(layer_norm(x)) over the rows of a [B][N] bf16 matrix; writes mean / rstd [B]",
         py::arg("x"), py::arg("y"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"),
         py::arg("eps"), py::arg("act"));

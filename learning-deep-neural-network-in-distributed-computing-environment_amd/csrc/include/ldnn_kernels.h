@@ -96,6 +96,35 @@ int gemm_pick_splitk(int M, int N, int K);
 hipError_t gemm_skinny_n(const GemmParams& p, int epi, hipStream_t s);
 constexpr size_t kOOBLimit = 0x80000000ull;
 
+// ---- fp8 Linear (quant_f8.hip, gemm_f8.hip): per-tensor power-of-two scaling, OCP e4m3fn / e5m2 ----
+// fmt: 0 = e4m3fn (max 448), 1 = e5m2 (max 57344).  words: device fp32 [4] = {amax (the bits of max |t|,
+// compared as unsigned integers: NaN > inf > finite), s = 2^e with e the largest integer such that
+// amax * 2^e <= fmt_max (e <= 126; amax == 0: s = 1; amax not finite: NaN), 1 / s, 0}.
+// src: bf16 [R][C] with row stride ld; C % 8 == 0, ld % 8 == 0, 16-byte aligned.  f8_amax writes words[0] in two
+// launches (one thread clears, the pass reduces), nothing on the host; f8_cast_transpose derives s and 1 / s
+// from it and writes them.
+hipError_t f8_amax(const uint16_t* src, int R, int C, int64_t ld, int fmt, float* words, hipStream_t s);
+// One read of src -> codes RNE(clamp(t * s)) row-major in out[Rp][Cp] and transposed in out_t[Cp][Rp]
+// (either may be nullptr); Rp / Cp: multiples of 128 >= R / C, the pad is written as code 0.
+hipError_t f8_cast_transpose(const uint16_t* src, int R, int C, int64_t ld, float* words, int fmt,
+                             uint8_t* out, uint8_t* out_t, int Rp, int Cp, hipStream_t s);
+// C[M][N] = epi(alpha * A[M][K] . B[N][K]^T), alpha = a_words[2] * b_words[2].  A / B: fp8 codes with row
+// strides lda / ldb, at least ceil128(M) / ceil128(N) rows and K % 128 == 0 (f8_cast_transpose's padded
+// outputs); A's format is a_fmt, B is e4m3.  bf16 C: epi in EPI_NONE / EPI_BIAS / EPI_BIAS_RELU /
+// EPI_BIAS_SIGMOID; fp32 C: beta * C + alpha * acc (EPI_NONE).  N % 8 == 0, ldc % 8 == 0.
+struct GemmF8Params {
+  const uint8_t* A;
+  const uint8_t* B;
+  void* C;
+  const float* bias;     // [N] fp32 (EPI_BIAS*)
+  const float* a_words;  // the operands' scale words
+  const float* b_words;
+  int M, N, K;
+  int lda, ldb, ldc;
+  float beta;
+};
+hipError_t gemm_f8(const GemmF8Params& p, int a_fmt, int epi, bool out_f32, hipStream_t s);
+
 // ---- implicit-GEMM convolution (conv.hip): NHWC activations, KRSC weights, C/K % 8 == 0
 struct ConvShape {
   int N, H, W, C;   // input (C padded to a multiple of 8)

@@ -18,19 +18,28 @@ from ..ops import functional as LF
 
 
 class Linear(nn.Linear):
-    """nn.Linear with an optional fused activation epilogue ('none'|'relu'|'sigmoid')."""
+    """nn.Linear with an optional fused activation epilogue ('none'|'relu'|'sigmoid').
+    ``compute_dtype="fp8"``: the layer's three GEMMs (forward, dgrad, wgrad) run on fp8 codes with per-tensor
+    power-of-two scales (``LF.linear_act``); parameters, keys and the optimizer's view stay those of "bf16"."""
 
-    def __init__(self, in_features, out_features, bias=True, activation: str = "none", device=None, dtype=None):
+    def __init__(self, in_features, out_features, bias=True, activation: str = "none", device=None, dtype=None,
+                 compute_dtype: str = "bf16"):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
         assert activation in LF.ACTS
+        if compute_dtype not in LF.LINEAR_DTYPES:
+            raise ValueError(f"Linear: compute_dtype must be one of {LF.LINEAR_DTYPES}, got {compute_dtype!r}")
         self.activation = activation
+        self.compute_dtype = compute_dtype
         self._ldnn_flat = None
 
     def forward(self, x):
+        if self.compute_dtype != "bf16":
+            return LF.linear_act(x, self.weight, self.bias, self.activation, self._ldnn_flat, self.compute_dtype)
         return LF.linear_act(x, self.weight, self.bias, self.activation, self._ldnn_flat)
 
     def extra_repr(self):
-        return super().extra_repr() + f", activation={self.activation}"
+        r = super().extra_repr() + f", activation={self.activation}"
+        return r if self.compute_dtype == "bf16" else r + f", compute_dtype={self.compute_dtype}"
 
 
 class ReLU(nn.ReLU):

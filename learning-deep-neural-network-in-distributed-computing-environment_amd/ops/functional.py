@@ -154,13 +154,202 @@ class _LinearActNative(torch.autograd.Function):
         return dx, None, None, None, None
 
 
-def linear_act(x, weight, bias=None, act: str = "none", flat=None):
-    """y = act(x @ W^T + b); native fused GEMM epilogue on the GPU."""
+# ------------------------------------------------------------------ fp8 Linear
+# Per-tensor current scaling with a power-of-two scale (csrc/kernels/quant_f8.hip states the recipe):
+# forward operands e4m3, the backward's incoming gradient e5m2.  name -> (kernel format id, max, torch dtype)
+FP8_FORMATS = {"e4m3": (0, 448.0, torch.float8_e4m3fn), "e5m2": (1, 57344.0, torch.float8_e5m2)}
+LINEAR_DTYPES = ("bf16", "fp8")
+
+
+def _up128(v: int) -> int:
+    return (v + 127) // 128 * 128
+
+
+def _fp8_codes(t: torch.Tensor, fmt: str):
+    """The recipe in torch ops, without a host read: (codes as a torch fp8 tensor of t's shape, amax, s, 1 / s)."""
+    _, fmax, dt = FP8_FORMATS[fmt]
+    tf = t.detach().float()
+    amax = tf.abs().max() if tf.numel() else tf.new_zeros(())
+    m, ex = torch.frexp(amax)
+    # fmt_max = 0.875 * 2^q: the largest e with amax * 2^e <= fmt_max, capped so that s and 1 / s are normal
+    q = 9 if fmt == "e4m3" else 16
+    e = (q - ex - (m > 0.875).to(ex.dtype)).clamp(max=126)
+    one = torch.ones((), dtype=torch.float32, device=tf.device)
+    ok = torch.isfinite(amax)
+    e = torch.where(ok & (amax > 0), e, torch.zeros_like(e))
+    nan = torch.full_like(one, float("nan"))
+    s = torch.where(ok, torch.ldexp(one, e), nan)
+    inv = torch.where(ok, torch.ldexp(one, -e), nan)
+    return (tf * s).clamp(-fmax, fmax).to(dt), amax, s, inv
+
+
+def fp8_quantize(t: torch.Tensor, fmt: str = "e4m3", transpose: bool = True):
+    """Quantise a [R, C] matrix for ``fp8_gemm``: ``(codes [Rp, Cp], codes_t [Cp, Rp] or None, words)``, uint8 fp8
+    codes with both extents rounded up to 128 (pad code 0) and ``words`` = fp32 [4] {amax (its bits), s, 1 / s, 0}
+    on t's device.  On the GPU (bf16, C and the row stride multiples of 8): f8_amax + f8_cast_transpose, three
+    launches and no host read; otherwise the same recipe in torch ops, which gives the same codes."""
+    R, C = t.shape
+    Rp, Cp = _up128(R), _up128(C)
+    if (_ext.use_native(t) and t.dtype == torch.bfloat16 and t.stride(1) == 1 and C % 8 == 0 and t.stride(0) % 8 == 0
+            and t.data_ptr() % 16 == 0):
+        Cn = _ext.C()
+        words = torch.empty(4, dtype=torch.float32, device=t.device)
+        codes = torch.empty(Rp, Cp, dtype=torch.uint8, device=t.device)
+        codes_t = torch.empty((Cp, Rp) if transpose else (0,), dtype=torch.uint8, device=t.device)
+        Cn.f8_amax(t, words, FP8_FORMATS[fmt][0])
+        Cn.f8_cast_transpose(t, words, FP8_FORMATS[fmt][0], codes, codes_t)
+        return codes, (codes_t if transpose else None), words
+    c, amax, s, inv = _fp8_codes(t, fmt)
+    codes = torch.zeros(Rp, Cp, dtype=torch.uint8, device=t.device)
+    codes[:R, :C] = c.view(torch.uint8)
+    words = torch.stack([amax, s, inv, torch.zeros_like(s)])
+    return codes, (codes.t().contiguous() if transpose else None), words
+
+
+def fp8_gemm(a8, b8, a_words, b_words, out, a_fmt: str = "e4m3", bias=None, act: str = "none", beta: float = 0.0):
+    """out[M, N] = act(a8 . b8^T / (s_a s_b) + bias) (bf16 out) or beta * out + a8 . b8^T / (s_a s_b) (fp32 out) over
+    ``fp8_quantize``'s padded K-contiguous codes; ``a8`` is in ``a_fmt``, ``b8`` e4m3.  On the GPU one gemm_f8
+    launch (gfx950 fp8 MFMA, fp32 accumulation); elsewhere the decoded codes in an fp32 matmul."""
     a = ACTS[act]
+    if _ext.use_native(out):
+        Cn = _ext.C()
+        if bias is None and a is not None:
+            bias = torch.zeros(out.shape[1], dtype=torch.float32, device=out.device)
+        epi = Cn.EPI_NONE if bias is None else {None: Cn.EPI_BIAS, 0: Cn.EPI_BIAS_RELU, 1: Cn.EPI_BIAS_SIGMOID}[a]
+        Cn.gemm_f8(a8, b8, out, a_words, b_words, FP8_FORMATS[a_fmt][0], epi, bias=bias, beta=beta)
+        return out
+    M, N = out.shape
+    r = (a8.view(FP8_FORMATS[a_fmt][2])[:M].float() @ b8.view(torch.float8_e4m3fn)[:N].float().t()) \
+        * (a_words[2] * b_words[2])
+    if out.dtype == torch.float32 and bias is None and a is None:
+        out.copy_(beta * out + r if beta != 0.0 else r)
+        return out
+    if bias is not None:
+        r = r + bias[:N]
+    out.copy_(F.relu(r) if a == 0 else torch.sigmoid(r) if a == 1 else r)
+    return out
+
+
+class _LinearActFp8Native(torch.autograd.Function):
+    """_LinearActNative with its three GEMMs in fp8 (gemm_f8.hip).  With both copies of every operand's codes at
+    hand each GEMM is C = A . B^T over K-contiguous operands: forward y = x8 . W8^T, dgrad dx = gz8 . Wt8^T,
+    wgrad dW = gzT8 . xT8^T.  Saved for the backward: xT8 and Wt8 (one byte per element, not the bf16 x), y, the
+    scale words.  The contract is _LinearActNative's: padded views in and out, the _ldnn_zpad mark, pad columns of
+    dW exactly 0 (pad codes are 0)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, flat):
+        C = _ext.C()
+        x = _bf16_rows(x)
+        w = flat.shadow_storage(weight)
+        npad, kpad = w.shape
+        K = weight.shape[1]
+        assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
+        x2 = x.reshape(-1, K)
+        if kpad != K:
+            zp = getattr(x, "_ldnn_zpad", False)
+            x2 = _padded_rows_view(x2, kpad)
+            if not zp:   # (as _LinearActNative: zero pad columns keep the weight gradient's pad columns 0)
+                x2.data[:, K:].zero_()
+        if x2.stride(0) % 8 or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        x8, xt8, xw = fp8_quantize(x2, "e4m3")
+        w8, wt8, ww = fp8_quantize(w, "e4m3")
+        y = torch.empty(x2.shape[0], npad, dtype=torch.bfloat16, device=x.device)
+        if bias is not None:
+            b = flat.master_storage(bias)
+        else:
+            b = torch.zeros(npad, dtype=torch.float32, device=x.device)
+        epi = {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
+        C.gemm_f8(x8, w8, y, xw, ww, 0, epi, bias=b)
+        ctx.save_for_backward(xt8, wt8, y, xw, ww)
+        ctx.act, ctx.flat, ctx.weight, ctx.bias = act, flat, weight, bias
+        ctx.xshape, ctx.x2shape = x.shape, x2.shape
+        n = weight.shape[0]
+        out = y if n == npad else y[:, :n]
+        out = out.reshape(*x.shape[:-1], n)
+        if act != 1 and n != npad and out.dim() == 2:
+            out._ldnn_zpad = True
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        C = _ext.C()
+        xt8, wt8, y, xw, ww = ctx.saved_tensors
+        flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
+        npad = y.shape[1]
+        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
+        if ctx.act is not None:
+            gz = torch.empty_like(y)
+            if bias is not None:
+                C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), ctx.act,
+                                 flat.grad_beta(bias) != 0.0)
+            else:
+                C.act_bwd(g.contiguous(), y, gz, ctx.act)
+        else:
+            gz = g.contiguous()
+            if bias is not None:
+                C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
+        gz8, gzt8, gw = fp8_quantize(gz, "e5m2")
+        # weight grad straight into the flat fp32 gradient buffer (accumulate, or overwrite as the step's first write)
+        C.gemm_f8(gzt8, xt8, flat.grad_storage(weight), gw, xw, 1, C.EPI_NONE, beta=flat.grad_beta(weight))
+        flat.notify(weight, bias)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(ctx.x2shape, dtype=torch.bfloat16, device=y.device)
+            C.gemm_f8(gz8, wt8, dx, gw, ww, 1, C.EPI_NONE)
+            K = weight.shape[1]
+            if dx.shape[1] != K:
+                dx = dx[:, :K]
+            dx = dx.reshape(ctx.xshape)
+        return dx, None, None, None, None
+
+
+class _LinearActFp8Twin(torch.autograd.Function):
+    """The fp8 Linear's recipe in torch ops (CPU, other dtypes, tensors the native path refuses): the operands are
+    rounded to bf16 as the native path holds them, quantised to the same codes, decoded, and multiplied in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.bfloat16)
+        xc, _, _, xinv = _fp8_codes(x2, "e4m3")
+        wc, _, _, winv = _fp8_codes(weight.detach().to(torch.bfloat16), "e4m3")
+        xq, wq = xc.float() * xinv, wc.float() * winv
+        y = xq @ wq.t()
+        if bias is not None:
+            y = y + bias.detach().float()
+        y = F.relu(y) if act == 0 else torch.sigmoid(y) if act == 1 else y
+        ctx.save_for_backward(xq, wq, y)
+        ctx.act, ctx.has_bias, ctx.xshape, ctx.dtypes = act, bias is not None, x.shape, (x.dtype, weight.dtype)
+        return y.reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        xq, wq, y = ctx.saved_tensors
+        g = gy.reshape(-1, gy.shape[-1]).float()
+        gz = g * (y > 0) if ctx.act == 0 else g * y * (1 - y) if ctx.act == 1 else g
+        gz = gz.to(torch.bfloat16)
+        gc, _, _, ginv = _fp8_codes(gz, "e5m2")
+        gq = gc.float() * ginv
+        dx = (gq @ wq).reshape(ctx.xshape).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+        dw = (gq.t() @ xq).to(ctx.dtypes[1])
+        db = gz.float().sum(0) if ctx.has_bias else None
+        return dx, dw, db, None
+
+
+def linear_act(x, weight, bias=None, act: str = "none", flat=None, compute_dtype: str = "bf16"):
+    """y = act(x @ W^T + b); native fused GEMM epilogue on the GPU.  ``compute_dtype="fp8"``: the three GEMMs of
+    the layer on fp8 codes (e4m3 forward operands, e5m2 gradient, per-tensor power-of-two scales)."""
+    a = ACTS[act]
+    if compute_dtype not in LINEAR_DTYPES:
+        raise ValueError(f"linear_act: compute_dtype must be one of {LINEAR_DTYPES}, got {compute_dtype!r}")
     if _ext.use_native(x):
         if flat is None or flat.shadow is None:
             raise RuntimeError("native Linear needs the model attached to FlatParams (ldnn.prepare(model))")
-        return _LinearActNative.apply(x, weight, bias, a, flat)
+        fn = _LinearActFp8Native if compute_dtype == "fp8" else _LinearActNative
+        return fn.apply(x, weight, bias, a, flat)
+    if compute_dtype == "fp8":
+        return _LinearActFp8Twin.apply(x, weight, bias, a)
     y = F.linear(x.float(), weight, bias)
     if a == 0:
         y = F.relu(y)
