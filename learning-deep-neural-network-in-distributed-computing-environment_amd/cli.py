@@ -121,11 +121,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "(native bandwidth kernels, dwconv.hip) followed by a 1x1 (the implicit-GEMM kernels): 7.9x "
                         "fewer parameters to aggregate, keep optimizer state for and checkpoint (enhanced_cnn "
                         "44,595,786 -> 5,662,346); every other model refuses it")
-    p.add_argument("--linear_dtype", choices=["bf16", "fp8"], default="bf16",
+    p.add_argument("--linear_dtype", choices=["bf16", "fp8", "mxfp8"], default="bf16",
                    help="fp8: the MLPs' hidden Linear layers run their three GEMMs (forward, dgrad, wgrad) on the "
                         "gfx950 fp8 matrix instruction (gemm_f8.hip): e4m3 activations and weights, e5m2 gradients, "
                         "per-tensor power-of-two scales taken from the current tensor on the device, fp32 accumulation; "
-                        "the backward keeps one byte per input element instead of two.  The output layer stays bf16; "
+                        "the backward keeps one byte per input element instead of two.  mxfp8: the same formats with one "
+                        "E8M0 scale per block of 32 along each GEMM's contraction dimension, fed to the block-scaled "
+                        "matrix instruction (gemm_mx8.hip); one quantisation launch per operand (quant_mx8.hip) instead "
+                        "of three, and an outlier costs precision in its own block only.  The output layer stays bf16; "
                         "autograd path only; every other model refuses it")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
                    help="Mixup of every training batch with a permutation of itself, lam ~ Beta(ALPHA, ALPHA), one "
@@ -319,9 +322,9 @@ def resolve_engine(args, model, dev, world: int) -> bool:
         why = "--norm group runs on the autograd path"
     elif getattr(args, "norm", "batch") == "layer":
         why = "--norm layer runs on the autograd path"
-    elif getattr(args, "linear_dtype", "bf16") == "fp8":
+    elif getattr(args, "linear_dtype", "bf16") != "bf16":
         # the static engine's layer chain is built on the bf16 kernels and their saved activations
-        why = "--linear_dtype fp8 runs on the autograd path"
+        why = f"--linear_dtype {args.linear_dtype} runs on the autograd path"
     if args.engine == "static" and why is not None:
         raise SystemExit(f"--engine static: {why}")
     return args.engine != "autograd" and why is None
@@ -405,8 +408,8 @@ def main(argv=None):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} must be in [0, 1], got {v}")
     from .models import FP8_LINEAR_MODELS, LAYER_NORM_MODELS, NORM_MODELS, SEPARABLE_MODELS
-    if args.linear_dtype == "fp8" and args.model not in FP8_LINEAR_MODELS:
-        raise SystemExit(f"--linear_dtype fp8: the fp8 Linear is built for the hidden layers of the MLPs "
+    if args.linear_dtype != "bf16" and args.model not in FP8_LINEAR_MODELS:
+        raise SystemExit(f"--linear_dtype {args.linear_dtype}: the fp8 Linear is built for the hidden layers of the MLPs "
                          f"({', '.join(FP8_LINEAR_MODELS)}), not for --model {args.model}")
     if args.separable and args.model not in SEPARABLE_MODELS:
         raise SystemExit(f"--separable: the depthwise-separable variant is built for {', '.join(SEPARABLE_MODELS)}, "

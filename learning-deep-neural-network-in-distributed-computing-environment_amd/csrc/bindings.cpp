@@ -2101,6 +2101,92 @@ void gemm_f8(const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& out, 
   check(ldnn::gemm_f8(p, (int)a_fmt, (int)epi, out_f32, cur_stream(out)), "gemm_f8");
 }
 
+// ---- mxfp8 Linear: mx8_quantize takes f8_cast_transpose's source; codes dense uint8 [Rp][Cp] with their scale
+// bytes [Rp][Cp / 32], the transposed pair [Cp][Rp] and [Cp][Rp / 32] (an empty pair skips that orientation)
+void mx8_check_pair(const at::Tensor& codes, const at::Tensor& scales, int64_t rows, int64_t cols,
+                    const at::Tensor& like, const char* who, const char* what) {
+  check_dev(codes, at::kByte, what);
+  check_dev(scales, at::kByte, what);
+  TORCH_CHECK(codes.dim() == 2 && codes.is_contiguous() && codes.size(0) == rows && codes.size(1) == cols &&
+                  aligned16(codes.data_ptr()) && codes.device() == like.device(),
+              who, ": ", what, " codes must be a dense [", rows, "][", cols, "] uint8 tensor, got ", codes.sizes());
+  TORCH_CHECK(scales.dim() == 2 && scales.is_contiguous() && scales.size(0) == rows && scales.size(1) == cols / 32 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0 && scales.device() == like.device(),
+              who, ": ", what, " scales must be a dense [", rows, "][", cols / 32, "] uint8 tensor, got ",
+              scales.sizes());
+}
+
+void mx8_quantize(const at::Tensor& src, int64_t fmt, const at::Tensor& out, const at::Tensor& out_s,
+                  const at::Tensor& out_t, const at::Tensor& out_ts) {
+  check_dev(src, at::kBFloat16, "src");
+  const int64_t ld = ld_of(src, "src");
+  TORCH_CHECK(src.size(0) >= 1 && src.size(1) >= 8 && src.size(1) % 8 == 0 && ld % 8 == 0 && ld >= src.size(1) &&
+                  aligned16(src.data_ptr()),
+              "mx8_quantize: src must be [R][C] bf16 with C and the row stride multiples of 8, 16-byte aligned, got ",
+              src.sizes(), " stride ", ld);
+  TORCH_CHECK(src.size(0) < (1ll << 31) - 128 && src.size(1) < (1ll << 31) - 128, "mx8_quantize: extents must fit 32 bits");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "mx8_quantize: fmt must be 0 (e4m3) or 1 (e5m2), got ", fmt);
+  const int64_t R = src.size(0), C = src.size(1), Rp = f8_up128(R), Cp = f8_up128(C);
+  const bool has = out.numel() > 0 || out_s.numel() > 0, has_t = out_t.numel() > 0 || out_ts.numel() > 0;
+  TORCH_CHECK(has || has_t, "mx8_quantize: both output pairs are empty");
+  if (has) mx8_check_pair(out, out_s, Rp, Cp, src, "mx8_quantize", "out");
+  if (has_t) mx8_check_pair(out_t, out_ts, Cp, Rp, src, "mx8_quantize", "out_t");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
+  check(ldnn::mx8_quantize(bf16_ptr(src), (int)R, (int)C, src.stride(0), (int)fmt,
+                           has ? out.data_ptr<uint8_t>() : nullptr, has ? out_s.data_ptr<uint8_t>() : nullptr,
+                           has_t ? out_t.data_ptr<uint8_t>() : nullptr, has_t ? out_ts.data_ptr<uint8_t>() : nullptr,
+                           (int)Rp, (int)Cp, cur_stream(src)),
+        "mx8_quantize");
+}
+
+// out[M][N] = epi(a8 . b8^T): a8 [>= M rows][K], b8 [>= N rows][K] padded fp8 codes with their scale bytes
+void gemm_mx8(const at::Tensor& a8, const at::Tensor& a_scales, const at::Tensor& b8, const at::Tensor& b_scales,
+              const at::Tensor& out, int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias, double beta) {
+  TORCH_CHECK(out.is_cuda() && (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat),
+              "gemm_mx8: out must be a bf16 or fp32 GPU tensor");
+  const bool out_f32 = out.scalar_type() == at::kFloat;
+  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.numel() > 0 && b8.numel() > 0 && a8.size(0) % 128 == 0 &&
+                  a8.size(1) % 128 == 0 && b8.size(0) % 128 == 0 && a8.size(0) < (1ll << 31) &&
+                  b8.size(0) < (1ll << 31) && a8.size(1) < (1ll << 31),
+              "gemm_mx8: operands must be dense uint8 [rows][K] with both extents multiples of 128, got ", a8.sizes(),
+              " and ", b8.sizes());
+  TORCH_CHECK(a8.size(1) == b8.size(1), "gemm_mx8: inner dims differ (", a8.size(1), " vs ", b8.size(1), ")");
+  mx8_check_pair(a8, a_scales, a8.size(0), a8.size(1), out, "gemm_mx8", "a8");
+  mx8_check_pair(b8, b_scales, b8.size(0), b8.size(1), out, "gemm_mx8", "b8");
+  const int64_t ldc = ld_of(out, "out"), M = out.size(0), N = out.size(1);
+  TORCH_CHECK(M >= 1 && N >= 8 && M <= a8.size(0) && N <= b8.size(0), "gemm_mx8: out ", out.sizes(), " exceeds the ",
+              a8.size(0), " x ", b8.size(0), " rows of the operands");
+  TORCH_CHECK(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && ldc < (1ll << 31) && aligned16(out.data_ptr()),
+              "gemm_mx8: N and the row stride of out must be multiples of 8, out 16-byte aligned");
+  TORCH_CHECK(a_fmt == 0 || a_fmt == 1, "gemm_mx8: a_fmt must be 0 (e4m3) or 1 (e5m2), got ", a_fmt);
+  ldnn::GemmMx8Params p{};
+  const bool bias_epi = epi == ldnn::EPI_BIAS || epi == ldnn::EPI_BIAS_RELU || epi == ldnn::EPI_BIAS_SIGMOID;
+  TORCH_CHECK(out_f32 ? epi == ldnn::EPI_NONE : (bias_epi || epi == ldnn::EPI_NONE),
+              "gemm_mx8: bf16 out takes EPI_NONE / EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID, fp32 out EPI_NONE");
+  TORCH_CHECK(out_f32 || beta == 0.0, "gemm_mx8: beta goes with an fp32 out");
+  if (bias_epi) {
+    TORCH_CHECK(bias.has_value(), "gemm_mx8: bias epilogue needs a bias tensor");
+    check_dev(*bias, at::kFloat, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() >= N && aligned16(bias->data_ptr()) &&
+                    bias->device() == out.device(),
+                "gemm_mx8: bad bias");
+    p.bias = bias->data_ptr<float>();
+  }
+  p.A = a8.data_ptr<uint8_t>();
+  p.B = b8.data_ptr<uint8_t>();
+  p.a_scales = a_scales.data_ptr<uint8_t>();
+  p.b_scales = b_scales.data_ptr<uint8_t>();
+  p.C = out.data_ptr();
+  p.M = (int)M;
+  p.N = (int)N;
+  p.K = (int)a8.size(1);
+  p.lda = p.ldb = p.K;
+  p.ldc = (int)ldc;
+  p.beta = (float)beta;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  check(ldnn::gemm_mx8(p, (int)a_fmt, (int)epi, out_f32, cur_stream(out)), "gemm_mx8");
+}
+
 // ---- LayerNorm: x, y, dy, dx logical [B][N] bf16 matrices with unit column stride, row strides that are
 // multiples of 8 and 16-byte aligned bases (a dense matrix with N % 8 == 0, or the [B][N] view of a padded
 // [B][ld] buffer); gamma, beta, dgamma, dbeta fp32 of at least N rounded up to 8 elements (the FlatParams
@@ -2909,6 +2995,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_f8", &gemm_f8, "fp8 MFMA GEMM out = epi(a8 . b8^T / (s_a s_b)) over padded K-contiguous codes",
         py::arg("a8"), py::arg("b8"), py::arg("out"), py::arg("a_words"), py::arg("b_words"), py::arg("a_fmt") = 0,
         py::arg("epi") = 0, py::arg("bias") = py::none(), py::arg("beta") = 0.0);
+  m.def("mx8_quantize", &mx8_quantize, "mxfp8 codes and E8M0 block scales (32 along the row) of src, row-major "
+        "[Rp][Cp] + [Rp][Cp / 32] and transposed [Cp][Rp] + [Cp][Rp / 32] (extents rounded up to 128, pad code 0 and "
+        "byte 127; an empty pair skips that orientation)", py::arg("src"), py::arg("fmt"), py::arg("out"),
+        py::arg("out_s"), py::arg("out_t"), py::arg("out_ts"));
+  m.def("gemm_mx8", &gemm_mx8, "block-scaled fp8 MFMA GEMM out = epi(a8 . b8^T) over padded K-contiguous codes and "
+        "their scale bytes", py::arg("a8"), py::arg("a_scales"), py::arg("b8"), py::arg("b_scales"), py::arg("out"),
+        py::arg("a_fmt") = 0, py::arg("epi") = 0, py::arg("bias") = py::none(), py::arg("beta") = 0.0);
   m.def("ln_fwd", &ln_fwd, "y = act(layer_norm(x)) over the rows of a [B][N] bf16 matrix; writes mean / rstd [B]",
         py::arg("x"), py::arg("y"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"),
         py::arg("eps"), py::arg("act"));

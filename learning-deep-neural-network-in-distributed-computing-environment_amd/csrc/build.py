@@ -104,7 +104,8 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
     # per-file additions.  optim_q.hip: no packed fp32 arithmetic (v_pk_mul_f32 / v_pk_fma_f32), so its
     # float4 expressions lower to the scalar forms the torch twin rounds like
     no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-    extra_flags = {"optim_q.hip": no_pk, "dwconv.hip": no_pk, "quant_f8.hip": no_pk, "gemm_f8.hip": no_pk}
+    extra_flags = {"optim_q.hip": no_pk, "dwconv.hip": no_pk, "quant_f8.hip": no_pk, "gemm_f8.hip": no_pk,
+                   "quant_mx8.hip": no_pk, "gemm_mx8.hip": no_pk}
     py_inc = sysconfig.get_paths()["include"]
     import pybind11
 

@@ -125,6 +125,29 @@ struct GemmF8Params {
 };
 hipError_t gemm_f8(const GemmF8Params& p, int a_fmt, int epi, bool out_f32, hipStream_t s);
 
+// ---- mxfp8 Linear (quant_mx8.hip, gemm_mx8.hip): one E8M0 scale byte per 32 elements along K ----
+// One read of src (f8_cast_transpose's source contract) -> the row-major pair out[Rp][Cp] / out_s[Rp][Cp / 32]
+// (blocks along C) and the transposed pair out_t[Cp][Rp] / out_ts[Cp][Rp / 32] (blocks along R, scales of their
+// own); either pair may be nullptr.  byte = 127 - e, e the largest integer with block amax * 2^e <= fmt_max,
+// clamped to [-127, 127]; a non-finite block: NaN codes (0x7f), byte 127; pad: code 0, byte 127.
+hipError_t mx8_quantize(const uint16_t* src, int R, int C, int64_t ld, int fmt, uint8_t* out, uint8_t* out_s,
+                        uint8_t* out_t, uint8_t* out_ts, int Rp, int Cp, hipStream_t s);
+// C[M][N] = epi(A[M][K] . B[N][K]^T) over mx8_quantize's outputs: codes with row strides lda / ldb, at least
+// ceil128(M) / ceil128(N) rows, K % 128 == 0, and dense scale arrays [rows][K / 32].  A's format is a_fmt, B is
+// e4m3.  Epilogues as gemm_f8, without alpha.
+struct GemmMx8Params {
+  const uint8_t* A;
+  const uint8_t* B;
+  const uint8_t* a_scales;
+  const uint8_t* b_scales;
+  void* C;
+  const float* bias;  // [N] fp32 (EPI_BIAS*)
+  int M, N, K;
+  int lda, ldb, ldc;
+  float beta;
+};
+hipError_t gemm_mx8(const GemmMx8Params& p, int a_fmt, int epi, bool out_f32, hipStream_t s);
+
 // ---- implicit-GEMM convolution (conv.hip): NHWC activations, KRSC weights, C/K % 8 == 0
 struct ConvShape {
   int N, H, W, C;   // input (C padded to a multiple of 8)

@@ -27,7 +27,7 @@ REGISTRY = {
 NORM_MODELS = ("enhanced_cnn", "enhanced_cnn_small", "resnet18", "resnet18_cifar")
 # the models that take a LayerNorm after every hidden Linear (norm="layer")
 LAYER_NORM_MODELS = ("mlp2", "mlp3", "mlp3_small")
-# the models whose hidden Linear layers take linear_dtype="fp8"
+# the models whose hidden Linear layers take linear_dtype="fp8" / "mxfp8"
 FP8_LINEAR_MODELS = ("mlp2", "mlp3", "mlp3_small")
 # the models that have a depthwise-separable variant (separable=True)
 SEPARABLE_MODELS = ("enhanced_cnn", "enhanced_cnn_small")
@@ -45,8 +45,9 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
     model refuses it.
     ``separable``: the EnhancedCNNs with every residual-block 3x3 convolution as a depthwise 3x3 followed
     by a 1x1 (``conv1.dw.weight`` / ``conv1.pw.weight``); every other model refuses it.
-    ``linear_dtype``: "bf16" (the default) or "fp8": the MLPs' hidden Linear layers run their three GEMMs on
-    fp8 codes (the output layer stays bf16; modules and keys are the default's); every other model refuses it."""
+    ``linear_dtype``: "bf16" (the default), "fp8" (per-tensor scales) or "mxfp8" (one scale per block of 32): the
+    MLPs' hidden Linear layers run their three GEMMs on fp8 codes (the output layer stays bf16; modules and keys are
+    the default's); every other model refuses it."""
     ctor, _ = REGISTRY[name]
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
@@ -66,10 +67,10 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
                              f"{', '.join(SEPARABLE_MODELS)}, not for {name}")
         kw.update(separable=True)
     if linear_dtype != "bf16":
-        if linear_dtype != "fp8":
-            raise ValueError(f"linear_dtype must be 'bf16' or 'fp8', got {linear_dtype!r}")
+        if linear_dtype not in ("fp8", "mxfp8"):
+            raise ValueError(f"linear_dtype must be 'bf16', 'fp8' or 'mxfp8', got {linear_dtype!r}")
         if name not in FP8_LINEAR_MODELS:
-            raise ValueError(f"linear_dtype='fp8': the fp8 Linear is built for the hidden layers of the MLPs "
+            raise ValueError(f"linear_dtype={linear_dtype!r}: the fp8 Linear is built for the hidden layers of the MLPs "
                              f"({', '.join(FP8_LINEAR_MODELS)}), not for {name}")
         kw.update(linear_dtype=linear_dtype)
     return ctor(**kw) if num_classes is None else ctor(num_classes, **kw)

@@ -20,7 +20,8 @@ from ..ops import functional as LF
 class Linear(nn.Linear):
     """nn.Linear with an optional fused activation epilogue ('none'|'relu'|'sigmoid').
     ``compute_dtype="fp8"``: the layer's three GEMMs (forward, dgrad, wgrad) run on fp8 codes with per-tensor
-    power-of-two scales (``LF.linear_act``); parameters, keys and the optimizer's view stay those of "bf16"."""
+    power-of-two scales (``LF.linear_act``), ``"mxfp8"`` with one scale per block of 32 along each GEMM's contraction
+    dimension; parameters, keys and the optimizer's view stay those of "bf16"."""
 
     def __init__(self, in_features, out_features, bias=True, activation: str = "none", device=None, dtype=None,
                  compute_dtype: str = "bf16"):

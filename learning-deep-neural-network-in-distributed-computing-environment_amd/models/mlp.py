@@ -9,8 +9,9 @@ Activations are fused into the Linear GEMM epilogue (ReLU or sigmoid, the
 two activations BASELINE.json names).  With ``norm="layer"`` every hidden
 Linear is followed by a LayerNorm over its width, which then carries the
 activation (Linear -> LayerNorm + activation -> Dropout); the default builds
-none.  With ``linear_dtype="fp8"`` the hidden Linears run their GEMMs on fp8
-codes (``layers.Linear(compute_dtype="fp8")``); modules and keys stay as they are.
+none.  With ``linear_dtype="fp8"`` or ``"mxfp8"`` the hidden Linears run their
+GEMMs on fp8 codes with per-tensor or per-block scales
+(``layers.Linear(compute_dtype=)``); modules and keys stay as they are.
 """
 from __future__ import annotations
 
@@ -23,8 +24,8 @@ class MLP(nn.Module):
     def __init__(self, in_features: int = 784, hidden=(4096, 4096), num_classes: int = 10,
                  activation: str = "relu", dropout: float = 0.0, norm: str = "batch", linear_dtype: str = "bf16"):
         super().__init__()
-        if linear_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"MLP: linear_dtype must be 'bf16' or 'fp8', got {linear_dtype!r}")
+        if linear_dtype not in ("bf16", "fp8", "mxfp8"):
+            raise ValueError(f"MLP: linear_dtype must be 'bf16', 'fp8' or 'mxfp8', got {linear_dtype!r}")
         if norm not in ("batch", "layer"):
             raise ValueError(f"MLP: norm must be 'batch' (the default: no normalisation layer) or 'layer', got {norm!r}")
         dims = [in_features, *hidden, num_classes]
@@ -33,7 +34,7 @@ class MLP(nn.Module):
         self.activation = activation
         layer_norm = norm == "layer"
         # with LayerNorm the hidden Linears hand their pre-activations on and the norm applies the activation
-        # linear_dtype="fp8": every hidden Linear runs its GEMMs in fp8; the output layer (the fused head and
+        # linear_dtype="fp8" / "mxfp8": every hidden Linear runs its GEMMs in fp8; the output layer (the fused head and
         # loss paths are built around it) stays bf16
         self.layers = nn.ModuleList(
             Linear(dims[i], dims[i + 1], activation=activation if i < len(dims) - 2 and not layer_norm else "none",

@@ -158,7 +158,7 @@ class _LinearActNative(torch.autograd.Function):
 # Per-tensor current scaling with a power-of-two scale (csrc/kernels/quant_f8.hip states the recipe):
 # forward operands e4m3, the backward's incoming gradient e5m2.  name -> (kernel format id, max, torch dtype)
 FP8_FORMATS = {"e4m3": (0, 448.0, torch.float8_e4m3fn), "e5m2": (1, 57344.0, torch.float8_e5m2)}
-LINEAR_DTYPES = ("bf16", "fp8")
+LINEAR_DTYPES = ("bf16", "fp8", "mxfp8")
 
 
 def _up128(v: int) -> int:
@@ -337,19 +337,226 @@ class _LinearActFp8Twin(torch.autograd.Function):
         return dx, dw, db, None
 
 
+# ------------------------------------------------------------------ mxfp8 Linear
+# OCP-MX style block scaling (csrc/kernels/quant_mx8.hip states the recipe): every 32 consecutive elements along
+# the contraction dimension share one E8M0 scale byte 127 - e, e the largest integer with amax * 2^e <= fmt_max.
+def _mx8_codes(t: torch.Tensor, fmt: str):
+    """The recipe in torch ops over the rows of a [R, C] matrix, without a host read: (uint8 codes [R, C], e as
+    int32 [R, ceil(C / 32)]).  A block cut by C takes its amax over the elements it has; a block that is not finite
+    is all NaN code (0x7f) with e = 0."""
+    _, fmax, dt = FP8_FORMATS[fmt]
+    tf = t.detach().float()
+    R, C = tf.shape
+    nb = -(-C // 32)
+    blk = F.pad(tf, (0, nb * 32 - C)).view(R, nb, 32)
+    amax = blk.abs().amax(dim=2)
+    m, ex = torch.frexp(amax)
+    q = 9 if fmt == "e4m3" else 16   # fmt_max = 0.875 * 2^q
+    ok = torch.isfinite(amax)
+    e = (q - ex - (m > 0.875).to(ex.dtype)).clamp(-127, 127)
+    e = torch.where(ok & (amax > 0), e, torch.zeros_like(e))
+    s = torch.ldexp(torch.ones_like(amax), e)
+    codes = (blk * s.unsqueeze(2)).clamp(-fmax, fmax).to(dt).view(torch.uint8)
+    codes = torch.where(ok.unsqueeze(2), codes, torch.full_like(codes, 0x7F))
+    return codes.view(R, nb * 32)[:, :C], e.to(torch.int32)
+
+
+def _mx8_dequant(codes: torch.Tensor, e: torch.Tensor, fmt: str) -> torch.Tensor:
+    """codes * 2^-e in fp32 (exact); ``e`` per block of 32 along the rows."""
+    return torch.ldexp(codes.contiguous().view(FP8_FORMATS[fmt][2]).float(),
+                       -e.repeat_interleave(32, dim=1)[:, :codes.shape[1]])
+
+
+def _mx8_padded(t: torch.Tensor, fmt: str):
+    R, C = t.shape
+    Rp, Cp = _up128(R), _up128(C)
+    c, e = _mx8_codes(t, fmt)
+    codes = torch.zeros(Rp, Cp, dtype=torch.uint8, device=t.device)
+    codes[:R, :C] = c
+    scales = torch.full((Rp, Cp // 32), 127, dtype=torch.uint8, device=t.device)
+    scales[:R, :e.shape[1]] = (127 - e).to(torch.uint8)
+    return codes, scales
+
+
+def _mx8_native_ok(t: torch.Tensor) -> bool:
+    return (_ext.use_native(t) and t.dtype == torch.bfloat16 and t.stride(1) == 1 and t.shape[1] % 8 == 0
+            and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _mx8_pair(rows: int, cols: int, device):
+    """Codes [rows, cols] and scale bytes [rows, cols / 32] as two views of one allocation."""
+    buf = torch.empty(rows * cols + rows * cols // 32, dtype=torch.uint8, device=device)
+    return buf[:rows * cols].view(rows, cols), buf[rows * cols:].view(rows, cols // 32)
+
+
+def mx8_quantize(t: torch.Tensor, fmt: str = "e4m3", transpose: bool = True):
+    """Quantise a [R, C] matrix for ``mx8_gemm``: ``(codes [Rp, Cp], scales [Rp, Cp / 32], codes_t [Cp, Rp],
+    scales_t [Cp, Rp / 32])`` (the last two None without ``transpose``): uint8 fp8 codes and E8M0 scale bytes, one
+    per 32 codes along the row, both extents rounded up to 128 (pad code 0, pad byte 127).  The transposed pair is
+    quantised from ``t`` with scales of its own (blocks of 32 rows of ``t``); it is not the transpose of ``codes``.
+    On the GPU (bf16, C and the row stride multiples of 8): one mx8_quantize launch and one read of ``t``; otherwise
+    the same recipe in torch ops, which gives the same bytes."""
+    R, C = t.shape
+    Rp, Cp = _up128(R), _up128(C)
+    if _mx8_native_ok(t):
+        codes, scales = _mx8_pair(Rp, Cp, t.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=t.device)
+        codes_t, scales_t = _mx8_pair(Cp, Rp, t.device) if transpose else (empty, empty)
+        _ext.C().mx8_quantize(t, FP8_FORMATS[fmt][0], codes, scales, codes_t, scales_t)
+        return (codes, scales, codes_t, scales_t) if transpose else (codes, scales, None, None)
+    codes, scales = _mx8_padded(t, fmt)
+    return (codes, scales, *_mx8_padded(t.t(), fmt)) if transpose else (codes, scales, None, None)
+
+
+def mx8_gemm(a8, a_scales, b8, b_scales, out, a_fmt: str = "e4m3", bias=None, act: str = "none", beta: float = 0.0):
+    """out[M, N] = act(a . b^T + bias) (bf16 out) or beta * out + a . b^T (fp32 out), a and b the matrices that
+    ``mx8_quantize``'s padded K-contiguous codes and scale bytes stand for; ``a8`` is in ``a_fmt``, ``b8`` e4m3.  On
+    the GPU one gemm_mx8 launch (gfx950 block-scaled fp8 MFMA, fp32 accumulation); elsewhere the decoded operands
+    in an fp32 matmul."""
+    a = ACTS[act]
+    if _ext.use_native(out):
+        Cn = _ext.C()
+        if bias is None and a is not None:
+            bias = torch.zeros(out.shape[1], dtype=torch.float32, device=out.device)
+        epi = Cn.EPI_NONE if bias is None else {None: Cn.EPI_BIAS, 0: Cn.EPI_BIAS_RELU, 1: Cn.EPI_BIAS_SIGMOID}[a]
+        Cn.gemm_mx8(a8, a_scales, b8, b_scales, out, FP8_FORMATS[a_fmt][0], epi, bias=bias, beta=beta)
+        return out
+    M, N = out.shape
+    r = _mx8_dequant(a8[:M], 127 - a_scales[:M].to(torch.int32), a_fmt) \
+        @ _mx8_dequant(b8[:N], 127 - b_scales[:N].to(torch.int32), "e4m3").t()
+    if out.dtype == torch.float32 and bias is None and a is None:
+        out.copy_(beta * out + r if beta != 0.0 else r)
+        return out
+    if bias is not None:
+        r = r + bias[:N]
+    out.copy_(F.relu(r) if a == 0 else torch.sigmoid(r) if a == 1 else r)
+    return out
+
+
+class _LinearActMx8Native(torch.autograd.Function):
+    """_LinearActFp8Native with block scales (quant_mx8.hip, gemm_mx8.hip): one mx8_quantize launch per operand
+    writes both orientations, each with the scales of the GEMM that contracts over it: forward y = x8 . W8^T
+    (blocks along K), dgrad dx = gz8 . Wt8^T (along N), wgrad dW = gzT8 . xT8^T (along the batch).  Saved for the
+    backward: the transposed codes and scales of x and W, and y.  The contract is _LinearActNative's: padded views
+    in and out, the _ldnn_zpad mark, pad columns of dW exactly 0 (pad codes are 0)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, flat):
+        C = _ext.C()
+        x = _bf16_rows(x)
+        w = flat.shadow_storage(weight)
+        npad, kpad = w.shape
+        K = weight.shape[1]
+        assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
+        x2 = x.reshape(-1, K)
+        if kpad != K:
+            zp = getattr(x, "_ldnn_zpad", False)
+            x2 = _padded_rows_view(x2, kpad)
+            if not zp:   # (as _LinearActNative: zero pad columns keep the weight gradient's pad columns 0)
+                x2.data[:, K:].zero_()
+        if x2.stride(0) % 8 or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        x8, xs, xt8, xts = mx8_quantize(x2, "e4m3")
+        w8, ws, wt8, wts = mx8_quantize(w, "e4m3")
+        y = torch.empty(x2.shape[0], npad, dtype=torch.bfloat16, device=x.device)
+        if bias is not None:
+            b = flat.master_storage(bias)
+        else:
+            b = torch.zeros(npad, dtype=torch.float32, device=x.device)
+        epi = {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
+        C.gemm_mx8(x8, xs, w8, ws, y, 0, epi, bias=b)
+        ctx.save_for_backward(xt8, xts, wt8, wts, y)
+        ctx.act, ctx.flat, ctx.weight, ctx.bias = act, flat, weight, bias
+        ctx.xshape, ctx.x2shape = x.shape, x2.shape
+        n = weight.shape[0]
+        out = y if n == npad else y[:, :n]
+        out = out.reshape(*x.shape[:-1], n)
+        if act != 1 and n != npad and out.dim() == 2:
+            out._ldnn_zpad = True
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        C = _ext.C()
+        xt8, xts, wt8, wts, y = ctx.saved_tensors
+        flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
+        npad = y.shape[1]
+        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
+        if ctx.act is not None:
+            gz = torch.empty_like(y)
+            if bias is not None:
+                C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), ctx.act,
+                                 flat.grad_beta(bias) != 0.0)
+            else:
+                C.act_bwd(g.contiguous(), y, gz, ctx.act)
+        else:
+            gz = g.contiguous()
+            if bias is not None:
+                C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
+        gz8, gzs, gzt8, gzts = mx8_quantize(gz, "e5m2")
+        # weight grad straight into the flat fp32 gradient buffer (accumulate, or overwrite as the step's first write)
+        C.gemm_mx8(gzt8, gzts, xt8, xts, flat.grad_storage(weight), 1, C.EPI_NONE, beta=flat.grad_beta(weight))
+        flat.notify(weight, bias)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(ctx.x2shape, dtype=torch.bfloat16, device=y.device)
+            C.gemm_mx8(gz8, gzs, wt8, wts, dx, 1, C.EPI_NONE)
+            K = weight.shape[1]
+            if dx.shape[1] != K:
+                dx = dx[:, :K]
+            dx = dx.reshape(ctx.xshape)
+        return dx, None, None, None, None
+
+
+class _LinearActMx8Twin(torch.autograd.Function):
+    """The mxfp8 Linear's recipe in torch ops (CPU, other dtypes, tensors the native path refuses): the operands
+    are rounded to bf16 as the native path holds them, quantised to the same codes and scale bytes in the
+    orientation of each GEMM, decoded, and multiplied in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.bfloat16)
+        w = weight.detach().to(torch.bfloat16)
+        y = _mx8_dequant(*_mx8_codes(x2, "e4m3"), "e4m3") @ _mx8_dequant(*_mx8_codes(w, "e4m3"), "e4m3").t()
+        if bias is not None:
+            y = y + bias.detach().float()
+        y = F.relu(y) if act == 0 else torch.sigmoid(y) if act == 1 else y
+        # the backward's copies: x^T in blocks along the batch, W^T in blocks along the output features
+        ctx.save_for_backward(_mx8_dequant(*_mx8_codes(x2.t(), "e4m3"), "e4m3"),
+                              _mx8_dequant(*_mx8_codes(w.t(), "e4m3"), "e4m3"), y)
+        ctx.act, ctx.has_bias, ctx.xshape, ctx.dtypes = act, bias is not None, x.shape, (x.dtype, weight.dtype)
+        return y.reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        xtq, wtq, y = ctx.saved_tensors
+        g = gy.reshape(-1, gy.shape[-1]).float()
+        gz = g * (y > 0) if ctx.act == 0 else g * y * (1 - y) if ctx.act == 1 else g
+        gz = gz.to(torch.bfloat16)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = (_mx8_dequant(*_mx8_codes(gz, "e5m2"), "e5m2") @ wtq.t()).reshape(ctx.xshape).to(ctx.dtypes[0])
+        dw = (_mx8_dequant(*_mx8_codes(gz.t(), "e5m2"), "e5m2") @ xtq.t()).to(ctx.dtypes[1])
+        db = gz.float().sum(0) if ctx.has_bias else None
+        return dx, dw, db, None
+
+
 def linear_act(x, weight, bias=None, act: str = "none", flat=None, compute_dtype: str = "bf16"):
     """y = act(x @ W^T + b); native fused GEMM epilogue on the GPU.  ``compute_dtype="fp8"``: the three GEMMs of
-    the layer on fp8 codes (e4m3 forward operands, e5m2 gradient, per-tensor power-of-two scales)."""
+    the layer on fp8 codes (e4m3 forward operands, e5m2 gradient, per-tensor power-of-two scales); ``"mxfp8"``: the
+    same formats with one E8M0 scale per block of 32 along each GEMM's contraction dimension."""
     a = ACTS[act]
     if compute_dtype not in LINEAR_DTYPES:
         raise ValueError(f"linear_act: compute_dtype must be one of {LINEAR_DTYPES}, got {compute_dtype!r}")
     if _ext.use_native(x):
         if flat is None or flat.shadow is None:
             raise RuntimeError("native Linear needs the model attached to FlatParams (ldnn.prepare(model))")
-        fn = _LinearActFp8Native if compute_dtype == "fp8" else _LinearActNative
+        fn = {"bf16": _LinearActNative, "fp8": _LinearActFp8Native, "mxfp8": _LinearActMx8Native}[compute_dtype]
         return fn.apply(x, weight, bias, a, flat)
     if compute_dtype == "fp8":
         return _LinearActFp8Twin.apply(x, weight, bias, a)
+    if compute_dtype == "mxfp8":
+        return _LinearActMx8Twin.apply(x, weight, bias, a)
     y = F.linear(x.float(), weight, bias)
     if a == 0:
         y = F.relu(y)

@@ -125,7 +125,8 @@ class StaticMLPEngine:
         if getattr(model, "norms", None):   # (a chain of GEMMs: there is no normalisation pass to run them in)
             raise ValueError("StaticMLPEngine: a norm='layer' MLP runs on the autograd path")
         if any(getattr(l, "compute_dtype", "bf16") != "bf16" for l in model.layers):   # (its chain is the bf16 kernels')
-            raise ValueError("StaticMLPEngine: a linear_dtype='fp8' MLP runs on the autograd path")
+            dt = next(l.compute_dtype for l in model.layers if getattr(l, "compute_dtype", "bf16") != "bf16")
+            raise ValueError(f"StaticMLPEngine: a linear_dtype={dt!r} MLP runs on the autograd path")
         self.device = torch.device(device or "cuda")
         if not _ext.use_native(torch.empty(0, device=self.device)):
             raise RuntimeError("StaticMLPEngine needs the native extension on a GPU")
