@@ -121,6 +121,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "(native bandwidth kernels, dwconv.hip) followed by a 1x1 (the implicit-GEMM kernels): 7.9x "
                         "fewer parameters to aggregate, keep optimizer state for and checkpoint (enhanced_cnn "
                         "44,595,786 -> 5,662,346); every other model refuses it")
+    p.add_argument("--group_width", type=int, default=1, metavar="W", choices=[1, 8, 16, 32],
+                   help="--separable: the 3x3 of every separable block mixes W neighbouring channels (a grouped "
+                        "convolution on the matrix pipe, gconv.hip) instead of none (1, depthwise, the default): "
+                        "9 (W - 1) more weights per channel (enhanced_cnn at 16: 6,569,546 parameters)")
     p.add_argument("--linear_dtype", choices=["bf16", "fp8", "mxfp8"], default="bf16",
                    help="fp8: the MLPs' hidden Linear layers run their three GEMMs (forward, dgrad, wgrad) on the "
                         "gfx950 fp8 matrix instruction (gemm_f8.hip): e4m3 activations and weights, e5m2 gradients, "
@@ -414,6 +418,9 @@ def main(argv=None):
     if args.separable and args.model not in SEPARABLE_MODELS:
         raise SystemExit(f"--separable: the depthwise-separable variant is built for {', '.join(SEPARABLE_MODELS)}, "
                          f"not for --model {args.model}")
+    if args.group_width != 1 and not args.separable:
+        raise SystemExit(f"--group_width {args.group_width}: the group width is the separable blocks' 3x3; "
+                         "give --separable as well")
     if args.norm == "layer" and args.model not in LAYER_NORM_MODELS:
         raise SystemExit(f"--norm layer: LayerNorm is built for the MLPs ({', '.join(LAYER_NORM_MODELS)}), "
                          f"not for --model {args.model}")
@@ -451,7 +458,8 @@ def main(argv=None):
             raise SystemExit(str(e))
     try:
         model = build_model(args.model, dropout=args.dropout, norm=args.norm, gn_groups=args.gn_groups,
-                            separable=args.separable, linear_dtype=args.linear_dtype)
+                            separable=args.separable, group_width=args.group_width,
+                            linear_dtype=args.linear_dtype)
     except ValueError as e:   # (a --gn_groups that does not divide a width)
         raise SystemExit(str(e))
     xavier_init(model)

@@ -1994,6 +1994,51 @@ void dwconv_wgrad(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& w
         "dwconv_wgrad");
 }
 
+// ---- grouped 3x3 conv on MFMA, padding 1, in == out == C channels in groups of gw (8, 16 or 32): activations as
+// the depthwise ones (Cp == C); w / dw the bf16 / fp32 KRSC storage [C][3][3][gw] of a [C,gw,3,3] parameter
+int64_t gc_check(const at::Tensor& x, const at::Tensor& y, const at::Tensor& w, at::ScalarType dt, int64_t stride,
+                 const char* who) {
+  dw_check(x, y, stride, who);
+  check_dev(w, dt, "w");
+  TORCH_CHECK(w.dim() == 4 && w.is_contiguous() && w.size(0) == x.size(3) && w.size(1) == 3 && w.size(2) == 3,
+              who, ": the weight storage of a grouped 3x3 kernel over ", x.size(3), " channels is [C][3][3][gw], got ",
+              w.sizes());
+  const int64_t gw = w.size(3);
+  TORCH_CHECK((gw == 8 || gw == 16 || gw == 32) && x.size(3) % gw == 0, who, ": group width ", gw, " over ", x.size(3),
+              " channels (supported: 8, 16, 32, dividing the channels)");
+  TORCH_CHECK(w.device() == x.device() && aligned16(w.data_ptr()), who, ": w on x's device, 16-byte aligned");
+  TORCH_CHECK(ldnn::gconv_workspace_floats(x.size(0), x.size(1), x.size(2), x.size(3), (int)gw, (int)stride) > 0, who,
+              ": shape too large for the kernels' 32-bit row and tile counts");
+  return gw;
+}
+
+void gconv_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& y, int64_t stride,
+               const c10::optional<at::Tensor>& bias, bool relu) {
+  const int64_t gw = gc_check(x, y, w, at::kBFloat16, stride, "gconv_fwd");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::gconv_forward(bf16_ptr(x), bf16_ptr(w), fptr_opt(bias, x.size(3), "bias", &x), relu, bf16_mut(y),
+                            x.size(0), x.size(1), x.size(2), x.size(3), (int)gw, (int)stride, cur_stream(x)),
+        "gconv_forward");
+}
+
+void gconv_dgrad(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& dx, int64_t stride) {
+  const int64_t gw = gc_check(dx, dy, w, at::kBFloat16, stride, "gconv_dgrad");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dx.device());
+  check(ldnn::gconv_dgrad(bf16_ptr(dy), bf16_ptr(w), bf16_mut(dx), dx.size(0), dx.size(1), dx.size(2), dx.size(3),
+                          (int)gw, (int)stride, cur_stream(dx)),
+        "gconv_dgrad");
+}
+
+void gconv_wgrad(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& ws, const at::Tensor& dw,
+                 bool accumulate, int64_t stride) {
+  const int64_t gw = gc_check(x, dy, dw, at::kFloat, stride, "gconv_wgrad");
+  const int64_t need = ldnn::gconv_workspace_floats(x.size(0), x.size(1), x.size(2), x.size(3), (int)gw, (int)stride);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(ldnn::gconv_wgrad(bf16_ptr(x), bf16_ptr(dy), fptr_opt(ws, need, "ws", &x, true), dw.data_ptr<float>(),
+                          accumulate, x.size(0), x.size(1), x.size(2), x.size(3), (int)gw, (int)stride, cur_stream(x)),
+        "gconv_wgrad");
+}
+
 // ---- fp8 Linear: src bf16 [R][C] with a unit column stride, C and the row stride multiples of 8, 16-byte
 // aligned; words fp32 [4] = {amax bits, s, 1 / s, counter}; codes dense uint8 with extents multiples of 128
 void f8_check_src(const at::Tensor& src, const at::Tensor& words, int64_t fmt, const char* who) {
@@ -2987,6 +3032,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dw"), py::arg("channels"), py::arg("accumulate"), py::arg("stride"));
   m.def("dwconv_workspace_floats", &ldnn::dwconv_workspace_floats, "fp32 scratch of one dwconv_wgrad call",
         py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("stride"));
+  m.def("gconv_fwd", &gconv_fwd, "grouped 3x3 / pad 1 conv (group width 8, 16 or 32, in == out channels) over dense "
+        "NHWC bf16 on MFMA: y = relu?(x * w (+ bias))", py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stride"),
+        py::arg("bias") = py::none(), py::arg("relu") = false);
+  m.def("gconv_dgrad", &gconv_dgrad, "input gradient of gconv_fwd (a gather, also at stride 2)", py::arg("dy"),
+        py::arg("w"), py::arg("dx"), py::arg("stride"));
+  m.def("gconv_wgrad", &gconv_wgrad, "weight gradient of gconv_fwd into the fp32 KRSC storage: stored, or added "
+        "(accumulate); fixed summation order", py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("dw"),
+        py::arg("accumulate"), py::arg("stride"));
+  m.def("gconv_workspace_floats", &ldnn::gconv_workspace_floats, "fp32 scratch of one gconv_wgrad call",
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("gw"), py::arg("stride"));
   m.def("f8_amax", &f8_amax, "words = {amax bits, s, 1 / s} of a bf16 [R][C] matrix for fp8 format fmt (0 e4m3, 1 e5m2)",
         py::arg("src"), py::arg("words"), py::arg("fmt"));
   m.def("f8_cast_transpose", &f8_cast_transpose, "fp8 codes of src * words[1], row-major [Rp][Cp] and transposed "

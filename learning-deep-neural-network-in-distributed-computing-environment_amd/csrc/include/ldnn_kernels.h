@@ -366,6 +366,20 @@ hipError_t dwconv_wgrad(const uint16_t* x, const uint16_t* dy, float* ws, float*
                         int64_t N, int64_t H, int64_t W, int64_t Cp, int stride, hipStream_t s);
 int64_t dwconv_workspace_floats(int64_t N, int64_t H, int64_t W, int64_t Cp, int stride);   // -1: unsupported shape
 
+// ---- Grouped 3x3 convolution on MFMA, padding 1, stride 1 or 2 (gconv.hip): in == out == C channels, group
+// width gw = C / groups in {8, 16, 32}.  x, dx [N][H][W][C] and y, dy [N][P][Q][C] dense NHWC bf16, 16-byte
+// aligned; w: the bf16 KRSC storage [C][3][3][gw] of a [C,gw,3,3] parameter; fp32 accumulation.  bias
+// (nullable, fp32 [C]) and relu: the forward epilogue.
+hipError_t gconv_forward(const uint16_t* x, const uint16_t* w, const float* bias, bool relu, uint16_t* y, int64_t N,
+                         int64_t H, int64_t W, int64_t C, int gw, int stride, hipStream_t s);
+hipError_t gconv_dgrad(const uint16_t* dy, const uint16_t* w, uint16_t* dx, int64_t N, int64_t H, int64_t W, int64_t C,
+                       int gw, int stride, hipStream_t s);
+// dw: the fp32 gradient storage [C][3][3][gw], stored or (accumulate) added onto.  ws: gconv_workspace_floats
+// fp32 of scratch (nothing to zero or keep).  No atomics: a shape has one summation order.
+hipError_t gconv_wgrad(const uint16_t* x, const uint16_t* dy, float* ws, float* dw, bool accumulate, int64_t N,
+                       int64_t H, int64_t W, int64_t C, int gw, int stride, hipStream_t s);
+int64_t gconv_workspace_floats(int64_t N, int64_t H, int64_t W, int64_t C, int gw, int stride);   // -1: unsupported
+
 // ---- GroupNorm on dense NHWC bf16 [N][P][C] (group_norm.hip), C % 8 == 0, C % G == 0
 // Statistics per (sample, group of C / G neighbouring channels), biased variance; residual add and
 // ReLU fused into the apply pass.  No atomics: a shape has one summation order.

@@ -31,10 +31,13 @@ LAYER_NORM_MODELS = ("mlp2", "mlp3", "mlp3_small")
 FP8_LINEAR_MODELS = ("mlp2", "mlp3", "mlp3_small")
 # the models that have a depthwise-separable variant (separable=True)
 SEPARABLE_MODELS = ("enhanced_cnn", "enhanced_cnn_small")
+# the group widths of a separable variant's 3x3 beside 1 (depthwise): build_model(..., group_width=)
+GROUP_WIDTHS = (8, 16, 32)
 
 
 def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0, norm: str = "batch",
-                gn_groups: int = 32, separable: bool = False, linear_dtype: str = "bf16") -> nn.Module:
+                gn_groups: int = 32, separable: bool = False, linear_dtype: str = "bf16",
+                group_width: int = 1) -> nn.Module:
     """``dropout``: the rate of the model's Dropout modules (MLPs: after every hidden layer; LeNet-5:
     after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist.
     ``norm``: "batch" (BatchNorm2d, the default) or "group" (GroupNorm with ``gn_groups`` groups under
@@ -45,6 +48,8 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
     model refuses it.
     ``separable``: the EnhancedCNNs with every residual-block 3x3 convolution as a depthwise 3x3 followed
     by a 1x1 (``conv1.dw.weight`` / ``conv1.pw.weight``); every other model refuses it.
+    ``group_width``: with ``separable``, the 3x3 mixes this many neighbouring channels (1: depthwise; 8, 16 or 32:
+    a grouped convolution, ``dw.weight`` [C, group_width, 3, 3] under the same keys).
     ``linear_dtype``: "bf16" (the default), "fp8" (per-tensor scales) or "mxfp8" (one scale per block of 32): the
     MLPs' hidden Linear layers run their three GEMMs on fp8 codes (the output layer stays bf16; modules and keys are
     the default's); every other model refuses it."""
@@ -61,6 +66,16 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
             raise ValueError(f"norm='layer': LayerNorm is built for the MLPs ({', '.join(LAYER_NORM_MODELS)}), "
                              f"not for {name}")
         kw.update(norm=norm)
+    if group_width != 1:
+        if group_width not in GROUP_WIDTHS:
+            raise ValueError(f"group_width must be 1 or one of {GROUP_WIDTHS}, got {group_width!r}")
+        if not separable:
+            raise ValueError(f"group_width={group_width}: the group width is the separable blocks' 3x3; it needs "
+                             "separable=True")
+        if name not in SEPARABLE_MODELS:
+            raise ValueError(f"group_width={group_width}: the separable variant is built for "
+                             f"{', '.join(SEPARABLE_MODELS)}, not for {name}")
+        kw.update(group_width=group_width)
     if separable:
         if name not in SEPARABLE_MODELS:
             raise ValueError(f"separable=True: the depthwise-separable variant is built for "

@@ -34,12 +34,14 @@ class ConvBNReLU(nn.Sequential):
 class SeparableConv2d(nn.Module):
     """A depthwise-separable 3x3 convolution: ``dw``, a per-channel 3x3 (stride, padding 1; the native
     dwconv.hip kernels on the GPU), then ``pw``, a 1x1 to ``out_channels`` (the implicit-GEMM kernels);
-    no norm or activation between them, no biases.  in * 9 + in * out weights instead of in * out * 9."""
+    no norm or activation between them, no biases.  in * 9 + in * out weights instead of in * out * 9.
+    ``group_width`` > 1: ``dw`` is a grouped 3x3 that mixes ``group_width`` (8, 16 or 32) neighbouring
+    channels (the gconv.hip MFMA kernels; weight [in, group_width, 3, 3]), under the same key."""
 
-    def __init__(self, in_channels, out_channels, stride=1):
+    def __init__(self, in_channels, out_channels, stride=1, group_width=1):
         super().__init__()
-        self.dw = Conv2d(in_channels, in_channels, kernel_size=3, stride=stride, padding=1, groups=in_channels,
-                         bias=False)
+        self.dw = Conv2d(in_channels, in_channels, kernel_size=3, stride=stride, padding=1,
+                         groups=in_channels // group_width, bias=False)
         self.pw = Conv2d(in_channels, out_channels, kernel_size=1, bias=False)
 
     def forward(self, x):
@@ -54,15 +56,15 @@ class ResBlock(nn.Module):
     its own launch."""
 
     def __init__(self, in_channels, out_channels, stride=1, norm: str = "batch", gn_groups: int = 32,
-                 separable: bool = False):
+                 separable: bool = False, group_width: int = 1):
         super().__init__()
         if separable:
-            self.conv1 = SeparableConv2d(in_channels, out_channels, stride)
+            self.conv1 = SeparableConv2d(in_channels, out_channels, stride, group_width)
         else:
             self.conv1 = Conv2d(in_channels, out_channels, kernel_size=3, stride=stride, padding=1, bias=False)
         self.bn1 = make_norm(norm, out_channels, gn_groups)
         if separable:
-            self.conv2 = SeparableConv2d(out_channels, out_channels)
+            self.conv2 = SeparableConv2d(out_channels, out_channels, group_width=group_width)
         else:
             self.conv2 = Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False)
         self.bn2 = make_norm(norm, out_channels, gn_groups)
@@ -121,9 +123,9 @@ def _head(x, pool, fc, drop=None):
 
 class EnhancedCNNModel(nn.Module):
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32, separable: bool = False):
+                 gn_groups: int = 32, separable: bool = False, group_width: int = 1):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),
@@ -151,9 +153,9 @@ class EnhancedCNNSmall(nn.Module):
     """The reference's commented-out smaller model (BAR/model.py:4-50)."""
 
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32, separable: bool = False):
+                 gn_groups: int = 32, separable: bool = False, group_width: int = 1):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),

@@ -1153,27 +1153,93 @@ class _DwConv2dNative(torch.autograd.Function):
         return dx, None, None, None, None, None, None
 
 
+class _GroupedConv2dNative(torch.autograd.Function):
+    """Grouped 3x3 / pad 1 / stride 1 or 2 convolution (in == out channels, group width 8, 16 or 32) on the
+    gconv.hip MFMA kernels, with _DwConv2dNative's contract: NHWC bf16 in and out, the weight gradient's
+    first write honouring flat.grad_beta, bias gradient through the colsum launches."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, flat, relu, mod):
+        C = _ext.C()
+        K = weight.shape[0]
+        w = flat.shadow_storage(weight)   # [C][3][3][gw]
+        xb = as_nhwc(x, K)
+        N, H, W, _ = xb.shape
+        y = torch.empty(N, (H - 1) // stride + 1, (W - 1) // stride + 1, K, dtype=torch.bfloat16, device=x.device)
+        C.gconv_fwd(xb, w, y, stride, flat.master_storage(bias) if bias is not None else None, relu)
+        ctx.save_for_backward(xb, y)
+        ctx.meta = (stride, flat, weight, bias, relu, K, x.dtype, mod)
+        return nchw_view(y, K)
+
+    @staticmethod
+    def backward(ctx, gy):
+        C = _ext.C()
+        xb, y = ctx.saved_tensors
+        stride, flat, weight, bias, relu, K, in_dtype, mod = ctx.meta
+        g = as_nhwc(_to_bf16(gy), K)
+        if relu:
+            gz = torch.empty_like(y)
+            if bias is not None:
+                C.act_bwd_colsum(g.contiguous().view(-1, K), y.view(-1, K), gz.view(-1, K),
+                                 flat.grad_storage(bias), 0, flat.grad_beta(bias) != 0.0,
+                                 ws=_colsum_ws(flat, bias, K, y.device))
+            else:
+                C.act_bwd(g.contiguous(), y, gz, 0)
+            g = gz
+        elif bias is not None:
+            C.colsum(g.contiguous().view(-1, K), flat.grad_storage(bias), flat.grad_beta(bias) != 0.0,
+                     ws=_colsum_ws(flat, bias, K, g.device))
+        g = g.contiguous()
+        N, H, W, _ = xb.shape
+        gw = weight.shape[1]
+        ws = _module_ws(mod, "_ldnn_gc_ws", C.gconv_workspace_floats(N, H, W, K, gw, stride), xb.device)
+        C.gconv_wgrad(xb, g, ws, flat.grad_storage(weight), flat.grad_beta(weight) != 0.0, stride)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxb = torch.empty_like(xb)
+            C.gconv_dgrad(g, flat.shadow_storage(weight), dxb, stride)
+            dx = _from_bf16(_zpad(nchw_view(dxb, K)), in_dtype)   # (C % 8 == 0: there are no pad channels)
+        flat.notify(weight, bias)
+        return dx, None, None, None, None, None, None
+
+
+GROUP_WIDTHS = (8, 16, 32)   # channels per group of the grouped 3x3 kernels (gconv.hip)
+
+
+def _same3x3(mod) -> bool:
+    return (mod.in_channels == mod.out_channels and mod.kernel_size == (3, 3) and mod.padding == (1, 1)
+            and mod.stride in ((1, 1), (2, 2)) and mod.dilation == (1, 1))
+
+
 def _depthwise3x3(mod) -> bool:
-    return (mod.groups == mod.in_channels == mod.out_channels and mod.kernel_size == (3, 3)
-            and mod.padding == (1, 1) and mod.stride in ((1, 1), (2, 2)) and mod.dilation == (1, 1))
+    return mod.groups == mod.in_channels and _same3x3(mod)
+
+
+def _grouped3x3(mod) -> bool:
+    return (mod.groups > 1 and mod.in_channels % mod.groups == 0 and mod.in_channels // mod.groups in GROUP_WIDTHS
+            and _same3x3(mod))
 
 
 def conv2d(x, mod, relu: bool = False, bn=None):
     """Convolution of module `mod` (nn.Conv2d parameters).  GPU: native implicit-GEMM
-    kernels on NHWC bf16 activations and KRSC bf16 weights (groups=1, dilation=1), or the
-    depthwise 3x3 kernels (groups == channels, padding 1, stride 1 or 2);
+    kernels on NHWC bf16 activations and KRSC bf16 weights (groups=1, dilation=1), the
+    depthwise 3x3 kernels (groups == channels, padding 1, stride 1 or 2) or the grouped 3x3 MFMA
+    kernels (in == out channels in groups of 8, 16 or 32, padding 1, stride 1 or 2);
     CPU: the fp32 reference."""
     if _ext.use_native(x):
         flat = getattr(mod, "_ldnn_flat", None)
         if flat is not None and flat.shadow is not None and mod.groups != 1 and _depthwise3x3(mod):
             return _zpad(_DwConv2dNative.apply(x, mod.weight, mod.bias, mod.stride[0], flat, relu, mod))
+        if flat is not None and flat.shadow is not None and _grouped3x3(mod):
+            return _zpad(_GroupedConv2dNative.apply(x, mod.weight, mod.bias, mod.stride[0], flat, relu, mod))
         ok = (flat is not None and flat.shadow is not None and mod.groups == 1 and mod.dilation == (1, 1)
               and mod.stride[0] == mod.stride[1] and mod.padding[0] == mod.padding[1]
               and isinstance(mod.padding, tuple))
         if not ok:
             raise RuntimeError("native conv needs groups=1, dilation=1, square stride/padding -- or a depthwise "
                                "3x3 (groups == in_channels == out_channels, padding 1, stride 1 or 2, "
-                               "dilation 1) -- and the model attached to FlatParams (ldnn.prepare(model))")
+                               "dilation 1), or a grouped 3x3 of the same kind with in_channels / groups in "
+                               f"{GROUP_WIDTHS} -- and the model attached to FlatParams (ldnn.prepare(model))")
         # output pad channels: zero weight rows and bias entries -> exactly 0 (also after ReLU)
         return _zpad(_Conv2dNative.apply(x, mod.weight, mod.bias, mod.stride[0], mod.padding[0], flat, relu, bn))
     y = F.conv2d(x.float(), mod.weight, mod.bias, mod.stride, mod.padding, mod.dilation, mod.groups)
