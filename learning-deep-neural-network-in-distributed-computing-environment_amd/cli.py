@@ -131,7 +131,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "per-tensor power-of-two scales taken from the current tensor on the device, fp32 accumulation; "
                         "the backward keeps one byte per input element instead of two.  mxfp8: the same formats with one "
                         "E8M0 scale per block of 32 along each GEMM's contraction dimension, fed to the block-scaled "
-                        "matrix instruction (gemm_mx8.hip); one quantisation launch per operand (quant_mx8.hip) instead "
+                        "matrix instruction (gemm_f8.hip, MX); one quantisation launch per operand (quant_mx8.hip) instead "
                         "of three, and an outlier costs precision in its own block only.  The output layer stays bf16; "
                         "autograd path only; every other model refuses it")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",

@@ -2041,22 +2041,26 @@ void gconv_wgrad(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& ws
 
 // ---- fp8 Linear: src bf16 [R][C] with a unit column stride, C and the row stride multiples of 8, 16-byte
 // aligned; words fp32 [4] = {amax bits, s, 1 / s, counter}; codes dense uint8 with extents multiples of 128
-void f8_check_src(const at::Tensor& src, const at::Tensor& words, int64_t fmt, const char* who) {
+void f8_check_src(const at::Tensor& src, int64_t fmt, const char* who) {
   check_dev(src, at::kBFloat16, "src");
-  check_dev(words, at::kFloat, "words");
   const int64_t ld = ld_of(src, "src");
   TORCH_CHECK(src.size(0) >= 1 && src.size(1) >= 8 && src.size(1) % 8 == 0 && ld % 8 == 0 && ld >= src.size(1) &&
                   aligned16(src.data_ptr()),
               who, ": src must be [R][C] bf16 with C and the row stride multiples of 8, 16-byte aligned, got ",
               src.sizes(), " stride ", ld);
   TORCH_CHECK(src.size(0) < (1ll << 31) - 128 && src.size(1) < (1ll << 31) - 128, who, ": extents must fit 32 bits");
-  TORCH_CHECK(words.is_contiguous() && words.numel() >= 4 && words.device() == src.device(), who,
-              ": words must hold 4 fp32 on src's device");
   TORCH_CHECK(fmt == 0 || fmt == 1, who, ": fmt must be 0 (e4m3) or 1 (e5m2), got ", fmt);
 }
 
+void f8_check_words(const at::Tensor& words, const at::Tensor& src, const char* who) {
+  check_dev(words, at::kFloat, "words");
+  TORCH_CHECK(words.is_contiguous() && words.numel() >= 4 && words.device() == src.device(), who,
+              ": words must hold 4 fp32 on src's device");
+}
+
 void f8_amax(const at::Tensor& src, const at::Tensor& words, int64_t fmt) {
-  f8_check_src(src, words, fmt, "f8_amax");
+  f8_check_src(src, fmt, "f8_amax");
+  f8_check_words(words, src, "f8_amax");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
   check(ldnn::f8_amax(bf16_ptr(src), (int)src.size(0), (int)src.size(1), src.stride(0), (int)fmt,
                       words.data_ptr<float>(), cur_stream(src)),
@@ -2067,7 +2071,8 @@ int64_t f8_up128(int64_t v) { return (v + 127) / 128 * 128; }
 
 void f8_cast_transpose(const at::Tensor& src, const at::Tensor& words, int64_t fmt, const at::Tensor& out,
                        const at::Tensor& out_t) {
-  f8_check_src(src, words, fmt, "f8_cast_transpose");
+  f8_check_src(src, fmt, "f8_cast_transpose");
+  f8_check_words(words, src, "f8_cast_transpose");
   const int64_t R = src.size(0), C = src.size(1), Rp = f8_up128(R), Cp = f8_up128(C);
   const bool has = out.numel() > 0, has_t = out_t.numel() > 0;
   TORCH_CHECK(has || has_t, "f8_cast_transpose: both outputs are empty");
@@ -2090,60 +2095,68 @@ void f8_cast_transpose(const at::Tensor& src, const at::Tensor& words, int64_t f
         "f8_cast_transpose");
 }
 
-// out[M][N] = epi(alpha * a8 . b8^T): a8 [>= M rows][K], b8 [>= N rows][K] padded fp8 codes (f8_cast_transpose)
-void gemm_f8(const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& out, const at::Tensor& a_words,
-             const at::Tensor& b_words, int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias,
-             double beta) {
+// What gemm_f8 and gemm_mx8 check and fill alike (`who` names the caller in the messages): out[M][N] over a8
+// [>= M rows][K] and b8 [>= N rows][K] padded fp8 codes.  The caller adds its scale operands.
+ldnn::GemmF8Params f8_gemm_params(const char* who, const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& out,
+                                  int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias, double beta) {
   check_dev(a8, at::kByte, "a8");
   check_dev(b8, at::kByte, "b8");
-  check_dev(a_words, at::kFloat, "a_words");
-  check_dev(b_words, at::kFloat, "b_words");
-  TORCH_CHECK(out.is_cuda() && (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat),
-              "gemm_f8: out must be a bf16 or fp32 GPU tensor");
+  TORCH_CHECK(out.is_cuda() && (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat), who,
+              ": out must be a bf16 or fp32 GPU tensor");
   const bool out_f32 = out.scalar_type() == at::kFloat;
   for (const at::Tensor* t : {&a8, &b8})
     TORCH_CHECK(t->dim() == 2 && t->is_contiguous() && t->numel() > 0 && t->size(0) % 128 == 0 &&
                     t->size(1) % 128 == 0 && aligned16(t->data_ptr()) && t->size(0) < (1ll << 31) &&
                     t->size(1) < (1ll << 31),
-                "gemm_f8: operands must be dense uint8 [rows][K] with both extents multiples of 128, got ", t->sizes());
-  TORCH_CHECK(a8.size(1) == b8.size(1), "gemm_f8: inner dims differ (", a8.size(1), " vs ", b8.size(1), ")");
+                who, ": operands must be dense uint8 [rows][K] with both extents multiples of 128, got ", t->sizes());
+  TORCH_CHECK(a8.size(1) == b8.size(1), who, ": inner dims differ (", a8.size(1), " vs ", b8.size(1), ")");
   const int64_t ldc = ld_of(out, "out"), M = out.size(0), N = out.size(1);
-  TORCH_CHECK(M >= 1 && N >= 8 && M <= a8.size(0) && N <= b8.size(0), "gemm_f8: out ", out.sizes(), " exceeds the ",
+  TORCH_CHECK(M >= 1 && N >= 8 && M <= a8.size(0) && N <= b8.size(0), who, ": out ", out.sizes(), " exceeds the ",
               a8.size(0), " x ", b8.size(0), " rows of the operands");
-  TORCH_CHECK(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && ldc < (1ll << 31) && aligned16(out.data_ptr()),
-              "gemm_f8: N and the row stride of out must be multiples of 8, out 16-byte aligned");
-  TORCH_CHECK(a_words.is_contiguous() && a_words.numel() >= 4 && b_words.is_contiguous() && b_words.numel() >= 4,
-              "gemm_f8: scale words hold 4 fp32 each");
-  TORCH_CHECK(a_fmt == 0 || a_fmt == 1, "gemm_f8: a_fmt must be 0 (e4m3) or 1 (e5m2), got ", a_fmt);
-  TORCH_CHECK(a8.device() == out.device() && b8.device() == out.device() && a_words.device() == out.device() &&
-                  b_words.device() == out.device(),
-              "gemm_f8: one device");
+  TORCH_CHECK(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && ldc < (1ll << 31) && aligned16(out.data_ptr()), who,
+              ": N and the row stride of out must be multiples of 8, out 16-byte aligned");
+  TORCH_CHECK(a_fmt == 0 || a_fmt == 1, who, ": a_fmt must be 0 (e4m3) or 1 (e5m2), got ", a_fmt);
   ldnn::GemmF8Params p{};
   const bool bias_epi = epi == ldnn::EPI_BIAS || epi == ldnn::EPI_BIAS_RELU || epi == ldnn::EPI_BIAS_SIGMOID;
-  TORCH_CHECK(out_f32 ? epi == ldnn::EPI_NONE : (bias_epi || epi == ldnn::EPI_NONE),
-              "gemm_f8: bf16 out takes EPI_NONE / EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID, fp32 out EPI_NONE");
-  TORCH_CHECK(out_f32 || beta == 0.0, "gemm_f8: beta goes with an fp32 out");
+  TORCH_CHECK(out_f32 ? epi == ldnn::EPI_NONE : (bias_epi || epi == ldnn::EPI_NONE), who,
+              ": bf16 out takes EPI_NONE / EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID, fp32 out EPI_NONE");
+  TORCH_CHECK(out_f32 || beta == 0.0, who, ": beta goes with an fp32 out");
   if (bias_epi) {
-    TORCH_CHECK(bias.has_value(), "gemm_f8: bias epilogue needs a bias tensor");
+    TORCH_CHECK(bias.has_value(), who, ": bias epilogue needs a bias tensor");
     check_dev(*bias, at::kFloat, "bias");
     TORCH_CHECK(bias->is_contiguous() && bias->numel() >= N && aligned16(bias->data_ptr()) &&
                     bias->device() == out.device(),
-                "gemm_f8: bad bias");
+                who, ": bad bias");
     p.bias = bias->data_ptr<float>();
   }
   p.A = a8.data_ptr<uint8_t>();
   p.B = b8.data_ptr<uint8_t>();
   p.C = out.data_ptr();
-  p.a_words = a_words.data_ptr<float>();
-  p.b_words = b_words.data_ptr<float>();
   p.M = (int)M;
   p.N = (int)N;
   p.K = (int)a8.size(1);
   p.lda = p.ldb = p.K;
   p.ldc = (int)ldc;
   p.beta = (float)beta;
+  return p;
+}
+
+// out[M][N] = epi(alpha * a8 . b8^T) over f8_cast_transpose's codes and the operands' scale words
+void gemm_f8(const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& out, const at::Tensor& a_words,
+             const at::Tensor& b_words, int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias,
+             double beta) {
+  ldnn::GemmF8Params p = f8_gemm_params("gemm_f8", a8, b8, out, a_fmt, epi, bias, beta);
+  check_dev(a_words, at::kFloat, "a_words");
+  check_dev(b_words, at::kFloat, "b_words");
+  TORCH_CHECK(a_words.is_contiguous() && a_words.numel() >= 4 && b_words.is_contiguous() && b_words.numel() >= 4,
+              "gemm_f8: scale words hold 4 fp32 each");
+  TORCH_CHECK(a8.device() == out.device() && b8.device() == out.device() && a_words.device() == out.device() &&
+                  b_words.device() == out.device(),
+              "gemm_f8: one device");
+  p.a_words = a_words.data_ptr<float>();
+  p.b_words = b_words.data_ptr<float>();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
-  check(ldnn::gemm_f8(p, (int)a_fmt, (int)epi, out_f32, cur_stream(out)), "gemm_f8");
+  check(ldnn::gemm_f8(p, false, (int)a_fmt, (int)epi, out.scalar_type() == at::kFloat, cur_stream(out)), "gemm_f8");
 }
 
 // ---- mxfp8 Linear: mx8_quantize takes f8_cast_transpose's source; codes dense uint8 [Rp][Cp] with their scale
@@ -2163,14 +2176,7 @@ void mx8_check_pair(const at::Tensor& codes, const at::Tensor& scales, int64_t r
 
 void mx8_quantize(const at::Tensor& src, int64_t fmt, const at::Tensor& out, const at::Tensor& out_s,
                   const at::Tensor& out_t, const at::Tensor& out_ts) {
-  check_dev(src, at::kBFloat16, "src");
-  const int64_t ld = ld_of(src, "src");
-  TORCH_CHECK(src.size(0) >= 1 && src.size(1) >= 8 && src.size(1) % 8 == 0 && ld % 8 == 0 && ld >= src.size(1) &&
-                  aligned16(src.data_ptr()),
-              "mx8_quantize: src must be [R][C] bf16 with C and the row stride multiples of 8, 16-byte aligned, got ",
-              src.sizes(), " stride ", ld);
-  TORCH_CHECK(src.size(0) < (1ll << 31) - 128 && src.size(1) < (1ll << 31) - 128, "mx8_quantize: extents must fit 32 bits");
-  TORCH_CHECK(fmt == 0 || fmt == 1, "mx8_quantize: fmt must be 0 (e4m3) or 1 (e5m2), got ", fmt);
+  f8_check_src(src, fmt, "mx8_quantize");
   const int64_t R = src.size(0), C = src.size(1), Rp = f8_up128(R), Cp = f8_up128(C);
   const bool has = out.numel() > 0 || out_s.numel() > 0, has_t = out_t.numel() > 0 || out_ts.numel() > 0;
   TORCH_CHECK(has || has_t, "mx8_quantize: both output pairs are empty");
@@ -2184,52 +2190,16 @@ void mx8_quantize(const at::Tensor& src, int64_t fmt, const at::Tensor& out, con
         "mx8_quantize");
 }
 
-// out[M][N] = epi(a8 . b8^T): a8 [>= M rows][K], b8 [>= N rows][K] padded fp8 codes with their scale bytes
+// out[M][N] = epi(a8 . b8^T) over mx8_quantize's codes with their scale bytes
 void gemm_mx8(const at::Tensor& a8, const at::Tensor& a_scales, const at::Tensor& b8, const at::Tensor& b_scales,
               const at::Tensor& out, int64_t a_fmt, int64_t epi, const c10::optional<at::Tensor>& bias, double beta) {
-  TORCH_CHECK(out.is_cuda() && (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat),
-              "gemm_mx8: out must be a bf16 or fp32 GPU tensor");
-  const bool out_f32 = out.scalar_type() == at::kFloat;
-  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.numel() > 0 && b8.numel() > 0 && a8.size(0) % 128 == 0 &&
-                  a8.size(1) % 128 == 0 && b8.size(0) % 128 == 0 && a8.size(0) < (1ll << 31) &&
-                  b8.size(0) < (1ll << 31) && a8.size(1) < (1ll << 31),
-              "gemm_mx8: operands must be dense uint8 [rows][K] with both extents multiples of 128, got ", a8.sizes(),
-              " and ", b8.sizes());
-  TORCH_CHECK(a8.size(1) == b8.size(1), "gemm_mx8: inner dims differ (", a8.size(1), " vs ", b8.size(1), ")");
+  ldnn::GemmF8Params p = f8_gemm_params("gemm_mx8", a8, b8, out, a_fmt, epi, bias, beta);
   mx8_check_pair(a8, a_scales, a8.size(0), a8.size(1), out, "gemm_mx8", "a8");
   mx8_check_pair(b8, b_scales, b8.size(0), b8.size(1), out, "gemm_mx8", "b8");
-  const int64_t ldc = ld_of(out, "out"), M = out.size(0), N = out.size(1);
-  TORCH_CHECK(M >= 1 && N >= 8 && M <= a8.size(0) && N <= b8.size(0), "gemm_mx8: out ", out.sizes(), " exceeds the ",
-              a8.size(0), " x ", b8.size(0), " rows of the operands");
-  TORCH_CHECK(N % 8 == 0 && ldc % 8 == 0 && ldc >= N && ldc < (1ll << 31) && aligned16(out.data_ptr()),
-              "gemm_mx8: N and the row stride of out must be multiples of 8, out 16-byte aligned");
-  TORCH_CHECK(a_fmt == 0 || a_fmt == 1, "gemm_mx8: a_fmt must be 0 (e4m3) or 1 (e5m2), got ", a_fmt);
-  ldnn::GemmMx8Params p{};
-  const bool bias_epi = epi == ldnn::EPI_BIAS || epi == ldnn::EPI_BIAS_RELU || epi == ldnn::EPI_BIAS_SIGMOID;
-  TORCH_CHECK(out_f32 ? epi == ldnn::EPI_NONE : (bias_epi || epi == ldnn::EPI_NONE),
-              "gemm_mx8: bf16 out takes EPI_NONE / EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID, fp32 out EPI_NONE");
-  TORCH_CHECK(out_f32 || beta == 0.0, "gemm_mx8: beta goes with an fp32 out");
-  if (bias_epi) {
-    TORCH_CHECK(bias.has_value(), "gemm_mx8: bias epilogue needs a bias tensor");
-    check_dev(*bias, at::kFloat, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() >= N && aligned16(bias->data_ptr()) &&
-                    bias->device() == out.device(),
-                "gemm_mx8: bad bias");
-    p.bias = bias->data_ptr<float>();
-  }
-  p.A = a8.data_ptr<uint8_t>();
-  p.B = b8.data_ptr<uint8_t>();
   p.a_scales = a_scales.data_ptr<uint8_t>();
   p.b_scales = b_scales.data_ptr<uint8_t>();
-  p.C = out.data_ptr();
-  p.M = (int)M;
-  p.N = (int)N;
-  p.K = (int)a8.size(1);
-  p.lda = p.ldb = p.K;
-  p.ldc = (int)ldc;
-  p.beta = (float)beta;
   c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
-  check(ldnn::gemm_mx8(p, (int)a_fmt, (int)epi, out_f32, cur_stream(out)), "gemm_mx8");
+  check(ldnn::gemm_f8(p, true, (int)a_fmt, (int)epi, out.scalar_type() == at::kFloat, cur_stream(out)), "gemm_mx8");
 }
 
 // ---- LayerNorm: x, y, dy, dx logical [B][N] bf16 matrices with unit column stride, row strides that are

@@ -105,7 +105,7 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
     # float4 expressions lower to the scalar forms the torch twin rounds like
     no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     extra_flags = {"optim_q.hip": no_pk, "dwconv.hip": no_pk, "quant_f8.hip": no_pk, "gemm_f8.hip": no_pk,
-                   "quant_mx8.hip": no_pk, "gemm_mx8.hip": no_pk, "gconv.hip": no_pk}
+                   "quant_mx8.hip": no_pk, "gconv.hip": no_pk}
     py_inc = sysconfig.get_paths()["include"]
     import pybind11
 

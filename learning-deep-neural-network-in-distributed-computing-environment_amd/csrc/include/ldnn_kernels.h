@@ -108,45 +108,33 @@ hipError_t f8_amax(const uint16_t* src, int R, int C, int64_t ld, int fmt, float
 // (either may be nullptr); Rp / Cp: multiples of 128 >= R / C, the pad is written as code 0.
 hipError_t f8_cast_transpose(const uint16_t* src, int R, int C, int64_t ld, float* words, int fmt,
                              uint8_t* out, uint8_t* out_t, int Rp, int Cp, hipStream_t s);
-// C[M][N] = epi(alpha * A[M][K] . B[N][K]^T), alpha = a_words[2] * b_words[2].  A / B: fp8 codes with row
-// strides lda / ldb, at least ceil128(M) / ceil128(N) rows and K % 128 == 0 (f8_cast_transpose's padded
-// outputs); A's format is a_fmt, B is e4m3.  bf16 C: epi in EPI_NONE / EPI_BIAS / EPI_BIAS_RELU /
-// EPI_BIAS_SIGMOID; fp32 C: beta * C + alpha * acc (EPI_NONE).  N % 8 == 0, ldc % 8 == 0.
+// C[M][N] = epi(alpha * A[M][K] . B[N][K]^T).  A / B: fp8 codes with row strides lda / ldb, at least
+// ceil128(M) / ceil128(N) rows and K % 128 == 0; A's format is a_fmt, B is e4m3.  mx = false: f8_cast_transpose's
+// padded outputs, alpha = a_words[2] * b_words[2]; mx = true: mx8_quantize's outputs with their dense scale
+// arrays [rows][K / 32], no alpha.  The pair of the scheme not taken stays null.  bf16 C: epi in EPI_NONE /
+// EPI_BIAS / EPI_BIAS_RELU / EPI_BIAS_SIGMOID; fp32 C: beta * C + alpha * acc (EPI_NONE).  N % 8 == 0, ldc % 8 == 0.
 struct GemmF8Params {
   const uint8_t* A;
   const uint8_t* B;
   void* C;
-  const float* bias;     // [N] fp32 (EPI_BIAS*)
-  const float* a_words;  // the operands' scale words
+  const float* bias;        // [N] fp32 (EPI_BIAS*)
+  const float* a_words;     // per-tensor: the operands' scale words
   const float* b_words;
+  const uint8_t* a_scales;  // mx: the operands' scale bytes
+  const uint8_t* b_scales;
   int M, N, K;
   int lda, ldb, ldc;
   float beta;
 };
-hipError_t gemm_f8(const GemmF8Params& p, int a_fmt, int epi, bool out_f32, hipStream_t s);
+hipError_t gemm_f8(const GemmF8Params& p, bool mx, int a_fmt, int epi, bool out_f32, hipStream_t s);
 
-// ---- mxfp8 Linear (quant_mx8.hip, gemm_mx8.hip): one E8M0 scale byte per 32 elements along K ----
+// ---- mxfp8 Linear (quant_mx8.hip, gemm_f8.hip with mx): one E8M0 scale byte per 32 elements along K ----
 // One read of src (f8_cast_transpose's source contract) -> the row-major pair out[Rp][Cp] / out_s[Rp][Cp / 32]
 // (blocks along C) and the transposed pair out_t[Cp][Rp] / out_ts[Cp][Rp / 32] (blocks along R, scales of their
 // own); either pair may be nullptr.  byte = 127 - e, e the largest integer with block amax * 2^e <= fmt_max,
 // clamped to [-127, 127]; a non-finite block: NaN codes (0x7f), byte 127; pad: code 0, byte 127.
 hipError_t mx8_quantize(const uint16_t* src, int R, int C, int64_t ld, int fmt, uint8_t* out, uint8_t* out_s,
                         uint8_t* out_t, uint8_t* out_ts, int Rp, int Cp, hipStream_t s);
-// C[M][N] = epi(A[M][K] . B[N][K]^T) over mx8_quantize's outputs: codes with row strides lda / ldb, at least
-// ceil128(M) / ceil128(N) rows, K % 128 == 0, and dense scale arrays [rows][K / 32].  A's format is a_fmt, B is
-// e4m3.  Epilogues as gemm_f8, without alpha.
-struct GemmMx8Params {
-  const uint8_t* A;
-  const uint8_t* B;
-  const uint8_t* a_scales;
-  const uint8_t* b_scales;
-  void* C;
-  const float* bias;  // [N] fp32 (EPI_BIAS*)
-  int M, N, K;
-  int lda, ldb, ldc;
-  float beta;
-};
-hipError_t gemm_mx8(const GemmMx8Params& p, int a_fmt, int epi, bool out_f32, hipStream_t s);
 
 // ---- implicit-GEMM convolution (conv.hip): NHWC activations, KRSC weights, C/K % 8 == 0
 struct ConvShape {

@@ -24,6 +24,7 @@
 // bytes of a row of out_t.
 #include <algorithm>
 #include "ldnn_common.h"
+#include "ldnn_f8.h"
 #include "ldnn_kernels.h"
 
 namespace ldnn {
@@ -90,22 +91,6 @@ __global__ __launch_bounds__(kAmaxThreads) void f8_amax_kernel(const bf16_t* __r
   uint32_t* w0 = reinterpret_cast<uint32_t*>(words);
   if (m > __hip_atomic_load(w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(w0, m);
 }
-
-template <int FMT>
-__device__ __forceinline__ uint32_t cvt4(float a, float b, float c, float d) {
-  int w = 0;
-  if constexpr (FMT == 0) {
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  } else {
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
-  }
-  return (uint32_t)w;
-}
-
-// (compares, not fminf / fmaxf: a NaN stays a NaN)
-__device__ __forceinline__ float clampf(float v, float mx) { return v > mx ? mx : (v < -mx ? -mx : v); }
 
 constexpr int kCtTile = 64;
 constexpr int kCtLds = 17;  // dwords per LDS row (16 + 1)

@@ -1,4 +1,4 @@
-// MXFP8 quantisation for the mxfp8 Linear (gemm_mx8.hip): OCP-MX style block scaling, OCP e4m3fn (max 448)
+// MXFP8 quantisation for the mxfp8 Linear (gemm_f8.hip with MX): OCP-MX style block scaling, OCP e4m3fn (max 448)
 // or e5m2 (max 57344) codes, one E8M0 scale byte per block of 32.
 //
 //   block = 32 consecutive elements along the contraction dimension of the GEMM that consumes the codes:
@@ -36,23 +36,11 @@
 // then walks 16 rows of tile column tr, reduces with lane tq ^ 1 to the 32-row block amax, converts down the
 // column and stores 16 bytes of an out_t row, and its scale bytes as in the row direction.
 #include "ldnn_common.h"
+#include "ldnn_f8.h"
 #include "ldnn_kernels.h"
 
 namespace ldnn {
 namespace {
-
-template <int FMT>
-__device__ __forceinline__ uint32_t mx_cvt4(float a, float b, float c, float d) {
-  int w = 0;
-  if constexpr (FMT == 0) {
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  } else {
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
-  }
-  return (uint32_t)w;
-}
 
 // amax16: the bf16 bit pattern of the block's amax (sign cleared).  Returns e; bad: the block is not finite.
 template <int FMT>
@@ -73,8 +61,7 @@ __device__ __forceinline__ u32x4 mx_codes16(const uint16_t (&v)[16], int e, bool
   u32x4 codes;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    codes[q] = mx_cvt4<FMT>(bf2f(v[4 * q]) * s, bf2f(v[4 * q + 1]) * s, bf2f(v[4 * q + 2]) * s,
-                            bf2f(v[4 * q + 3]) * s);
+    codes[q] = cvt4<FMT>(bf2f(v[4 * q]) * s, bf2f(v[4 * q + 1]) * s, bf2f(v[4 * q + 2]) * s, bf2f(v[4 * q + 3]) * s);
     if (bad) {
       uint32_t w = 0u;
 #pragma unroll

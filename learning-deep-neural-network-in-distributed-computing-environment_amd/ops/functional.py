@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import Callable, NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -80,6 +81,73 @@ def _padded_rows_view(g: torch.Tensor, npad: int, zero_pad_guaranteed: bool = Tr
     return out
 
 
+# The blocks the native Linears share (_LinearActNative on bf16 operands, _LinearActQuantNative on fp8 codes): the
+# contract is padded views in and out, the _ldnn_zpad mark, and pad columns of dW that are exactly 0.
+def _linear_x2(x, weight, kpad):
+    """The bf16 rows ``x`` as the [rows, kpad] operand of the layer's GEMMs."""
+    K = weight.shape[1]
+    assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
+    x2 = x.reshape(-1, K)
+    if kpad != K:
+        # pad columns must be 0 so the weight-gradient pad columns stay exactly 0
+        # (the producer's pad may hold e.g. sigmoid(0) = 0.5)
+        zp = getattr(x, "_ldnn_zpad", False)
+        x2 = _padded_rows_view(x2, kpad)
+        if not zp:
+            # through .data: the producer saved this buffer for its own backward and
+            # its pad columns never influence that backward (their gradient is 0)
+            x2.data[:, K:].zero_()
+    return x2
+
+
+def _bias_epi(C, act):
+    return {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
+
+
+def _linear_bias(bias, flat, npad, device):
+    """The fp32 [npad] bias storage of the forward epilogue (zeros for a layer without one)."""
+    if bias is not None:
+        return flat.master_storage(bias)
+    return torch.zeros(npad, dtype=torch.float32, device=device)
+
+
+def _linear_out(y, x, weight, act):
+    """The layer's output as a view of the padded GEMM result ``y``."""
+    n, npad = weight.shape[0], y.shape[1]
+    out = y if n == npad else y[:, :n]
+    out = out.reshape(*x.shape[:-1], n)
+    if act != 1 and n != npad and out.dim() == 2:
+        # pad rows of W and pad entries of b are exactly 0 (their gradients are), so the
+        # pad columns hold act(0) = 0: a padded consumer skips re-zeroing them
+        out._ldnn_zpad = True
+    return out
+
+
+def _linear_gz(gy, y, act, bias, flat):
+    """The gradient at the pre-activation, bf16 [rows, npad]; the bias gradient goes into its flat storage."""
+    C = _ext.C()
+    g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), y.shape[1])
+    if act is not None:
+        gz = torch.empty_like(y)
+        if bias is not None:   # activation backward + the bias gradient's column sums in one pass
+            C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), act, flat.grad_beta(bias) != 0.0)
+        else:
+            C.act_bwd(g.contiguous(), y, gz, act)
+    else:
+        gz = g.contiguous()
+        if bias is not None:
+            C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
+    return gz
+
+
+def _linear_dx(dx, weight, xshape):
+    """The padded dgrad result trimmed to the input's features, in the input's shape."""
+    K = weight.shape[1]
+    if dx.shape[1] != K:
+        dx = dx[:, :K]
+    return dx.reshape(xshape)
+
+
 class _LinearActNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, flat):
@@ -87,58 +155,23 @@ class _LinearActNative(torch.autograd.Function):
         x = _bf16_rows(x)
         w = flat.shadow_storage(weight)
         npad, kpad = w.shape
-        K = weight.shape[1]
-        assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
-        x2 = x.reshape(-1, K)
-        if kpad != K:
-            # pad columns must be 0 so the weight-gradient pad columns stay exactly 0
-            # (the producer's pad may hold e.g. sigmoid(0) = 0.5)
-            zp = getattr(x, "_ldnn_zpad", False)
-            x2 = _padded_rows_view(x2, kpad)
-            if not zp:
-                # through .data: the producer saved this buffer for its own backward and
-                # its pad columns never influence that backward (their gradient is 0)
-                x2.data[:, K:].zero_()
+        x2 = _linear_x2(x, weight, kpad)
         y = torch.empty(x2.shape[0], npad, dtype=torch.bfloat16, device=x.device)
-        if bias is not None:
-            b = flat.master_storage(bias)
-        else:
-            b = torch.zeros(npad, dtype=torch.float32, device=x.device)
-        epi = {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
         # (a split-K forward with the in-launch combine for the 64 x 512 -> 1000 classifier
         # measured slower standalone and neutral in the ResNet-18 step: removed in round 4,
         # profiles/r3s3/head_micro.jsonl)
-        C.gemm(x2, w, y, True, True, epi, bias=b)
+        C.gemm(x2, w, y, True, True, _bias_epi(C, act), bias=_linear_bias(bias, flat, npad, x.device))
         ctx.save_for_backward(x2, y)
         ctx.act, ctx.flat, ctx.weight, ctx.bias = act, flat, weight, bias
         ctx.xshape = x.shape
-        n = weight.shape[0]
-        out = y if n == npad else y[:, :n]
-        out = out.reshape(*x.shape[:-1], n)
-        if act != 1 and n != npad and out.dim() == 2:
-            # pad rows of W and pad entries of b are exactly 0 (their gradients are), so the
-            # pad columns hold act(0) = 0: a padded consumer skips re-zeroing them
-            out._ldnn_zpad = True
-        return out
+        return _linear_out(y, x, weight, act)
 
     @staticmethod
     def backward(ctx, gy):
         C = _ext.C()
         x2, y = ctx.saved_tensors
         flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
-        npad = y.shape[1]
-        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
-        if ctx.act is not None:
-            gz = torch.empty_like(y)
-            if bias is not None:   # activation backward + the bias gradient's column sums in one pass
-                C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), ctx.act,
-                                 flat.grad_beta(bias) != 0.0)
-            else:
-                C.act_bwd(g.contiguous(), y, gz, ctx.act)
-        else:
-            gz = g.contiguous()
-            if bias is not None:
-                C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
+        gz = _linear_gz(gy, y, ctx.act, bias, flat)
         # weight grad straight into the flat fp32 gradient buffer (accumulate, or
         # overwrite as the step's first write: FlatParams.grad_beta)
         C.gemm(gz, x2, flat.grad_storage(weight), False, False, beta=flat.grad_beta(weight))
@@ -147,10 +180,7 @@ class _LinearActNative(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x2.shape, dtype=torch.bfloat16, device=x2.device)
             C.gemm(gz, flat.shadow_storage(weight), dx, True, False)
-            K = weight.shape[1]
-            if dx.shape[1] != K:
-                dx = dx[:, :K]
-            dx = dx.reshape(ctx.xshape)
+            dx = _linear_dx(dx, weight, ctx.xshape)
         return dx, None, None, None, None
 
 
@@ -210,131 +240,11 @@ def fp8_gemm(a8, b8, a_words, b_words, out, a_fmt: str = "e4m3", bias=None, act:
     """out[M, N] = act(a8 . b8^T / (s_a s_b) + bias) (bf16 out) or beta * out + a8 . b8^T / (s_a s_b) (fp32 out) over
     ``fp8_quantize``'s padded K-contiguous codes; ``a8`` is in ``a_fmt``, ``b8`` e4m3.  On the GPU one gemm_f8
     launch (gfx950 fp8 MFMA, fp32 accumulation); elsewhere the decoded codes in an fp32 matmul."""
-    a = ACTS[act]
-    if _ext.use_native(out):
-        Cn = _ext.C()
-        if bias is None and a is not None:
-            bias = torch.zeros(out.shape[1], dtype=torch.float32, device=out.device)
-        epi = Cn.EPI_NONE if bias is None else {None: Cn.EPI_BIAS, 0: Cn.EPI_BIAS_RELU, 1: Cn.EPI_BIAS_SIGMOID}[a]
-        Cn.gemm_f8(a8, b8, out, a_words, b_words, FP8_FORMATS[a_fmt][0], epi, bias=bias, beta=beta)
-        return out
     M, N = out.shape
-    r = (a8.view(FP8_FORMATS[a_fmt][2])[:M].float() @ b8.view(torch.float8_e4m3fn)[:N].float().t()) \
-        * (a_words[2] * b_words[2])
-    if out.dtype == torch.float32 and bias is None and a is None:
-        out.copy_(beta * out + r if beta != 0.0 else r)
-        return out
-    if bias is not None:
-        r = r + bias[:N]
-    out.copy_(F.relu(r) if a == 0 else torch.sigmoid(r) if a == 1 else r)
-    return out
-
-
-class _LinearActFp8Native(torch.autograd.Function):
-    """_LinearActNative with its three GEMMs in fp8 (gemm_f8.hip).  With both copies of every operand's codes at
-    hand each GEMM is C = A . B^T over K-contiguous operands: forward y = x8 . W8^T, dgrad dx = gz8 . Wt8^T,
-    wgrad dW = gzT8 . xT8^T.  Saved for the backward: xT8 and Wt8 (one byte per element, not the bf16 x), y, the
-    scale words.  The contract is _LinearActNative's: padded views in and out, the _ldnn_zpad mark, pad columns of
-    dW exactly 0 (pad codes are 0)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, act, flat):
-        C = _ext.C()
-        x = _bf16_rows(x)
-        w = flat.shadow_storage(weight)
-        npad, kpad = w.shape
-        K = weight.shape[1]
-        assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
-        x2 = x.reshape(-1, K)
-        if kpad != K:
-            zp = getattr(x, "_ldnn_zpad", False)
-            x2 = _padded_rows_view(x2, kpad)
-            if not zp:   # (as _LinearActNative: zero pad columns keep the weight gradient's pad columns 0)
-                x2.data[:, K:].zero_()
-        if x2.stride(0) % 8 or x2.data_ptr() % 16:
-            x2 = x2.contiguous()
-        x8, xt8, xw = fp8_quantize(x2, "e4m3")
-        w8, wt8, ww = fp8_quantize(w, "e4m3")
-        y = torch.empty(x2.shape[0], npad, dtype=torch.bfloat16, device=x.device)
-        if bias is not None:
-            b = flat.master_storage(bias)
-        else:
-            b = torch.zeros(npad, dtype=torch.float32, device=x.device)
-        epi = {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
-        C.gemm_f8(x8, w8, y, xw, ww, 0, epi, bias=b)
-        ctx.save_for_backward(xt8, wt8, y, xw, ww)
-        ctx.act, ctx.flat, ctx.weight, ctx.bias = act, flat, weight, bias
-        ctx.xshape, ctx.x2shape = x.shape, x2.shape
-        n = weight.shape[0]
-        out = y if n == npad else y[:, :n]
-        out = out.reshape(*x.shape[:-1], n)
-        if act != 1 and n != npad and out.dim() == 2:
-            out._ldnn_zpad = True
-        return out
-
-    @staticmethod
-    def backward(ctx, gy):
-        C = _ext.C()
-        xt8, wt8, y, xw, ww = ctx.saved_tensors
-        flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
-        npad = y.shape[1]
-        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
-        if ctx.act is not None:
-            gz = torch.empty_like(y)
-            if bias is not None:
-                C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), ctx.act,
-                                 flat.grad_beta(bias) != 0.0)
-            else:
-                C.act_bwd(g.contiguous(), y, gz, ctx.act)
-        else:
-            gz = g.contiguous()
-            if bias is not None:
-                C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
-        gz8, gzt8, gw = fp8_quantize(gz, "e5m2")
-        # weight grad straight into the flat fp32 gradient buffer (accumulate, or overwrite as the step's first write)
-        C.gemm_f8(gzt8, xt8, flat.grad_storage(weight), gw, xw, 1, C.EPI_NONE, beta=flat.grad_beta(weight))
-        flat.notify(weight, bias)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(ctx.x2shape, dtype=torch.bfloat16, device=y.device)
-            C.gemm_f8(gz8, wt8, dx, gw, ww, 1, C.EPI_NONE)
-            K = weight.shape[1]
-            if dx.shape[1] != K:
-                dx = dx[:, :K]
-            dx = dx.reshape(ctx.xshape)
-        return dx, None, None, None, None
-
-
-class _LinearActFp8Twin(torch.autograd.Function):
-    """The fp8 Linear's recipe in torch ops (CPU, other dtypes, tensors the native path refuses): the operands are
-    rounded to bf16 as the native path holds them, quantised to the same codes, decoded, and multiplied in fp32."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, act):
-        x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.bfloat16)
-        xc, _, _, xinv = _fp8_codes(x2, "e4m3")
-        wc, _, _, winv = _fp8_codes(weight.detach().to(torch.bfloat16), "e4m3")
-        xq, wq = xc.float() * xinv, wc.float() * winv
-        y = xq @ wq.t()
-        if bias is not None:
-            y = y + bias.detach().float()
-        y = F.relu(y) if act == 0 else torch.sigmoid(y) if act == 1 else y
-        ctx.save_for_backward(xq, wq, y)
-        ctx.act, ctx.has_bias, ctx.xshape, ctx.dtypes = act, bias is not None, x.shape, (x.dtype, weight.dtype)
-        return y.reshape(*x.shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        xq, wq, y = ctx.saved_tensors
-        g = gy.reshape(-1, gy.shape[-1]).float()
-        gz = g * (y > 0) if ctx.act == 0 else g * y * (1 - y) if ctx.act == 1 else g
-        gz = gz.to(torch.bfloat16)
-        gc, _, _, ginv = _fp8_codes(gz, "e5m2")
-        gq = gc.float() * ginv
-        dx = (gq @ wq).reshape(ctx.xshape).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
-        dw = (gq.t() @ xq).to(ctx.dtypes[1])
-        db = gz.float().sum(0) if ctx.has_bias else None
-        return dx, dw, db, None
+    return _f8_gemm_tail(
+        _FP8, (a8, a_words), (b8, b_words), out, a_fmt, bias, act, beta,
+        lambda: (a8.view(FP8_FORMATS[a_fmt][2])[:M].float() @ b8.view(torch.float8_e4m3fn)[:N].float().t())
+        * (a_words[2] * b_words[2]))
 
 
 # ------------------------------------------------------------------ mxfp8 Linear
@@ -413,118 +323,129 @@ def mx8_gemm(a8, a_scales, b8, b_scales, out, a_fmt: str = "e4m3", bias=None, ac
     ``mx8_quantize``'s padded K-contiguous codes and scale bytes stand for; ``a8`` is in ``a_fmt``, ``b8`` e4m3.  On
     the GPU one gemm_mx8 launch (gfx950 block-scaled fp8 MFMA, fp32 accumulation); elsewhere the decoded operands
     in an fp32 matmul."""
-    a = ACTS[act]
+    M, N = out.shape
+    return _f8_gemm_tail(
+        _MX8, (a8, a_scales), (b8, b_scales), out, a_fmt, bias, act, beta,
+        lambda: _mx8_dequant(a8[:M], 127 - a_scales[:M].to(torch.int32), a_fmt)
+        @ _mx8_dequant(b8[:N], 127 - b_scales[:N].to(torch.int32), "e4m3").t())
+
+
+# ------------------------------------------------------------------ what the two fp8 schemes share
+class _F8Scheme(NamedTuple):
+    """What tells the per-tensor fp8 Linear from the block-scaled one.  An operand is ``(codes, words)`` for fp8 and
+    ``(codes, scales)`` for mxfp8."""
+    quantize: Callable   # (t [R, C], fmt) -> (operand [Rp, Cp], operand_t [Cp, Rp]), both K-contiguous for a GEMM
+    gemm: Callable       # (a, b, out, a_fmt id, epi, bias=, beta=): out = epi(a . b^T), one native launch
+    roundtrip: Callable  # (t [R, C], fmt) -> t quantised along its rows and decoded, fp32, in torch ops
+
+
+def _fp8_operands(t, fmt):
+    codes, codes_t, words = fp8_quantize(t, fmt)
+    return (codes, words), (codes_t, words)
+
+
+def _fp8_roundtrip(t, fmt):
+    codes, _, _, inv = _fp8_codes(t, fmt)
+    return codes.float() * inv
+
+
+def _mx8_operands(t, fmt):
+    codes, scales, codes_t, scales_t = mx8_quantize(t, fmt)
+    return (codes, scales), (codes_t, scales_t)
+
+
+# (the bindings are looked up at the call: the launch-count tests wrap them)
+_FP8 = _F8Scheme(_fp8_operands,
+                 lambda a, b, out, fmt, epi, **kw: _ext.C().gemm_f8(a[0], b[0], out, a[1], b[1], fmt, epi, **kw),
+                 _fp8_roundtrip)
+_MX8 = _F8Scheme(_mx8_operands,
+                 lambda a, b, out, fmt, epi, **kw: _ext.C().gemm_mx8(*a, *b, out, fmt, epi, **kw),
+                 lambda t, fmt: _mx8_dequant(*_mx8_codes(t, fmt), fmt))
+
+
+def _f8_gemm_tail(scheme, a, b, out, a_fmt, bias, act, beta, decoded):
+    """fp8_gemm and mx8_gemm behind their operands: on the GPU the scheme's launch with the epilogue ``bias`` and
+    ``act`` ask for; elsewhere ``decoded()``, the fp32 product of the decoded operands, through beta / bias / act."""
+    k = ACTS[act]
     if _ext.use_native(out):
         Cn = _ext.C()
-        if bias is None and a is not None:
+        if bias is None and k is not None:
             bias = torch.zeros(out.shape[1], dtype=torch.float32, device=out.device)
-        epi = Cn.EPI_NONE if bias is None else {None: Cn.EPI_BIAS, 0: Cn.EPI_BIAS_RELU, 1: Cn.EPI_BIAS_SIGMOID}[a]
-        Cn.gemm_mx8(a8, a_scales, b8, b_scales, out, FP8_FORMATS[a_fmt][0], epi, bias=bias, beta=beta)
+        scheme.gemm(a, b, out, FP8_FORMATS[a_fmt][0], Cn.EPI_NONE if bias is None else _bias_epi(Cn, k), bias=bias,
+                    beta=beta)
         return out
-    M, N = out.shape
-    r = _mx8_dequant(a8[:M], 127 - a_scales[:M].to(torch.int32), a_fmt) \
-        @ _mx8_dequant(b8[:N], 127 - b_scales[:N].to(torch.int32), "e4m3").t()
-    if out.dtype == torch.float32 and bias is None and a is None:
+    r = decoded()
+    if out.dtype == torch.float32 and bias is None and k is None:
         out.copy_(beta * out + r if beta != 0.0 else r)
         return out
     if bias is not None:
-        r = r + bias[:N]
-    out.copy_(F.relu(r) if a == 0 else torch.sigmoid(r) if a == 1 else r)
+        r = r + bias[:out.shape[1]]
+    out.copy_(F.relu(r) if k == 0 else torch.sigmoid(r) if k == 1 else r)
     return out
 
 
-class _LinearActMx8Native(torch.autograd.Function):
-    """_LinearActFp8Native with block scales (quant_mx8.hip, gemm_mx8.hip): one mx8_quantize launch per operand
-    writes both orientations, each with the scales of the GEMM that contracts over it: forward y = x8 . W8^T
-    (blocks along K), dgrad dx = gz8 . Wt8^T (along N), wgrad dW = gzT8 . xT8^T (along the batch).  Saved for the
-    backward: the transposed codes and scales of x and W, and y.  The contract is _LinearActNative's: padded views
-    in and out, the _ldnn_zpad mark, pad columns of dW exactly 0 (pad codes are 0)."""
+class _LinearActQuantNative(torch.autograd.Function):
+    """_LinearActNative with its three GEMMs on fp8 codes (gemm_f8.hip), per-tensor or block-scaled as ``scheme``
+    says.  With both orientations of every operand at hand each GEMM is C = A . B^T over K-contiguous operands:
+    forward y = x8 . W8^T, dgrad dx = gz8 . Wt8^T, wgrad dW = gzT8 . xT8^T; with block scales each orientation
+    carries the scales of the GEMM that contracts over it (along K, along N, along the batch).  Saved for the
+    backward: the transposed operands of x and W (one byte per element, not the bf16 x) and y.  Pad columns of dW
+    are exactly 0 because pad codes are 0."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act, flat):
+    def forward(ctx, x, weight, bias, act, flat, scheme):
         C = _ext.C()
         x = _bf16_rows(x)
         w = flat.shadow_storage(weight)
         npad, kpad = w.shape
-        K = weight.shape[1]
-        assert x.shape[-1] == K, f"Linear expects {K} input features, got {x.shape[-1]}"
-        x2 = x.reshape(-1, K)
-        if kpad != K:
-            zp = getattr(x, "_ldnn_zpad", False)
-            x2 = _padded_rows_view(x2, kpad)
-            if not zp:   # (as _LinearActNative: zero pad columns keep the weight gradient's pad columns 0)
-                x2.data[:, K:].zero_()
+        x2 = _linear_x2(x, weight, kpad)
         if x2.stride(0) % 8 or x2.data_ptr() % 16:
             x2 = x2.contiguous()
-        x8, xs, xt8, xts = mx8_quantize(x2, "e4m3")
-        w8, ws, wt8, wts = mx8_quantize(w, "e4m3")
+        x8, xt8 = scheme.quantize(x2, "e4m3")
+        w8, wt8 = scheme.quantize(w, "e4m3")
         y = torch.empty(x2.shape[0], npad, dtype=torch.bfloat16, device=x.device)
-        if bias is not None:
-            b = flat.master_storage(bias)
-        else:
-            b = torch.zeros(npad, dtype=torch.float32, device=x.device)
-        epi = {None: C.EPI_BIAS, 0: C.EPI_BIAS_RELU, 1: C.EPI_BIAS_SIGMOID}[act]
-        C.gemm_mx8(x8, xs, w8, ws, y, 0, epi, bias=b)
-        ctx.save_for_backward(xt8, xts, wt8, wts, y)
-        ctx.act, ctx.flat, ctx.weight, ctx.bias = act, flat, weight, bias
+        scheme.gemm(x8, w8, y, 0, _bias_epi(C, act), bias=_linear_bias(bias, flat, npad, x.device))
+        ctx.save_for_backward(*xt8, *wt8, y)
+        ctx.act, ctx.flat, ctx.weight, ctx.bias, ctx.scheme = act, flat, weight, bias, scheme
         ctx.xshape, ctx.x2shape = x.shape, x2.shape
-        n = weight.shape[0]
-        out = y if n == npad else y[:, :n]
-        out = out.reshape(*x.shape[:-1], n)
-        if act != 1 and n != npad and out.dim() == 2:
-            out._ldnn_zpad = True
-        return out
+        return _linear_out(y, x, weight, act)
 
     @staticmethod
     def backward(ctx, gy):
         C = _ext.C()
-        xt8, xts, wt8, wts, y = ctx.saved_tensors
-        flat, weight, bias = ctx.flat, ctx.weight, ctx.bias
-        npad = y.shape[1]
-        g = _padded_rows_view(_bf16_rows(gy.reshape(-1, gy.shape[-1])), npad)
-        if ctx.act is not None:
-            gz = torch.empty_like(y)
-            if bias is not None:
-                C.act_bwd_colsum(g.contiguous(), y, gz, flat.grad_storage(bias), ctx.act,
-                                 flat.grad_beta(bias) != 0.0)
-            else:
-                C.act_bwd(g.contiguous(), y, gz, ctx.act)
-        else:
-            gz = g.contiguous()
-            if bias is not None:
-                C.colsum(gz, flat.grad_storage(bias), flat.grad_beta(bias) != 0.0)
-        gz8, gzs, gzt8, gzts = mx8_quantize(gz, "e5m2")
+        *ops, y = ctx.saved_tensors
+        xt8, wt8 = ops[:2], ops[2:]
+        flat, weight, bias, scheme = ctx.flat, ctx.weight, ctx.bias, ctx.scheme
+        gz8, gzt8 = scheme.quantize(_linear_gz(gy, y, ctx.act, bias, flat), "e5m2")
         # weight grad straight into the flat fp32 gradient buffer (accumulate, or overwrite as the step's first write)
-        C.gemm_mx8(gzt8, gzts, xt8, xts, flat.grad_storage(weight), 1, C.EPI_NONE, beta=flat.grad_beta(weight))
+        scheme.gemm(gzt8, xt8, flat.grad_storage(weight), 1, C.EPI_NONE, beta=flat.grad_beta(weight))
         flat.notify(weight, bias)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(ctx.x2shape, dtype=torch.bfloat16, device=y.device)
-            C.gemm_mx8(gz8, gzs, wt8, wts, dx, 1, C.EPI_NONE)
-            K = weight.shape[1]
-            if dx.shape[1] != K:
-                dx = dx[:, :K]
-            dx = dx.reshape(ctx.xshape)
-        return dx, None, None, None, None
+            scheme.gemm(gz8, wt8, dx, 1, C.EPI_NONE)
+            dx = _linear_dx(dx, weight, ctx.xshape)
+        return dx, None, None, None, None, None
 
 
-class _LinearActMx8Twin(torch.autograd.Function):
-    """The mxfp8 Linear's recipe in torch ops (CPU, other dtypes, tensors the native path refuses): the operands
-    are rounded to bf16 as the native path holds them, quantised to the same codes and scale bytes in the
-    orientation of each GEMM, decoded, and multiplied in fp32."""
+class _LinearActQuantTwin(torch.autograd.Function):
+    """The fp8 and mxfp8 Linears' recipe in torch ops (CPU, other dtypes, tensors the native path refuses): the
+    operands are rounded to bf16 as the native path holds them, quantised to the same codes (and scale bytes) in
+    the orientation of each GEMM, decoded, and multiplied in fp32.  (Per-tensor, the decoded transpose is the
+    transpose of the decoded matrix.)"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act):
+    def forward(ctx, x, weight, bias, act, roundtrip):
         x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.bfloat16)
         w = weight.detach().to(torch.bfloat16)
-        y = _mx8_dequant(*_mx8_codes(x2, "e4m3"), "e4m3") @ _mx8_dequant(*_mx8_codes(w, "e4m3"), "e4m3").t()
+        y = roundtrip(x2, "e4m3") @ roundtrip(w, "e4m3").t()
         if bias is not None:
             y = y + bias.detach().float()
         y = F.relu(y) if act == 0 else torch.sigmoid(y) if act == 1 else y
         # the backward's copies: x^T in blocks along the batch, W^T in blocks along the output features
-        ctx.save_for_backward(_mx8_dequant(*_mx8_codes(x2.t(), "e4m3"), "e4m3"),
-                              _mx8_dequant(*_mx8_codes(w.t(), "e4m3"), "e4m3"), y)
+        ctx.save_for_backward(roundtrip(x2.t(), "e4m3"), roundtrip(w.t(), "e4m3"), y)
         ctx.act, ctx.has_bias, ctx.xshape, ctx.dtypes = act, bias is not None, x.shape, (x.dtype, weight.dtype)
+        ctx.roundtrip = roundtrip
         return y.reshape(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
@@ -535,10 +456,10 @@ class _LinearActMx8Twin(torch.autograd.Function):
         gz = gz.to(torch.bfloat16)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = (_mx8_dequant(*_mx8_codes(gz, "e5m2"), "e5m2") @ wtq.t()).reshape(ctx.xshape).to(ctx.dtypes[0])
-        dw = (_mx8_dequant(*_mx8_codes(gz.t(), "e5m2"), "e5m2") @ xtq.t()).to(ctx.dtypes[1])
+            dx = (ctx.roundtrip(gz, "e5m2") @ wtq.t()).reshape(ctx.xshape).to(ctx.dtypes[0])
+        dw = (ctx.roundtrip(gz.t(), "e5m2") @ xtq.t()).to(ctx.dtypes[1])
         db = gz.float().sum(0) if ctx.has_bias else None
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def linear_act(x, weight, bias=None, act: str = "none", flat=None, compute_dtype: str = "bf16"):
@@ -548,15 +469,15 @@ def linear_act(x, weight, bias=None, act: str = "none", flat=None, compute_dtype
     a = ACTS[act]
     if compute_dtype not in LINEAR_DTYPES:
         raise ValueError(f"linear_act: compute_dtype must be one of {LINEAR_DTYPES}, got {compute_dtype!r}")
+    scheme = {"bf16": None, "fp8": _FP8, "mxfp8": _MX8}[compute_dtype]
     if _ext.use_native(x):
         if flat is None or flat.shadow is None:
             raise RuntimeError("native Linear needs the model attached to FlatParams (ldnn.prepare(model))")
-        fn = {"bf16": _LinearActNative, "fp8": _LinearActFp8Native, "mxfp8": _LinearActMx8Native}[compute_dtype]
-        return fn.apply(x, weight, bias, a, flat)
-    if compute_dtype == "fp8":
-        return _LinearActFp8Twin.apply(x, weight, bias, a)
-    if compute_dtype == "mxfp8":
-        return _LinearActMx8Twin.apply(x, weight, bias, a)
+        if scheme is None:
+            return _LinearActNative.apply(x, weight, bias, a, flat)
+        return _LinearActQuantNative.apply(x, weight, bias, a, flat, scheme)
+    if scheme is not None:
+        return _LinearActQuantTwin.apply(x, weight, bias, a, scheme.roundtrip)
     y = F.linear(x.float(), weight, bias)
     if a == 0:
         y = F.relu(y)

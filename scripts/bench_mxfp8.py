@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Rates of the mxfp8 Linear's kernels (quant_mx8.hip, gemm_mx8.hip) beside the per-tensor fp8 path and bf16, at a
+"""Rates of the mxfp8 Linear's kernels (quant_mx8.hip, gemm_f8.hip) beside the per-tensor fp8 path and bf16, at a
 4096 x 4096 hidden layer and batch 4096.  The variants alternate inside one process (HIP events around single
 launches, medians of --reps); every record is one JSON line, printed and appended to <out>/bench_mxfp8.jsonl.
 
