@@ -125,6 +125,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--separable: the 3x3 of every separable block mixes W neighbouring channels (a grouped "
                         "convolution on the matrix pipe, gconv.hip) instead of none (1, depthwise, the default): "
                         "9 (W - 1) more weights per channel (enhanced_cnn at 16: 6,569,546 parameters)")
+    p.add_argument("--se_ratio", type=int, default=0, metavar="R",
+                   help="the EnhancedCNNs with a Squeeze-and-Excitation gate (Hu et al. 2018) in every residual block: "
+                        "global average pool, two small Linear layers with max(8, C / R) hidden units, a sigmoid, and "
+                        "the per-channel scale fused with the block's residual add and ReLU (native NHWC bf16 passes, "
+                        "se.hip; enhanced_cnn at 16: 44,948,026 parameters).  R must divide every block width; 0 "
+                        "(default): none; every other model refuses it")
     p.add_argument("--linear_dtype", choices=["bf16", "fp8", "mxfp8"], default="bf16",
                    help="fp8: the MLPs' hidden Linear layers run their three GEMMs (forward, dgrad, wgrad) on the "
                         "gfx950 fp8 matrix instruction (gemm_f8.hip): e4m3 activations and weights, e5m2 gradients, "
@@ -411,7 +417,7 @@ def main(argv=None):
     for flag, v in (("--mix_prob", args.mix_prob), ("--mix_switch_prob", args.mix_switch_prob)):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} must be in [0, 1], got {v}")
-    from .models import FP8_LINEAR_MODELS, LAYER_NORM_MODELS, NORM_MODELS, SEPARABLE_MODELS
+    from .models import FP8_LINEAR_MODELS, LAYER_NORM_MODELS, NORM_MODELS, SE_MODELS, SEPARABLE_MODELS
     if args.linear_dtype != "bf16" and args.model not in FP8_LINEAR_MODELS:
         raise SystemExit(f"--linear_dtype {args.linear_dtype}: the fp8 Linear is built for the hidden layers of the MLPs "
                          f"({', '.join(FP8_LINEAR_MODELS)}), not for --model {args.model}")
@@ -421,6 +427,11 @@ def main(argv=None):
     if args.group_width != 1 and not args.separable:
         raise SystemExit(f"--group_width {args.group_width}: the group width is the separable blocks' 3x3; "
                          "give --separable as well")
+    if args.se_ratio < 0:
+        raise SystemExit(f"--se_ratio must be >= 0, got {args.se_ratio}")
+    if args.se_ratio and args.model not in SE_MODELS:
+        raise SystemExit(f"--se_ratio {args.se_ratio}: the Squeeze-and-Excitation blocks are built for "
+                         f"{', '.join(SE_MODELS)}, not for --model {args.model}")
     if args.norm == "layer" and args.model not in LAYER_NORM_MODELS:
         raise SystemExit(f"--norm layer: LayerNorm is built for the MLPs ({', '.join(LAYER_NORM_MODELS)}), "
                          f"not for --model {args.model}")
@@ -459,8 +470,8 @@ def main(argv=None):
     try:
         model = build_model(args.model, dropout=args.dropout, norm=args.norm, gn_groups=args.gn_groups,
                             separable=args.separable, group_width=args.group_width,
-                            linear_dtype=args.linear_dtype)
-    except ValueError as e:   # (a --gn_groups that does not divide a width)
+                            linear_dtype=args.linear_dtype, se_ratio=args.se_ratio)
+    except ValueError as e:   # (a --gn_groups or --se_ratio that does not divide a width)
         raise SystemExit(str(e))
     xavier_init(model)
     use_engine = resolve_engine(args, model, dev, world)

@@ -1936,6 +1936,65 @@ void gn_bwd(const at::Tensor& x, const at::Tensor& dy, const at::Tensor& dx, con
         "gn_backward");
 }
 
+// ---- Squeeze-and-Excitation: u, y, residual, dy, du, dres dense NHWC bf16 [N][H][W][C]; the parameters and their
+// gradients are the padded fp32 storages w1 [Chp][C], b1 [Chp], w2 [C][Chp], b2 [C]
+ldnn::SeArgs se_args(const at::Tensor& u, const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& gate,
+                     int64_t Ch, bool relu, const c10::optional<at::Tensor>& mask) {
+  check_dev(u, at::kBFloat16, "u");
+  TORCH_CHECK(u.dim() == 4 && u.is_contiguous() && u.numel() > 0, "se: u must be dense NHWC [N][H][W][C]");
+  TORCH_CHECK(aligned16(u.data_ptr()), "se: u must be 16-byte aligned");
+  const int64_t N = u.size(0), P = u.size(1) * u.size(2), C = u.size(3);
+  TORCH_CHECK(C % 8 == 0, "se: C must be a multiple of 8, got ", C);
+  TORCH_CHECK(N <= 65535 && C <= ldnn::se_max_channels(), "se: at most 65535 samples and ", ldnn::se_max_channels(),
+              " channels");
+  TORCH_CHECK(Ch >= 1 && Ch <= C, "se: ", Ch, " hidden units for ", C, " channels");
+  const int64_t Chp = (Ch + 7) / 8 * 8;
+  ldnn::SeArgs a{};
+  a.u = bf16_ptr(u);
+  a.N = N, a.P = P, a.C = (int)C, a.Ch = (int)Ch;
+  a.relu = relu ? 1 : 0;
+  a.w1 = fptr_opt(w1, Chp * C, "w1", &u, true);
+  a.w2 = fptr_opt(w2, C * Chp, "w2", &u, true);
+  a.gate = fptr_opt(gate, ldnn::se_workspace_floats(N, (int)C, (int)Ch), "gate", &u, true);
+  TORCH_CHECK(!mask.has_value() || (relu && mask->device() == u.device()), "se: mask needs relu, u's device");
+  a.mask = relu_mask(mask, u.numel(), "se");
+  return a;
+}
+
+void se_fwd(const at::Tensor& u, const at::Tensor& y, const c10::optional<at::Tensor>& residual, const at::Tensor& w1,
+            const at::Tensor& b1, const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& gate, int64_t Ch,
+            bool relu, const c10::optional<at::Tensor>& mask) {
+  ldnn::SeArgs a = se_args(u, w1, w2, gate, Ch, relu, mask);
+  a.y = const_cast<uint16_t*>(gn_act(y, u, "y"));
+  TORCH_CHECK(y.data_ptr() != u.data_ptr(), "se_fwd: in-place is not supported");
+  if (residual.has_value()) a.residual = gn_act(*residual, u, "residual");
+  a.b1 = fptr_opt(b1, (Ch + 7) / 8 * 8, "b1", &u);
+  a.b2 = fptr_opt(b2, u.size(3), "b2", &u);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(u.device());
+  check(ldnn::se_forward(a, cur_stream(u)), "se_forward");
+}
+
+void se_bwd(const at::Tensor& u, const at::Tensor& dy, const at::Tensor& du, const c10::optional<at::Tensor>& dres,
+            const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& gate, const at::Tensor& ws,
+            const at::Tensor& dw1, const at::Tensor& db1, const at::Tensor& dw2, const at::Tensor& db2, int64_t Ch,
+            bool relu, const c10::optional<at::Tensor>& mask, int64_t store) {
+  ldnn::SeArgs a = se_args(u, w1, w2, gate, Ch, relu, mask);
+  TORCH_CHECK(relu == mask.has_value(), "se_bwd: the backward of a relu forward reads its bit mask");
+  TORCH_CHECK(store >= 0 && store < 16, "se_bwd: store is a mask of the four SeStore bits");
+  const int64_t C = u.size(3), Chp = (Ch + 7) / 8 * 8;
+  a.ws = fptr_opt(ws, ldnn::se_workspace_floats(u.size(0), (int)C, (int)Ch), "ws", &u, true);
+  TORCH_CHECK(a.ws != a.gate, "se_bwd: ws must not be the forward's gate buffer");
+  const uint16_t* g = gn_act(dy, u, "dy");
+  uint16_t* d = const_cast<uint16_t*>(gn_act(du, u, "du"));
+  uint16_t* dr = dres.has_value() ? const_cast<uint16_t*>(gn_act(*dres, u, "dres")) : nullptr;
+  TORCH_CHECK(d != a.u && d != g && dr != d, "se_bwd: in-place is not supported");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
+  check(ldnn::se_backward(a, g, d, dr, fptr_opt(dw1, Chp * C, "dw1", &u, true), fptr_opt(db1, Chp, "db1", &u, true),
+                          fptr_opt(dw2, C * Chp, "dw2", &u, true), fptr_opt(db2, C, "db2", &u, true), (int)store,
+                          cur_stream(u)),
+        "se_backward");
+}
+
 // ---- depthwise 3x3 conv, padding 1: x / dx [N][H][W][Cp], y / dy [N][P][Q][Cp] dense NHWC bf16; w / dw the
 // bf16 / fp32 KRSC storage [Cp][3][3][8] of a [C,1,3,3] parameter
 void dw_check(const at::Tensor& x, const at::Tensor& y, int64_t stride, const char* who) {
@@ -2992,6 +3051,18 @@ PYBIND11_MODULE(_C, m) {
         py::arg("N"), py::arg("P"), py::arg("C"), py::arg("G"));
   m.def("gn_slabs", &ldnn::gn_slabs, "pixel slabs per sample of the GroupNorm statistics passes", py::arg("N"),
         py::arg("P"), py::arg("C"), py::arg("G"));
+  m.def("se_fwd", &se_fwd, "y = relu?(s * u (+ residual)), s = sigmoid(W2 relu(W1 mean_hw(u) + b1) + b2), over dense "
+        "NHWC bf16; writes z | s | h into gate for the backward",
+        py::arg("u"), py::arg("y"), py::arg("residual"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+        py::arg("gate"), py::arg("hidden"), py::arg("relu"), py::arg("mask") = py::none());
+  m.def("se_bwd", &se_bwd, "backward of se_fwd: du, optional dres, the four parameter gradients stored (store bits "
+        "1 w1, 2 b1, 4 w2, 8 b2) or added",
+        py::arg("u"), py::arg("dy"), py::arg("du"), py::arg("dres"), py::arg("w1"), py::arg("w2"), py::arg("gate"),
+        py::arg("ws"), py::arg("dw1"), py::arg("db1"), py::arg("dw2"), py::arg("db2"), py::arg("hidden"),
+        py::arg("relu"), py::arg("mask") = py::none(), py::arg("store") = 0);
+  m.def("se_workspace_floats", &ldnn::se_workspace_floats, "fp32 elements of se_fwd's gate and of se_bwd's ws",
+        py::arg("N"), py::arg("C"), py::arg("hidden"));
+  m.def("se_max_channels", &ldnn::se_max_channels, "the widest C the Squeeze-and-Excitation kernels take");
   m.def("dwconv_fwd", &dwconv_fwd, "depthwise 3x3 / pad 1 conv over dense NHWC bf16: y = relu?(x * w (+ bias))",
         py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stride"), py::arg("bias") = py::none(),
         py::arg("relu") = false);

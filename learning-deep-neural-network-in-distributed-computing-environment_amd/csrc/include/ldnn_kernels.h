@@ -396,6 +396,35 @@ hipError_t gn_forward(const GnArgs& a, hipStream_t s);
 hipError_t gn_backward(const GnArgs& a, const uint16_t* dy, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
                        bool grad_assign, hipStream_t s);
 
+// ---- Squeeze-and-Excitation on dense NHWC bf16 [N][P][C] (se.hip), C % 8 == 0, C <= se_max_channels()
+//   z = mean_p u,  h = relu(W1 z + b1),  s = sigmoid(W2 h + b2),  y = relu?(s * u (+ residual))
+// Ch hidden units (1 <= Ch <= C), Chp = Ch rounded up to 8.  The parameters and their gradients are the
+// padded fp32 storages W1 [Chp][C], b1 [Chp], W2 [C][Chp], b2 [C].  No atomics: a shape has one summation order.
+struct SeArgs {
+  const uint16_t* u;          // [N][P][C] input
+  const uint16_t* residual;   // optional [N][P][C] added before the ReLU (forward)
+  uint16_t* y;                // [N][P][C] output (forward)
+  const float* w1;
+  const float* b1;            // (forward)
+  const float* w2;
+  const float* b2;            // (forward)
+  float* gate;                // [se_workspace_floats] z | s | h: written by the forward, read by the backward
+  float* ws;                  // [se_workspace_floats] scratch of the backward, nothing to zero or keep
+  uint8_t* mask;              // [N*P*C/8] ReLU bits in bn_fwd's layout, as GnArgs::mask
+  int64_t N, P;
+  int C, Ch;
+  int relu;
+};
+// se_backward's `store` bits: the parameter's gradient is stored (the step's first write; pad rows and
+// columns become exactly 0) instead of added
+enum SeStore : int { SE_STORE_W1 = 1, SE_STORE_B1 = 2, SE_STORE_W2 = 4, SE_STORE_B2 = 8 };
+int se_max_channels();
+int64_t se_workspace_floats(int64_t N, int C, int Ch);   // the size of gate, and of ws
+hipError_t se_forward(const SeArgs& a, hipStream_t s);
+// du, optionally dres = the masked dy, and the four parameter gradients
+hipError_t se_backward(const SeArgs& a, const uint16_t* dy, uint16_t* du, uint16_t* dres, float* dw1, float* db1,
+                       float* dw2, float* db2, int store, hipStream_t s);
+
 // ---- LayerNorm over the last dimension of a logical [B][N] bf16 matrix (layer_norm.hip), activation fused
 // Row strides ld >= N in elements, ld % 8 == 0, bases 16-byte aligned; N <= ln_max_width(), any N >= 1
 // (the last vector's lanes beyond N are selected away and may hold anything, NaN included).  The

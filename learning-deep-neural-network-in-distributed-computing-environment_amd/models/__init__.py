@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from .cnn import EnhancedCNNModel, EnhancedCNNSmall, LeNet5, ResBlock, SeparableConv2d  # noqa: F401
 from .layers import (NORMS, CrossEntropyLoss, Dropout, FocalLoss, GroupNorm, LayerNorm, Linear,  # noqa: F401
-                     WeightedCrossEntropyLoss, reseed_dropout)
+                     SqueezeExcite, WeightedCrossEntropyLoss, reseed_dropout)
 from .mlp import MLP, mlp2, mlp3  # noqa: F401
 from .resnet import ResNet, resnet18  # noqa: F401
 
@@ -33,11 +33,13 @@ FP8_LINEAR_MODELS = ("mlp2", "mlp3", "mlp3_small")
 SEPARABLE_MODELS = ("enhanced_cnn", "enhanced_cnn_small")
 # the group widths of a separable variant's 3x3 beside 1 (depthwise): build_model(..., group_width=)
 GROUP_WIDTHS = (8, 16, 32)
+# the models whose residual blocks take a Squeeze-and-Excitation gate (se_ratio > 0)
+SE_MODELS = ("enhanced_cnn", "enhanced_cnn_small")
 
 
 def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0, norm: str = "batch",
                 gn_groups: int = 32, separable: bool = False, linear_dtype: str = "bf16",
-                group_width: int = 1) -> nn.Module:
+                group_width: int = 1, se_ratio: int = 0) -> nn.Module:
     """``dropout``: the rate of the model's Dropout modules (MLPs: after every hidden layer; LeNet-5:
     after fc1 and fc2; the ResNets and EnhancedCNNs: in front of the classifier).  0: none exist.
     ``norm``: "batch" (BatchNorm2d, the default) or "group" (GroupNorm with ``gn_groups`` groups under
@@ -52,7 +54,10 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
     a grouped convolution, ``dw.weight`` [C, group_width, 3, 3] under the same keys).
     ``linear_dtype``: "bf16" (the default), "fp8" (per-tensor scales) or "mxfp8" (one scale per block of 32): the
     MLPs' hidden Linear layers run their three GEMMs on fp8 codes (the output layer stays bf16; modules and keys are
-    the default's); every other model refuses it."""
+    the default's); every other model refuses it.
+    ``se_ratio``: R > 0 gives every residual block of the EnhancedCNNs a Squeeze-and-Excitation gate with
+    max(8, C // R) hidden units (``se.fc1.weight`` / ``se.fc1.bias`` / ``se.fc2.weight`` / ``se.fc2.bias`` beside the
+    default's keys); 0, the default, builds none; every other model refuses it."""
     ctor, _ = REGISTRY[name]
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
@@ -88,6 +93,13 @@ def build_model(name: str, num_classes: int | None = None, dropout: float = 0.0,
             raise ValueError(f"linear_dtype={linear_dtype!r}: the fp8 Linear is built for the hidden layers of the MLPs "
                              f"({', '.join(FP8_LINEAR_MODELS)}), not for {name}")
         kw.update(linear_dtype=linear_dtype)
+    if se_ratio:
+        if se_ratio < 0:
+            raise ValueError(f"se_ratio must be >= 0, got {se_ratio!r}")
+        if name not in SE_MODELS:
+            raise ValueError(f"se_ratio={se_ratio}: the Squeeze-and-Excitation blocks are built for "
+                             f"{', '.join(SE_MODELS)}, not for {name}")
+        kw.update(se_ratio=se_ratio)
     return ctor(**kw) if num_classes is None else ctor(num_classes, **kw)
 
 

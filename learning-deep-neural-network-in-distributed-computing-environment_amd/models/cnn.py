@@ -14,8 +14,8 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..ops import functional as LF
-from .layers import (AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, make_norm,
-                     pair_conv_bn)
+from .layers import (AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d, ReLU, SqueezeExcite,
+                     make_norm, pair_conv_bn)
 
 
 class ConvBNReLU(nn.Sequential):
@@ -53,10 +53,11 @@ class ResBlock(nn.Module):
     changes) -> add -> ReLU; convs without bias (BAR/model.py:52-72).  ``norm="group"``: a
     GroupNorm under every BN's attribute name (bn1, bn2, shortcut.1).  ``separable``: conv1 and conv2
     are ``SeparableConv2d`` (keys conv1.dw.weight / conv1.pw.weight); the shortcut conv then runs as
-    its own launch."""
+    its own launch.  ``se_ratio`` R > 0: a ``SqueezeExcite(out_channels, R)`` under ``se`` gates the main
+    branch before the add, relu(s * bn2(conv2(.)) + shortcut), in the standard SE-ResNet placement."""
 
     def __init__(self, in_channels, out_channels, stride=1, norm: str = "batch", gn_groups: int = 32,
-                 separable: bool = False, group_width: int = 1):
+                 separable: bool = False, group_width: int = 1, se_ratio: int = 0):
         super().__init__()
         if separable:
             self.conv1 = SeparableConv2d(in_channels, out_channels, stride, group_width)
@@ -77,6 +78,9 @@ class ResBlock(nn.Module):
         self.relu = ReLU()
         self.group_norm = norm == "group"
         self.separable = separable
+        self.se_ratio = se_ratio
+        if se_ratio:   # (none constructed at ratio 0: named_modules() stay the reference's)
+            self.se = SqueezeExcite(out_channels, se_ratio)
         if not self.group_norm:
             pair_conv_bn(self.conv1.pw if separable else self.conv1, self.bn1)
             pair_conv_bn(self.conv2.pw if separable else self.conv2, self.bn2)
@@ -90,6 +94,16 @@ class ResBlock(nn.Module):
         return LF.conv2d_pair(x, LF.shortcut_input(x), self.conv1, self.shortcut[0])
 
     def forward(self, x):
+        if self.se_ratio:
+            # either norm: norm2 without add or ReLU, the shortcut's norm output (or x) as the residual of
+            # the SE pass, which gates, adds and applies the ReLU.  No twins: autograd sums x's two gradients
+            if len(self.shortcut):
+                c1, sc = self._conv1_shortcut(x)
+                res = self.shortcut[1].act(sc)
+            else:
+                c1, res = self.conv1(x), LF.shortcut_input(x)
+            u = self.bn2.act(self.conv2(self.bn1.act(c1, relu=True)))
+            return self.se.act(u, residual=res, relu=True)
         if self.group_norm:
             # conv -> gn(+ReLU), conv -> gn(+ residual + ReLU); the shortcut's GroupNorm output is
             # the residual of the main branch's pass.  No twins: autograd sums x's two gradients
@@ -123,9 +137,9 @@ def _head(x, pool, fc, drop=None):
 
 class EnhancedCNNModel(nn.Module):
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32, separable: bool = False, group_width: int = 1):
+                 gn_groups: int = 32, separable: bool = False, group_width: int = 1, se_ratio: int = 0):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width, se_ratio=se_ratio)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),
@@ -153,9 +167,9 @@ class EnhancedCNNSmall(nn.Module):
     """The reference's commented-out smaller model (BAR/model.py:4-50)."""
 
     def __init__(self, num_classes: int = 10, in_channels: int = 3, dropout: float = 0.0, norm: str = "batch",
-                 gn_groups: int = 32, separable: bool = False, group_width: int = 1):
+                 gn_groups: int = 32, separable: bool = False, group_width: int = 1, se_ratio: int = 0):
         super().__init__()
-        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width)
+        nk = dict(norm=norm, gn_groups=gn_groups, separable=separable, group_width=group_width, se_ratio=se_ratio)
         self.prep = ConvBNReLU(
             Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1, bias=False),
             make_norm(norm, 64, gn_groups),

@@ -324,6 +324,31 @@ def make_norm(norm: str, channels: int, gn_groups: int = 32):
     return GroupNorm(gn_groups, channels)
 
 
+class SqueezeExcite(nn.Module):
+    """The channel gate of Hu et al. 2018 over [N, C, H, W]: ``s = sigmoid(fc2(relu(fc1(mean over h, w))))``,
+    one value per sample and channel, with ``fc1`` a ``Linear(C, Ch)`` and ``fc2`` a ``Linear(Ch, C)``,
+    ``Ch = max(8, C // ratio)``.  The two are the package's ``Linear`` (keys fc1.weight, fc1.bias, fc2.weight,
+    fc2.bias), so initialisation, checkpoints and the optimizers treat them like any Linear; their forward is
+    never called: ``act`` runs the whole gate, the scaling, a residual add and a ReLU in the native kernels
+    (se.hip) on the GPU."""
+
+    def __init__(self, channels: int, ratio: int = 16):
+        super().__init__()
+        if ratio < 1 or channels % ratio:
+            raise ValueError(f"se_ratio={ratio} does not divide the {channels} channels of a residual block")
+        hidden = max(8, channels // ratio)
+        self.fc1 = Linear(channels, hidden)
+        self.fc2 = Linear(hidden, channels)
+        self._ldnn_flat = None
+
+    def forward(self, u):
+        return LF.se_scale_act(u, self)
+
+    def act(self, u, residual=None, relu: bool = False):
+        """relu?(s * u + residual) in one fused pass."""
+        return LF.se_scale_act(u, self, residual, relu)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def forward(self, x):
         return LF.pool2d(x, self, True)

@@ -1471,6 +1471,83 @@ def group_norm_act(x, mod, residual=None, relu: bool = False):
     return y.to(torch.bfloat16) if x.is_cuda and x.dtype == torch.bfloat16 else y
 
 
+# ------------------------------------------------------------------ Squeeze-and-Excitation
+class _SqueezeExciteNative(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, w1, b1, w2, b2, residual, mod, flat, relu):
+        C_ = _ext.C()
+        N, C, H, W = u.shape
+        Ch, dev = w1.shape[0], u.device
+        ub = u.as_strided((N, H, W, C), (H * W * C, W * C, C, 1), u.storage_offset())
+        rb = None
+        if residual is not None:
+            rb = as_nhwc(_to_bf16(residual), C, zero_pad=False)
+        y = torch.empty(N, H, W, C, dtype=torch.bfloat16, device=dev)
+        gate = torch.empty(C_.se_workspace_floats(N, C, Ch), dtype=torch.float32, device=dev)   # z | s | h
+        # the ReLU leaves a bit mask for the backward (which then never reads y); only when one will run
+        mask = (torch.empty(N * H * W * C // 8, dtype=torch.uint8, device=dev)
+                if relu and any(ctx.needs_input_grad) else None)
+        C_.se_fwd(ub, y, rb, flat.master_storage(w1), flat.master_storage(b1), flat.master_storage(w2),
+                  flat.master_storage(b2), gate, Ch, relu, mask=mask)
+        ctx.save_for_backward(ub, gate)
+        ctx.mask = mask
+        ctx.meta = (flat, (w1, b1, w2, b2), mod, residual is not None, residual.dtype if residual is not None else None)
+        ctx.set_materialize_grads(False)
+        return _zpad(nchw_view(y, C))
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return (None,) * 9
+        C_ = _ext.C()
+        ub, gate = ctx.saved_tensors
+        flat, params, mod, has_res, res_dtype = ctx.meta
+        w1, b1, w2, b2 = params
+        N, H, W, C = ub.shape
+        Ch = w1.shape[0]
+        g = as_nhwc(_to_bf16(gy), C, zero_pad=False).contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        du = torch.empty_like(ub)
+        dres = torch.empty_like(ub) if has_res and ctx.needs_input_grad[5] else None
+        # a parameter's first write of the step stores instead of adding (bits 1 w1, 2 b1, 4 w2, 8 b2)
+        store = sum(bit for bit, p in zip((1, 2, 4, 8), params) if flat.grad_beta(p) == 0.0)
+        ws = _module_ws(mod, "_ldnn_se_ws", C_.se_workspace_floats(N, C, Ch), ub.device)   # (da2 | dz | dh)
+        C_.se_bwd(ub, g, du, dres, flat.master_storage(w1), flat.master_storage(w2), gate, ws, flat.grad_storage(w1),
+                  flat.grad_storage(b1), flat.grad_storage(w2), flat.grad_storage(b2), Ch, ctx.mask is not None,
+                  mask=ctx.mask, store=store)
+        flat.notify(w2, b2, w1, b1)
+        dresv = _from_bf16(nchw_view(dres, C), res_dtype) if dres is not None else None
+        return _zpad(nchw_view(du, C)), None, None, None, None, dresv, None, None, None
+
+
+def se_scale_act(u, mod, residual=None, relu: bool = False):
+    """relu?(s * u (+ residual)) with the Squeeze-and-Excitation gate of ``mod`` (a ``SqueezeExcite``:
+    ``fc1`` [Ch, C] and ``fc2`` [C, Ch]):  z = mean over h, w of u;  s = sigmoid(fc2(relu(fc1(z)))), one
+    value per sample and channel.  GPU, bf16 activations in the dense NHWC layout the native ops
+    produce, C % 8 == 0: the kernels of se.hip (two launches forward, three backward; fp32 arithmetic,
+    the parameters read from the FlatParams master, their gradients written into the flat gradient
+    buffer).  Everything else -- the CPU, other dtypes or layouts, a module not attached to FlatParams,
+    more than 65535 samples or more channels than the kernels' LDS vectors hold -- is the same formula
+    in fp32 torch ops."""
+    flat = getattr(mod, "_ldnn_flat", None)
+    fc1, fc2 = mod.fc1, mod.fc2
+    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if (_ext.use_native(u) and _dense_nhwc(u) and u.shape[1] % 8 == 0 and u.shape[0] <= 65535
+            and flat is not None and all(id(p) in flat.by_param for p in params)
+            and u.shape[1] == fc1.in_features and u.shape[1] <= _ext.C().se_max_channels()):
+        return _SqueezeExciteNative.apply(u, *params, residual, mod, flat, relu)
+    uf = u.float()
+    z = uf.mean(dim=(2, 3))
+    s = torch.sigmoid(F.linear(F.relu(F.linear(z, fc1.weight, fc1.bias)), fc2.weight, fc2.bias))
+    y = uf * s[:, :, None, None]
+    if residual is not None:
+        y = y + residual
+    if relu:
+        y = F.relu(y)
+    return y.to(torch.bfloat16) if u.is_cuda and u.dtype == torch.bfloat16 else y
+
+
 # ------------------------------------------------------------------ LayerNorm
 def _ln_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else _up8(t.shape[1])   # (a single row's stride is arbitrary)
